@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- SCAN hot path on MI355X: train images/sec, VGG16 C2F, 1024x2048 synthetic frames.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one full domain-adaptation iteration (reference fcos_core/engine/trainer.py:266-424:
 source forward + losses, 5 CKA discriminators on source, target forward, 5 CKA discriminators on
@@ -18,10 +18,26 @@ reference's loaders do (data/build.py:181-188).  Collectives per step: three gra
 contiguous arena ranges on a side stream, the 9x257 paradigm all-reduce, one loss-scalar reduce.
 
 Prints ONE JSON line on rank 0.  `value` = source/target image PAIRS per second over all GPUs
-(frames/s = 2x, in config); `roofline` = the conv kernel with the largest share, timed live with HIP
-events on its stream; `roofline_pointwise` = HBM GB/s of the pointwise kernels (tools/pointwise_roofline.py);
-`cpu_baseline` = the torch-CPU restatement (oracle/scan_ref.py, a port of the reference's CPU path) on this
-host's cores: 1 warm-up + 3 timed iterations at the best thread count of a short sweep.
+(frames/s = 2x, in config); `ms_per_step` = milliseconds of one timed step.  A plain run does only what
+that headline needs: set-up, W warm-up steps, K timed steps, the line.  `--full` adds everything else,
+each part still switchable off by its --no-* option: `roofline` = the conv kernel with the largest share,
+timed live with HIP events on its stream in extra serial steps; the companion legs (exact fp32-MFMA and
+two-piece arithmetics, three-phase schedule, inference, one-rank RCCL, drop-in surface); `roofline_pointwise`
+= HBM GB/s of the pointwise kernels (tools/pointwise_roofline.py); `cpu_baseline` = the torch-CPU
+restatement (oracle/scan_ref.py, a port of the reference's CPU path) on this host's cores: 1 warm-up + 3
+timed iterations at the best thread count of a short sweep.  Without --full these keys are null.
+
+`--dump-outputs DIR`: after the timed steps, the state the run started from (parameters, momentum, module
+buffers, iteration, paradigm counter, torch's generators: capture_state) is put back and ONE more step of
+the timed path runs on the same frames, in the same stream set-up; rank 0 writes what that step returned,
+as DIR/<name>.npy -- every loss (float64, shape [1]) and, per sub-model, its parameters after the SGD
+update (`param_<sub-model>.npy`) and its gradient of the step (`grad_<sub-model>.npy`), float32, at most
+DUMP_MAX_ELEMS elements each: beyond that a fixed sample of the flat buffer, the sorted indices drawn with
+seed DUMP_SEED (dump_index).  Frames, targets, weights and torch's generators (BENCH_SEED) are seeded, so
+that step's inputs are the same in every run, and its outputs agree between two runs to rounding (~2e-7 on
+the losses: some reductions, the GroupNorm sums among them, use float atomics).  The timed steps' own last
+step is not written: it starts from the state W + N - 1 training steps left, and training amplifies those
+rounding differences step by step (~1e-3 on the losses after seven steps), so it differs from run to run.
 """
 import argparse
 import json
@@ -45,6 +61,69 @@ PEAK_BF16X3_TFLOPS = PEAK_BF16_TFLOPS / 3.0
 HEADLINE_MODE = "bf16x6"
 XGMI_LINK_GBS = 153.0  # per link and direction; 7 links per GPU (MI355X_MICROARCH.md)
 RCCL_MAX_NCHANNELS = 32  # launcher default for N > 1 (profiles/r06_dp_emulation.txt: 16-64 resident workgroups cost the step the same, 8 more), see launch_ranks
+BENCH_SEED = 1234  # torch.manual_seed of every run (+ 100 * rank), like the synthetic frames' seeds
+DUMP_MAX_ELEMS = 1 << 19  # per --dump-outputs array: 2 MB of float32, 16 parameter / gradient arrays of the 8 sub-models <= 32 MB
+DUMP_SEED = 0
+
+
+def dump_index(n):
+    """the elements of a flat buffer of n that --dump-outputs writes: all of them up to DUMP_MAX_ELEMS, else a sorted sample
+    drawn with a fixed seed (the same n gives the same indices in every run and on every build)"""
+    import numpy as np
+    if n <= DUMP_MAX_ELEMS:
+        return np.arange(n, dtype=np.int64)
+    return np.unique(np.random.RandomState(DUMP_SEED).randint(0, n, size=DUMP_MAX_ELEMS, dtype=np.int64))
+
+
+def capture_state(trainer):
+    """everything a training step reads and changes besides the frames: per sub-model the flat parameters, momentum and
+    first-step flag, every module buffer (the middle head's prototype), the iteration (learning-rate schedule), the paradigm
+    counter, and torch's generators (attention dropout)"""
+    import torch
+    model = trainer.model
+    return {"groups": {k: (g.flat_p.clone(), g.flat_m.clone(), g.first) for k, g in trainer.groups.items()},
+            "buffers": {k: {n: b.clone() for n, b in m.named_buffers()} for k, m in model.items()},
+            "iteration": trainer.iteration, "counter": model["middle_head"].counter_rnn.counter,
+            "rng": (torch.get_rng_state(), torch.cuda.get_rng_state())}
+
+
+def restore_state(trainer, st):
+    """put a capture_state() snapshot back (in place: parameters and .grad stay views of the flat buffers)"""
+    import torch
+    from scan_amd import ops
+    model = trainer.model
+    torch.cuda.synchronize()
+    for k, g in trainer.groups.items():
+        p, m, first = st["groups"][k]
+        g.flat_p.copy_(p)
+        g.flat_m.copy_(m)
+        g.first = first
+    for k, m in model.items():
+        bufs = dict(m.named_buffers())
+        for n, b in st["buffers"][k].items():
+            bufs[n].copy_(b)
+    trainer.iteration = st["iteration"]
+    model["middle_head"].counter_rnn.counter = st["counter"]
+    torch.set_rng_state(st["rng"][0])
+    torch.cuda.set_rng_state(st["rng"][1])
+    ops.invalidate_weight_planes()  # the cached bf16 planes belong to the trained weights
+    torch.cuda.synchronize()
+
+
+def dump_outputs(out_dir, losses, trainer):
+    """--dump-outputs: the losses of a step and every sub-model's parameters (after its SGD update) and gradient (of that
+    step) as out_dir/<name>.npy; called right after that step, before anything else runs one"""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.array([float(v)], dtype=np.float64) for k, v in losses.items()}
+    for k, g in trainer.groups.items():
+        idx = torch.from_numpy(dump_index(g.flat_p.numel())).to(g.flat_p.device)
+        arrays["param_" + k] = g.flat_p.index_select(0, idx).float().cpu().numpy()
+        arrays["grad_" + k] = g.flat_g.index_select(0, idx).float().cpu().numpy()
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return sum(a.nbytes for a in arrays.values())
 
 
 def csrc_sha1():
@@ -308,7 +387,17 @@ def main():
     ap.add_argument("--serial-streams", action="store_true",
                     help="run everything on one stream (no side-stream overlap): what the per-kernel roofline "
                          "figures and the rocprof summaries under profiles/ are taken with")
+    ap.add_argument("--full", action="store_true",
+                    help="measure beyond the headline: per-kernel roofline (extra serial steps), companion legs, board-sustained "
+                         "MFMA rate, pointwise HBM roofline, CPU baseline (each still subject to its --no-* option).  "
+                         "Off: the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps restore the run's starting state, run one more step and write what it "
+                         "computed (losses, sampled parameters and gradients per sub-model) as DIR/<name>.npy, "
+                         "float32 / float64, rank 0 only")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ  # started by torch.distributed.run
     if not launched and a.gpus > 1:
@@ -359,7 +448,7 @@ def main():
         raise SystemExit("bench.py: SCAN_HIP_LIB selects %s, not the product library scan_amd/libscan_hip.so -- no headline is "
                          "printed from an experiment build (pass --allow-exp-lib for an A/B timing run)" % _lib.LIB_PATH)
     ops.CONV_MODE = a.conv_mode
-    if a.conv_mode != HEADLINE_MODE and not a.no_companions:
+    if a.conv_mode != HEADLINE_MODE and a.full and not a.no_companions:
         raise SystemExit("--conv-mode %s is a profiling aid: combine it with --no-companions" % a.conv_mode)
     if a.ft_positives is not None:
         if not a.forward_target:
@@ -368,13 +457,16 @@ def main():
         condgraph.FT_CANDIDATE_FRACTION = float(a.ft_positives)
     mcfg = engine.CONFIGS[a.model]
     body = mcfg["conv_body"]
+    # torch's generators drive the attention dropout of the middle head: left unseeded their state differs between two
+    # processes (losses 1e-2 apart after one step); seeded, two runs agree to rounding (2e-7 after one step)
+    torch.manual_seed(BENCH_SEED + 100 * rank)
     model = engine.build_model(device=dev, settings=mcfg)
     engine.load_procedural_weights(model, mcfg["num_classes"], body)
     # under torch.distributed.run the data-parallel path (flat-buffer all-reduce on the side stream, paradigm
     # all-reduce) is exercised even with a single rank
     trainer = engine.Trainer(model, settings=mcfg, distributed=True if dist.is_initialized() else None)
     if a.three_phase:
-        if not a.no_companions:
+        if a.full and not a.no_companions:
             raise SystemExit("--three-phase is a profiling aid: combine it with --no-companions")
         trainer.paired = False
 
@@ -411,6 +503,7 @@ def main():
             comm.reduce_loss_dict(losses)
         return losses
 
+    start = capture_state(trainer) if a.dump_outputs else None  # the state the first warm-up step starts from
     for _ in range(a.warmup):
         step()
     barrier()
@@ -420,28 +513,38 @@ def main():
     barrier()
     dt = time.time() - t0
     dt_local = dt
-    # per-kernel roofline figures: HIP events around every conv launch on its stream.  With the side-stream overlap
-    # of the timed region an event pair also spans whatever co-runs on the other streams, so the kernels are timed
-    # in two extra steps with the overlap switched off (same kernels, same shapes; rocprof: profiles/*serial*).
-    set_serial(True)
-    # one untimed step in this schedule first: its allocation pattern differs from the overlapped one, and a first pass
-    # through the caching allocator (hipMalloc) would otherwise land in the serial figure quoted below
-    trainer.step(imgs_s, tg, imgs_t, forward_target=a.forward_target)
-    torch.cuda.synchronize()
-    ops.kernel_timer.enabled = True
-    ops.kernel_timer.reset()
-    roof_steps = 2
-    t0r = time.time()
-    for _ in range(roof_steps):
+    dumped_bytes = None
+    if a.dump_outputs:  # outside the timed region, before any other leg runs a step; every rank steps (collectives)
+        restore_state(trainer, start)
+        del start
+        losses = step()
+        barrier()
+        if rank == 0:
+            dumped_bytes = dump_outputs(a.dump_outputs, losses, trainer)
+    ksum, roof_steps, dtr = {}, 0, None
+    if a.full:
+        # per-kernel roofline figures: HIP events around every conv launch on its stream.  With the side-stream overlap
+        # of the timed region an event pair also spans whatever co-runs on the other streams, so the kernels are timed
+        # in two extra steps with the overlap switched off (same kernels, same shapes; rocprof: profiles/*serial*).
+        set_serial(True)
+        # one untimed step in this schedule first: its allocation pattern differs from the overlapped one, and a first pass
+        # through the caching allocator (hipMalloc) would otherwise land in the serial figure quoted below
         trainer.step(imgs_s, tg, imgs_t, forward_target=a.forward_target)
-    torch.cuda.synchronize()
-    dtr = time.time() - t0r
-    ops.kernel_timer.enabled = False
+        torch.cuda.synchronize()
+        ops.kernel_timer.enabled = True
+        ops.kernel_timer.reset()
+        roof_steps = 2
+        t0r = time.time()
+        for _ in range(roof_steps):
+            trainer.step(imgs_s, tg, imgs_t, forward_target=a.forward_target)
+        torch.cuda.synchronize()
+        dtr = time.time() - t0r
+        ops.kernel_timer.enabled = False
+        ksum = ops.kernel_timer.summary()
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    ksum = ops.kernel_timer.summary()
     finite = all(bool(torch.isfinite(v)) for v in losses.values())
 
     # ---- companion legs (N = 1, headline model only): same frames, same trainer, outside the timed region
@@ -485,7 +588,7 @@ def main():
             ops.CONV_MODE = HEADLINE_MODE
             set_serial(a.serial_streams)
 
-    if world == 1 and not a.no_companions and not a.forward_target:
+    if a.full and world == 1 and not a.no_companions and not a.forward_target:
         # (a) the exact fp32 matrix-core kernels (v_mfma_f32_32x32x2_f32 / 16x16x4_f32 = an fp32 fma chain): the same
         # arithmetic as the headline on the 16x narrower pipe; and the two-piece split (16 significand bits per operand:
         # NARROWER than the reference's arithmetic, 2e-6 on the losses) -- what giving up the third piece would buy
@@ -696,7 +799,7 @@ def main():
                            "random-mantissa operands, 2 s: the socket sits at its 1.4 kW cap at 2.0-2.2 GHz "
                            "(profiles/r04_mfma_peak.txt); the conv kernels run at the same cap (r04_kernel_power_clock.txt)"}
         pointwise = None
-        if not a.no_pointwise and world == 1:
+        if a.full and not a.no_pointwise and world == 1:
             from tools import pointwise_roofline
             del trainer, model, imgs_s, imgs_t
             torch.cuda.empty_cache()
@@ -708,7 +811,7 @@ def main():
                          "kernels": [{k: r[k] for k in ("kernel", "M", "bytes", "us", "GBps", "frac", "fits_llc")}
                                      for r in recs]}
         cpu = None
-        if not a.no_cpu_baseline and a.model == "c2f" and world == 1:  # rank 0 at N=1 only
+        if a.full and not a.no_cpu_baseline and a.model == "c2f" and world == 1:  # rank 0 at N=1 only
             cb = cpu_baseline(H, W)
             cpu = {"value": round(1.0 / cb["best_s"], 5), "unit": "pairs/s", "cores": cb["cores"], "kind": "port",
                    "cpu_model": cb["cpu_model"], "visible_threads": cb["visible_threads"],
@@ -746,7 +849,8 @@ def main():
                        "losses_finite": finite, "rank_ms_per_step": rank_ms,
                        "dp_policy": trainer_policy, "rank0_cpu_binding": binding,
                        "rccl_env": {k: os.environ[k] for k in ("NCCL_MAX_NCHANNELS", "NCCL_MIN_NCHANNELS") if k in os.environ},
-                       "gradient_buckets": buckets, "gradient_buckets_modelled_for_ranks": n_model},
+                       "gradient_buckets": buckets, "gradient_buckets_modelled_for_ranks": n_model,
+                       "full": a.full, "dumped_output_bytes": dumped_bytes},
             "roofline": roof, "roofline_pointwise": pointwise, "cpu_baseline": cpu,
             "strict_fp32": strict, "bf16x3_two_piece": fast, "three_phase_schedule": three_phase, "inference": infer,
             "dp1_nccl": dp1, "extra": {"drop_in": drop_in},

@@ -5,7 +5,7 @@ A="$1"; B="$2"; K="$3"; R=${4:-3}
 for r in $(seq $R); do
   for v in "$A" "$B"; do
     echo -n "[$v] "
-    env $v python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-pointwise --no-companions 2>/dev/null | tail -1 | python3 -c "
+    env $v python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-pointwise --no-companions 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 ks=d['roofline']['all_conv_kernels']

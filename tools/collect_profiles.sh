@@ -11,7 +11,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out
 mkdir -p $O
 cd /tmp
-B="--steps 10 --warmup 3 --no-cpu-baseline --no-pointwise --no-companions"
+B="--full --steps 10 --warmup 3 --no-cpu-baseline --no-pointwise --no-companions"
 rocprofv3 --kernel-trace --stats -d /tmp/p_ov_$$ --output-format csv -- python3 $R/bench.py $B > $O/${TAG}_prof_overlap.log 2>&1
 python3 $R/tools/gpu_idle.py $(find /tmp/p_ov_$$ -name "*kernel_trace.csv" | head -1) > $O/${TAG}_gpu_idle.json 2>/dev/null
 cp $(find /tmp/p_ov_$$ -name "*kernel_stats.csv" | head -1) $O/${TAG}_bench_overlap_kernel_stats.csv

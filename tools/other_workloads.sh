@@ -3,7 +3,7 @@
 TAG=${1:-r04}
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd $R
-F="--no-cpu-baseline --no-pointwise --no-companions --steps 5 --warmup 2"
+F="--full --no-cpu-baseline --no-pointwise --no-companions --steps 5 --warmup 2"
 run() {
   echo "## bench.py $*"
   timeout 600 python3 bench.py $F "$@" 2>/dev/null | tail -1 | python3 -c "
