@@ -307,7 +307,7 @@ int scan_conv3x3_wgrad_bf16x3(const float* x, const scan_pyramid_t* d, int32_t C
  * v_mfma_f32_32x32x2_f32 kernels of scan_conv2d_* (tests/test_gpu_kernels.py::test_conv_error_vs_fp64), on a pipe whose
  * ceiling is 2.5 PFLOP/s / 6 = 417 TFLOP/s fp32-equivalent instead of 157.
  * Arguments as for the _bf16x3 functions with a third plane: wh / wm / wl = scan_weight_split3 planes (same layout and
- * modes as scan_weight_split).  y and mask must be 16-byte aligned, Ns % 4 == 0.
+ * modes as scan_weight_split, plus the Winograd modes 2 / 3 below).  y and mask must be 16-byte aligned, Ns % 4 == 0.
  * scan_conv3x3_gn_bf16x6: clear != 0 zeroes gn_ws first (scan_conv3x3_gn_bf16x3), 0 adds to it (.._gn_acc_bf16x3). */
 int scan_weight_split3(const float* w, int32_t O, int32_t T, int32_t Cs, int32_t mode, void* wh, void* wm, void* wl,
                        int32_t Csw, void* stream);
@@ -338,6 +338,17 @@ int scan_conv1x1_wgrad_bf16x6(const float* x, const scan_pyramid_t* xd, int32_t 
  * 64-channel tile on 16x16-pixel tiles (single-level pyramids with sizes that are multiples of 16), 2064 = on 32x16-pixel
  * tiles (H a multiple of 32 too) */
 int scan_conv3x3_bf16x6_instance(const scan_pyramid_t* d, int32_t Nout);
+/* 1-D Winograd F(2,3) along x for three-piece 3x3 / stride-1 convs: two outputs of a row from four products per ky instead
+ * of six.  wh / wm / wl = scan_weight_split3 planes of mode 2 (forward: [O][12][Csw], tap j * 3 + ky
+ * = sum_kx G[j][kx] w[o][ky * 3 + kx][c], G = [1 0 0; 1/2 1/2 1/2; 1/2 -1/2 1/2; 0 0 1], in fp64, rounded once to fp32)
+ * or mode 3 (data gradient: the same transform of the mode-1 planes, [Cs][12][Csw]); Csw % 32 == 0, Nout > 64.
+ * gn_ws != NULL: GroupNorm(32, 256) sums as scan_conv3x3_gn_bf16x6 (Nout == 256, no mask, relu == 0; clear as there).
+ * No fused pool.  scan_conv3x3_bf16x6_wino: 1 if scan_tune "conv_wino" is on and a launch with these channels takes this
+ * path (0: the caller uses scan_conv3x3_bf16x6 on mode-0 / 1 planes). */
+int scan_conv3x3_wino_bf16x6(const float* x, const scan_pyramid_t* d, int32_t Cs, const void* wh, const void* wm,
+                             const void* wl, int32_t Csw, const float* bias, const float* mask, float* y, int32_t Nout,
+                             int32_t Ns, int32_t relu, float* gn_ws, int32_t clear, void* stream);
+int scan_conv3x3_bf16x6_wino(int32_t Nout, int32_t Csw);
 /* w [Cout][T][Cin_s] -> wt [Cin_s][T][Cout_s] (zero padded) */
 int scan_weight_transpose(const float* w, int32_t Cout, int32_t T, int32_t Cin_s, float* wt, int32_t Cout_s,
                           void* stream);

@@ -63,6 +63,9 @@ SIGNATURES = {
     "scan_conv3x3_bf16x3_instance": (ctypes.c_int, [_PD, c_i32]),
     "scan_conv1x1_bf16x6_instance": (ctypes.c_int, [_PD, c_i32, c_i32]),
     "scan_conv3x3_bf16x6_instance": (ctypes.c_int, [_PD, c_i32]),
+    "scan_conv3x3_bf16x6_wino": (ctypes.c_int, [c_i32, c_i32]),
+    "scan_conv3x3_wino_bf16x6": (ctypes.c_int, [c_vp, _PD, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
+                                                c_vp, c_i32, c_vp]),
     "scan_sigmoid_focal_loss_forward": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i32, c_f32, c_f32, c_vp, c_vp, c_vp]),
     "scan_sigmoid_focal_loss_backward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f32, c_i64, c_i32, c_f32, c_f32, c_vp, c_vp]),
     "scan_iou_loss_forward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),

@@ -20,6 +20,9 @@
 //          2-byte scalars: PMC showed 16x the algorithmic bytes fetched (profiles/r02_pmc_traffic.json).  Now a
 //          workgroup moves a 64 (o) x 64 (c) tile of one tap through LDS: float4 reads along c (256 B per weight row),
 //          a conflict-free transposed LDS read (pitch 65), 16-byte stores along o.
+//   modes 2 / 3 (Winograd F(2,3) planes of modes 0 / 1, 12 taps per row, T = 9): mode 2 as mode 0 (a thread reads the
+//          three source taps of its 8 plane elements), mode 3 as mode 1 with each tile element combined from the three
+//          source taps of its output tap on the read side.
 // Same element arithmetic as weight_split_kernel (conv_bf16x3.hip): bit-identical planes.
 #define SPLIT_ELEMS_PER_BLOCK 2048
 #define SPLIT_TILE 64
@@ -55,6 +58,24 @@ __global__ __launch_bounds__(256) void weight_split_batched_kernel(const int64_t
             Csw = (int)job[8];
   const int64_t blk = (int64_t)blockIdx.x - job[9];
   const int tid = threadIdx.x;
+  if (mode == 2) {
+    const int64_t total = (int64_t)rows * 12 * Csw;
+    const int64_t i = blk * SPLIT_ELEMS_PER_BLOCK + (int64_t)tid * 8;
+    if (i >= total) return;
+    const int col = (int)(i % Csw);
+    const int64_t rt = i / Csw;  // row * 12 + (j * 3 + ky)
+    const int tt = (int)(rt % 12), row = (int)(rt / 12);
+    const int j = tt / 3, ky = tt - 3 * j;
+    const float* src = w + ((int64_t)row * T + ky * 3) * Cs + col;
+    float v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const bool in = col + k < Cs;
+      v[k] = wino_g(j, in ? src[k] : 0.f, in ? src[Cs + k] : 0.f, in ? src[2 * Cs + k] : 0.f);
+    }
+    split8_store(v, wh, wl, w2, i);
+    return;
+  }
   if (mode == 0) {
     // plane rows are Csw (a multiple of 8) long, so an 8-element group never straddles two rows
     const int64_t total = (int64_t)rows * T * Csw;
@@ -76,11 +97,12 @@ __global__ __launch_bounds__(256) void weight_split_batched_kernel(const int64_t
     split8_store(v, wh, wl, w2, i);
     return;
   }
-  // mode 1: block -> (tap tt of the OUTPUT, c tile, o tile)
+  // modes 1 / 3: block -> (tap tt of the OUTPUT, c tile, o tile)
   const int tiles_o = (Csw + SPLIT_TILE - 1) / SPLIT_TILE, tiles_c = (rows + SPLIT_TILE - 1) / SPLIT_TILE;
   const int to = (int)(blk % tiles_o);
   const int tc = (int)((blk / tiles_o) % tiles_c);
   const int tt = (int)(blk / ((int64_t)tiles_o * tiles_c));
+  const int TO = mode == 3 ? 12 : T;  // taps per plane row
   const int o0 = to * SPLIT_TILE, c0 = tc * SPLIT_TILE;
   {  // read: 16 lanes x float4 along c per weight row, 16 rows per pass
     const int cl = (tid & 15) * 4, ol = tid >> 4;
@@ -89,14 +111,27 @@ __global__ __launch_bounds__(256) void weight_split_batched_kernel(const int64_t
       const int o = o0 + ol + 16 * p, c = c0 + cl;
       float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
       if (o < O && c < Cs) {
-        const float* src = w + ((int64_t)o * T + (T - 1 - tt)) * Cs + c;
-        if (c + 4 <= Cs && (Cs & 3) == 0) {
-          a = *reinterpret_cast<const float4*>(src);
+        auto read4 = [&](int t) {  // source tap t of weight row o at channels c .. c + 3
+          const float* src = w + ((int64_t)o * T + t) * Cs + c;
+          float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (c + 4 <= Cs && (Cs & 3) == 0) {
+            r = *reinterpret_cast<const float4*>(src);
+          } else {
+            r.x = src[0];
+            if (c + 1 < Cs) r.y = src[1];
+            if (c + 2 < Cs) r.z = src[2];
+            if (c + 3 < Cs) r.w = src[3];
+          }
+          return r;
+        };
+        if (mode == 1) {
+          a = read4(T - 1 - tt);
         } else {
-          a.x = src[0];
-          if (c + 1 < Cs) a.y = src[1];
-          if (c + 2 < Cs) a.z = src[2];
-          if (c + 3 < Cs) a.w = src[3];
+          // Winograd tap (j, ky) of the flipped kernel: source taps 8 - (ky * 3 + kx), kx = 0..2
+          const int j = tt / 3, ky = tt - 3 * j;
+          const float4 g0 = read4(8 - ky * 3), g1 = read4(7 - ky * 3), g2 = read4(6 - ky * 3);
+          a = make_float4(wino_g(j, g0.x, g1.x, g2.x), wino_g(j, g0.y, g1.y, g2.y), wino_g(j, g0.z, g1.z, g2.z),
+                          wino_g(j, g0.w, g1.w, g2.w));
         }
       }
       float* t = &tile[ol + 16 * p][cl];
@@ -113,16 +148,17 @@ __global__ __launch_bounds__(256) void weight_split_batched_kernel(const int64_t
         float v[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) v[k] = tile[o8 + k][cl + 32 * p];
-        split8_store(v, wh, wl, w2, ((int64_t)c * T + tt) * Csw + o);
+        split8_store(v, wh, wl, w2, ((int64_t)c * TO + tt) * Csw + o);
       }
     }
   }
 }
 
 extern "C" int64_t scan_weight_split_job_blocks(int32_t O, int32_t T, int32_t Cs, int32_t mode, int32_t Csw) {
-  if (mode == 0) return ((int64_t)O * T * Csw + SPLIT_ELEMS_PER_BLOCK - 1) / SPLIT_ELEMS_PER_BLOCK;
+  const int64_t TO = mode >= 2 ? 12 : T;  // taps per plane row (modes 2 / 3: the Winograd planes of a T = 9 weight)
+  if (mode == 0 || mode == 2) return ((int64_t)O * TO * Csw + SPLIT_ELEMS_PER_BLOCK - 1) / SPLIT_ELEMS_PER_BLOCK;
   const int64_t tiles_o = (Csw + SPLIT_TILE - 1) / SPLIT_TILE, tiles_c = (Cs + SPLIT_TILE - 1) / SPLIT_TILE;
-  return tiles_o * tiles_c * T;
+  return tiles_o * tiles_c * TO;
 }
 
 extern "C" int scan_weight_split_batched(const int64_t* jobs, int32_t n_jobs, int32_t job_words, int64_t total_blocks,

@@ -339,20 +339,33 @@ __global__ __launch_bounds__(NT, NT == 512 ? 2 : 3) void conv3x3_bf16x3_kernel(
 // w [O][T][Cs] fp32 -> NP bf16 planes (conv_split.h).
 //   mode 0: out[o][t][c]            (O rows, row length Csw >= Cs, zero padded)       -- forward
 //   mode 1: out[c][T-1-t][o]        (Cs rows, row length Csw >= O, zero padded)       -- dgrad (flip + transpose)
+//   modes 2 / 3 (T = 9 only): the Winograd F(2,3) planes of modes 0 / 1 -- 12 taps j * 3 + ky per row, tap (j, ky) =
+//           sum_kx G[j][kx] * (mode 0 / 1 value of tap ky * 3 + kx), in fp64, rounded once to fp32, then split
+//           (conv_fwd.hip, WINO)
 template <int NP>
 __global__ void weight_split_kernel(const float* __restrict__ w, int O, int T, int Cs, int mode, int rows, int Csw,
                                     __bf16* __restrict__ w0, __bf16* __restrict__ w1, __bf16* __restrict__ w2) {
-  const int64_t total = (int64_t)rows * T * Csw;
+  const int TO = mode >= 2 ? 12 : T;  // taps per plane row
+  const int64_t total = (int64_t)rows * TO * Csw;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int col = (int)(i % Csw);
     const int64_t rt = i / Csw;
-    const int tt = (int)(rt % T);
-    const int row = (int)(rt / T);
+    const int tt = (int)(rt % TO);
+    const int row = (int)(rt / TO);
     float v = 0.f;
     if (mode == 0) {
       if (col < Cs) v = w[((int64_t)row * T + tt) * Cs + col];
-    } else {
+    } else if (mode == 1) {
       if (col < O) v = w[((int64_t)col * T + (T - 1 - tt)) * Cs + row];
+    } else {
+      const int j = tt / 3, ky = tt - 3 * j;
+      double g[3] = {0.0, 0.0, 0.0};
+      for (int kx = 0; kx < 3; ++kx) {
+        const int t = ky * 3 + kx;
+        if (mode == 2 && col < Cs) g[kx] = w[((int64_t)row * T + t) * Cs + col];
+        if (mode == 3 && col < O) g[kx] = w[((int64_t)col * T + (T - 1 - t)) * Cs + row];
+      }
+      v = wino_g(j, g[0], g[1], g[2]);
     }
     __bf16 q[NP];
     split1_np<NP>(v, q);
@@ -394,11 +407,12 @@ static void make_tiles(const scan_pyramid_t* d, TileTab* tt, int TH) {
 static int weight_split_launch(int np, const float* w, int32_t O, int32_t T, int32_t Cs, int32_t mode, void* w0, void* w1,
                                void* w2, int32_t Csw, void* stream) {
   SCAN_CHECK_ARG(w && w0 && w1 && (np == 2 || w2) && O > 0 && T > 0 && Cs > 0, "weight_split: bad arguments");
-  SCAN_CHECK_ARG(mode == 0 || mode == 1, "weight_split: mode must be 0 or 1");
-  SCAN_CHECK_ARG(Csw % 8 == 0 && Csw >= (mode == 0 ? Cs : O), "weight_split: Csw=%d must be a multiple of 8 and cover the row",
-                 Csw);
-  const int rows = mode == 0 ? O : Cs;
-  const int64_t total = (int64_t)rows * T * Csw;
+  SCAN_CHECK_ARG(mode >= 0 && mode <= 3, "weight_split: mode must be 0..3");
+  SCAN_CHECK_ARG(mode < 2 || (np == 3 && T == 9), "weight_split: the Winograd modes 2 / 3 take three pieces and T = 9");
+  SCAN_CHECK_ARG(Csw % 8 == 0 && Csw >= ((mode & 1) == 0 ? Cs : O),
+                 "weight_split: Csw=%d must be a multiple of 8 and cover the row", Csw);
+  const int rows = (mode & 1) == 0 ? O : Cs;
+  const int64_t total = (int64_t)rows * (mode >= 2 ? 12 : T) * Csw;
   __bf16 *p0 = reinterpret_cast<__bf16*>(w0), *p1 = reinterpret_cast<__bf16*>(w1), *p2 = reinterpret_cast<__bf16*>(w2);
   if (np == 3)
     hipLaunchKernelGGL(weight_split_kernel<3>, dim3(grid_for(total, 256)), dim3(256), 0, as_stream(stream), w, O, T, Cs, mode,
@@ -524,6 +538,35 @@ extern "C" int scan_conv3x3_gn_bf16x6(const float* x, const scan_pyramid_t* d, i
                                       const void* wl, int32_t Csw, const float* bias, float* y, int32_t Nout, int32_t Ns,
                                       float* gn_ws, int32_t clear, void* stream) {
   return conv3x3_gn_launch(3, clear, x, d, Cs, wh, wm, wl, Csw, bias, y, Nout, Ns, gn_ws, stream);
+}
+
+// the Winograd F(2,3) instance (conv_fwd.hip): wh / wm / wl = scan_weight_split3 planes of mode 2 (forward) or 3 (data
+// gradient); gn_ws != nullptr: the GroupNorm sums of scan_conv3x3_gn_bf16x6 (Nout == 256, clear as there); relu: bit 0 =
+// ReLU, bit 1 = fused 2x2 / stride-2 max-pool as scan_conv3x3_pool2_bf16x6 (single level, even H and W)
+int conv3x3_wino_launch(const float* x, const scan_pyramid_t* d, int32_t Cs, const void* w0, const void* w1, const void* w2,
+                        int32_t Csw, const float* bias, const float* mask, float* y, int32_t Nout, int32_t Ns, int32_t relu,
+                        void* stream, double* gn_ws);
+extern "C" int scan_conv3x3_wino_bf16x6(const float* x, const scan_pyramid_t* d, int32_t Cs, const void* wh, const void* wm,
+                                        const void* wl, int32_t Csw, const float* bias, const float* mask, float* y,
+                                        int32_t Nout, int32_t Ns, int32_t relu, float* gn_ws, int32_t clear, void* stream) {
+  SCAN_CHECK_ARG(x && d && wh && wm && wl && y && Cs > 0 && Cs % 4 == 0 && Csw >= Cs && Nout > 0 && Ns >= Nout &&
+                     d->n_levels >= 1 && d->n_levels <= SCAN_MAX_LEVELS && d->n_images >= 1 && v2_ok(y, mask, Ns),
+                 "conv3x3_wino_bf16x6: bad arguments");
+  if (gn_ws != nullptr) {
+    SCAN_CHECK_ARG(Nout == 256 && mask == nullptr && !relu, "conv3x3_wino_bf16x6: GroupNorm sums need Nout == 256, no mask, no ReLU");
+    if (clear) {
+      const size_t bytes = sizeof(double) * 2 * 32 * (size_t)d->n_levels * d->n_images;
+      if (hipMemsetAsync(gn_ws, 0, bytes, as_stream(stream)) != hipSuccess) {
+        scan_set_error("conv3x3_wino_bf16x6: memset failed");
+        return -2;
+      }
+    }
+  }
+  if (relu & 2)
+    SCAN_CHECK_ARG(d->n_levels == 1 && (d->h[0] & 1) == 0 && (d->w[0] & 1) == 0 && mask == nullptr && gn_ws == nullptr,
+                   "conv3x3_wino_bf16x6: the fused pool needs a single-level pyramid with even H and W, no mask, no sums");
+  return conv3x3_wino_launch(x, d, Cs, wh, wm, wl, Csw, bias, mask, y, Nout, Ns, relu & 3, stream,
+                             reinterpret_cast<double*>(gn_ws));
 }
 
 // conv3x3 + bias (+ ReLU) + 2x2 / stride-2 max-pool in one launch: y [N, H/2, W/2, Ns] (forward only; single-level

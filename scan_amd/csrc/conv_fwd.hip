@@ -40,6 +40,9 @@ struct TileTab2 {
 
 // 16-byte slot swizzle of a 64-byte row: k-group kg of row idx lives at slot kg ^ swz(idx)
 __device__ __forceinline__ int swz(int idx) { return (idx >> 1) & 2; }
+// ... of the Winograd patch (column j * 8 + t of patch row r): an MFMA fragment reads pairs t = 0..7 of TWO adjacent rows
+// (2048 B apart), so the row parity flips the slot as well -- the 16 lanes of a ds_read_b128 group hit 16 distinct slots
+__device__ __forceinline__ int wsw(int t, int r) { return ((t >> 1) & 2) ^ (r & 1); }
 
 // The weight plane slot I of a thread reads from, WITHOUT a run-time table: slot = tid + NT * I lies in plane slot / PL, and
 // for every instance that is one compile-time plane or one of two neighbours.  (Written as a nested select on the run-time
@@ -95,7 +98,14 @@ __device__ __forceinline__ void mma_pieces(const bf16x8 (&w)[NP], const bf16x8 (
 // slot swizzle moves to the per-lane SOURCE address: the DMA writes a wave's 64 x 16 bytes contiguously).  Needs whole
 // K chunks (Csw % 32 == 0).  Rows beyond Nout in the last channel tile lie beyond the plane, i.e. beyond the buffer
 // descriptor's num_records: the range check returns zeros for them, which is what the DMA writes.
-template <int NP, int BN, int TH, int NT, int KS, int TPB = 1, bool GL = false>
+//
+// WINO: 1-D Winograd F(2,3) along x (three pieces, 3x3, LDS-DMA weights only).  An output pair (x, x + 1) of a row is
+// y0 = m0 + (m1 + m2), y1 = (m1 - m2) - m3, m_j = sum over (c, ky) of (G g)_j (B^T d)_j: four products per pair and ky
+// instead of six.  The patch holds the fp32 transform B^T d of every pair (4 components x 8 pairs per row, computed while
+// staging, then split); the weight planes hold G g in 12 taps j * 3 + ky (scan_weight_split modes 2 / 3).  The MFMA
+// B operand is 16 "pixels" = 8 pairs x 2 rows of one component, so the four accumulator sets share one lane map and the
+// output transform stays in registers.  Numerics: tools/wino_numerics.py, DESIGN.md section 3.1.
+template <int NP, int BN, int TH, int NT, int KS, int TPB = 1, bool GL = false, bool WINO = false>
 __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
     const float* __restrict__ src, scan_pyramid_t d, int Cs, const __bf16* __restrict__ w0, const __bf16* __restrict__ w1,
     const __bf16* __restrict__ w2, int Csw, const float* __restrict__ bias, const float* __restrict__ mask,
@@ -103,21 +113,25 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
     double* __restrict__ gn_ws) {
   constexpr int HALO = KS / 2, NTAPS = KS * KS;
   constexpr int PH = TH + 2 * HALO;
-  constexpr int PWK = V2_TW + 2 * HALO;
+  constexpr int PWK = WINO ? 32 : V2_TW + 2 * HALO;  // patch columns per row: halo pixels, or 4 components x 8 pairs
   constexpr int NPATCH = PH * PWK;
+  constexpr int WTAPS = WINO ? 12 : NTAPS;            // weight taps per plane row
   constexpr int WAVES = NT / 64;
   constexpr int WN_WAVES = BN >= 128 ? 2 : 1;
   constexpr int WM_WAVES = WAVES / WN_WAVES;
   constexpr int TM = TH / WM_WAVES;             // 16-pixel tile rows per wave
   constexpr int TN = BN / (16 * WN_WAVES);      // 16-channel tiles per wave (4, or 8 for BN = 256)
-  constexpr int ASLOTS = (NPATCH * 8 + NT - 1) / NT;  // float4 of the halo patch per thread per chunk
+  constexpr int TMW = WINO ? TM / 2 : TM;           // MFMA pixel tiles per wave and tap (Winograd: 2 rows x 8 pairs each)
+  constexpr int ASLOTS = WINO ? (PH * 64 + NT - 1) / NT : (NPATCH * 8 + NT - 1) / NT;  // staging slots per thread per chunk
+  constexpr int AK = WINO ? 4 : 1;                   // halo pixels (float4 loads) per slot: a Winograd slot is one pair
   constexpr int BSLOTS = BN * 4 * NP;                 // 16-byte weight segments per (chunk, tap)
   constexpr int BSEG = (BSLOTS + NT - 1) / NT;        // ... per thread
-  constexpr int NGRP = NTAPS / TPB;                   // barrier intervals per chunk
+  constexpr int NGRP = WTAPS / TPB;                   // barrier intervals per chunk
   static_assert(NP == 2 || NP == 3, "two or three pieces per operand");
   static_assert(TM * WM_WAVES == TH && (TM % 2) == 0, "tile rows must split evenly (and pair up for the fused pool)");
   static_assert(NTAPS % TPB == 0, "taps per barrier must divide the tap count");
   static_assert(BSLOTS % 64 == 0, "a wave's 64 weight segments lie in one plane (and past the end only as a whole wave)");
+  static_assert(!WINO || (GL && KS == 3 && TPB == 1 && NP == 3 && TM % 2 == 0), "Winograd: three pieces, 3x3, LDS-DMA weights");
 
   extern __shared__ __align__(16) unsigned char smem_raw[];
   __bf16* As = reinterpret_cast<__bf16*>(smem_raw);  // [NP plane][NPATCH][32]
@@ -147,6 +161,7 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
   // read zeros -- no predication, no per-chunk address arithmetic, no 64-bit per-lane pointers held across the K loop.
   constexpr unsigned BAD = 0x80000000u;
   unsigned voff[ASLOTS];
+  unsigned vok = 0;  // Winograd: bit 4 i + k = halo pixel k of slot i lies in the image (its offset is voff[i] + k * 4 Cs)
   const int c_tail = Cs - (nchunks - 1) * V2_CK;  // channels of the last chunk (1..32)
   // a lane's float4 column inside a chunk is the same for all its slots (NT is a multiple of 8): one predicate says
   // whether it lies beyond the channel count in the last chunk
@@ -163,35 +178,79 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
     else
       base_row = sd.row_off[lvl] + ((int64_t)img * Hs + (ty0 >> 1)) * Ws + (tx0 >> 1);
     a_src = uniform_rsrc_b(src + base_row * Cs, 0x7ffffff0);
+    if constexpr (WINO) {
+      // slot = (patch row, pair t, float4 c4): the four halo pixels 2t .. 2t + 3 of the pair
 #pragma unroll
-    for (int i = 0; i < ASLOTS; ++i) {
-      const int slot = tid + NT * i;
-      const int q = slot >> 3, c4 = slot & 7;
-      const int py = q / PWK, px = q - py * PWK;
-      const int y = ty0 - HALO + py, x = tx0 - HALO + px;
-      bool ok = (slot < NPATCH * 8) && y >= 0 && y < H && x >= 0 && x < W;
-      int pix = py * W + px;
-      if (mapped) {
-        if (map == 1) {
-          ok = ok && 2 * y < Hs && 2 * x < Ws;
-          pix = 2 * py * Ws + 2 * px;
-        } else {
-          ok = ok && ((y | x) & 1) == 0 && (y >> 1) < Hs && (x >> 1) < Ws;
-          pix = (py >> 1) * Ws + (px >> 1);
+      for (int i = 0; i < ASLOTS; ++i) {
+        const int slot = tid + NT * i;
+        const int c4 = slot & 7, t = (slot >> 3) & 7, py = slot >> 6;
+        voff[i] = (unsigned)(((py * W + 2 * t) * Cs + 4 * c4) * 4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int y = ty0 - HALO + py, x = tx0 - HALO + 2 * t + k;
+          if ((slot < PH * 64) && y >= 0 && y < H && x >= 0 && x < W) vok |= 1u << (4 * i + k);
         }
       }
-      voff[i] = ok ? (unsigned)((pix * Cs + 4 * c4) * 4) : BAD;
+    } else {
+#pragma unroll
+      for (int i = 0; i < ASLOTS; ++i) {
+        const int slot = tid + NT * i;
+        const int q = slot >> 3, c4 = slot & 7;
+        const int py = q / PWK, px = q - py * PWK;
+        const int y = ty0 - HALO + py, x = tx0 - HALO + px;
+        bool ok = (slot < NPATCH * 8) && y >= 0 && y < H && x >= 0 && x < W;
+        int pix = py * W + px;
+        if (mapped) {
+          if (map == 1) {
+            ok = ok && 2 * y < Hs && 2 * x < Ws;
+            pix = 2 * py * Ws + 2 * px;
+          } else {
+            ok = ok && ((y | x) & 1) == 0 && (y >> 1) < Hs && (x >> 1) < Ws;
+            pix = (py >> 1) * Ws + (px >> 1);
+          }
+        }
+        voff[i] = ok ? (unsigned)((pix * Cs + 4 * c4) * 4) : BAD;
+      }
     }
   }
-  float4 ra[ASLOTS];
+  float4 ra[ASLOTS][AK];
   auto load_a = [&](int cc) {
     const int soff = cc * (V2_CK * 4);
     const bool kill = tail_bad && cc == nchunks - 1;
 #pragma unroll
     for (int i = 0; i < ASLOTS; ++i)
-      ra[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(a_src, (int)(kill ? BAD : voff[i]), soff, 0));
+#pragma unroll
+      for (int k = 0; k < AK; ++k) {
+        const unsigned off = !WINO ? voff[i] : ((vok >> (4 * i + k)) & 1) ? voff[i] + (unsigned)(k * Cs * 4) : BAD;
+        ra[i][k] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(a_src, (int)(kill ? BAD : off), soff, 0));
+      }
   };
   auto store_a = [&]() {
+    if constexpr (WINO) {
+      // B^T d in fp32 (one rounding per value), then the exact split; component j of pair t goes to patch column j * 8 + t
+#pragma unroll
+      for (int i = 0; i < ASLOTS; ++i) {
+        const int slot = tid + NT * i;
+        if (slot < PH * 64) {
+          const int c4 = slot & 7, t = (slot >> 3) & 7, py = slot >> 6;
+          const float4 d0 = ra[i][0], d1 = ra[i][1], d2 = ra[i][2], d3 = ra[i][3];
+          const float4 u[4] = {make_float4(d0.x - d2.x, d0.y - d2.y, d0.z - d2.z, d0.w - d2.w),
+                               make_float4(d1.x + d2.x, d1.y + d2.y, d1.z + d2.z, d1.w + d2.w),
+                               make_float4(d2.x - d1.x, d2.y - d1.y, d2.z - d1.z, d2.w - d1.w),
+                               make_float4(d1.x - d3.x, d1.y - d3.y, d1.z - d3.z, d1.w - d3.w)};
+          const int sl = (((c4 >> 1) ^ wsw(t, py)) << 3) + ((c4 & 1) << 2);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            bf16x4 pc[NP];
+            split4_np<NP>(u[j], pc);
+            const int off = (py * PWK + j * 8 + t) * 32 + sl;
+#pragma unroll
+            for (int p = 0; p < NP; ++p) *reinterpret_cast<bf16x4*>(As + p * NPATCH * 32 + off) = pc[p];
+          }
+        }
+      }
+      return;
+    }
 #pragma unroll
     for (int i = 0; i < ASLOTS; ++i) {
       const int slot = tid + NT * i;
@@ -199,7 +258,7 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
         const int q = slot >> 3, c4 = slot & 7;
         const int px = q % PWK;
         bf16x4 pc[NP];
-        split4_np<NP>(ra[i], pc);
+        split4_np<NP>(ra[i][0], pc);
         const int off = q * 32 + (((c4 >> 1) ^ swz(px)) << 3) + ((c4 & 1) << 2);
 #pragma unroll
         for (int p = 0; p < NP; ++p) *reinterpret_cast<bf16x4*>(As + p * NPATCH * 32 + off) = pc[p];
@@ -253,10 +312,10 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
     const int plane = slot / (BN * 4);
     const int rem = slot - plane * BN * 4;   // destination slot inside the plane: row * 4 + dslot
     const int row = rem >> 2, seg = (rem & 3) ^ swz(row);  // source k-group of that slot (swz is an involution)
-    boff[i] = (unsigned)((((n0 + row) * NTAPS) * Csw + 8 * seg) * 2);
+    boff[i] = (unsigned)((((n0 + row) * WTAPS) * Csw + 8 * seg) * 2);
   }
   // (separate variables, not an array: an array of __amdgpu_buffer_rsrc_t silently drops the kernel's host stub)
-  const int plane_bytes = Nout * NTAPS * Csw * 2;  // rows >= Nout are out of range: they read (and the DMA writes) zeros
+  const int plane_bytes = Nout * WTAPS * Csw * 2;  // rows >= Nout are out of range: they read (and the DMA writes) zeros
   auto plane_rsrc = [&](int i) { return uniform_rsrc_b(slot_plane_i<NT, BN * 4, NP>(i, tid, w0, w1, w2), plane_bytes); };
   const __amdgpu_buffer_rsrc_t b_src0 = plane_rsrc(0), b_src1 = plane_rsrc(1), b_src2 = plane_rsrc(2),
                                b_src3 = plane_rsrc(3), b_src4 = plane_rsrc(4), b_src5 = plane_rsrc(5);
@@ -290,6 +349,13 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
   for (int b = 0; b < TN; ++b)
 #pragma unroll
     for (int a = 0; a < TM; ++a) acc[b][a] = f32x4v{0.f, 0.f, 0.f, 0.f};
+  f32x4v wacc[WINO ? 4 : 1][WINO ? TN : 1][TMW];  // Winograd: m_j per (channel tile, 2-row pixel tile)
+#pragma unroll
+  for (int j = 0; j < (WINO ? 4 : 1); ++j)
+#pragma unroll
+    for (int b = 0; b < (WINO ? TN : 1); ++b)
+#pragma unroll
+      for (int a = 0; a < TMW; ++a) wacc[j][b][a] = f32x4v{0.f, 0.f, 0.f, 0.f};
 
   auto patch_off = [&](int tap) {
     const int ky = tap / KS, kx = tap - KS * ky;
@@ -378,8 +444,59 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
     }
   };
 
+  // Winograd: one barrier interval per weight tap (j, ky); the MFMA B fragment of lane (lr, kg) is pair lr & 7 of patch
+  // row wm * TM + 2 * tm + (lr >> 3) + ky, component j
+  auto wino_mma = [&](int j, int ky, int buf, f32x4v (&aj)[WINO ? TN : 1][TMW], auto&& mid) {
+    const __bf16* bt = Bs + (buf * NP) * BN * 32 + w_off;
+    const int prow = wm * TM + (lr >> 3) + ky, t = lr & 7;
+    const int p_off = (prow * PWK + j * 8 + t) * 32 + ((kg ^ wsw(t, prow)) << 3);
+    bf16x8 pf[NP][TMW];
+#pragma unroll
+    for (int p = 0; p < NP; ++p)
+#pragma unroll
+      for (int tm = 0; tm < TMW; ++tm)
+        pf[p][tm] = *reinterpret_cast<const bf16x8*>(As + p * NPATCH * 32 + p_off + tm * 2 * PWK * 32);
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn) {
+      bf16x8 wf[NP];
+      read_w(bt, tn, wf);
+      mma_pieces<NP, TMW>(wf, pf, aj[tn]);
+      if (tn == (SCAN_CONV_MID >= 0 ? SCAN_CONV_MID : 0)) {
+        __builtin_amdgcn_sched_barrier(0);
+        mid();
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+  };
+
   load_a(0);
-  if constexpr (GL) {
+  if constexpr (WINO) {
+    issue_b(0, 0, 0);
+    for (int cc = 0; cc < nchunks; ++cc) {
+      __syncthreads();  // every wave is done reading the previous chunk's patch
+      store_a();
+      auto comp = [&](int j, f32x4v (&aj)[WINO ? TN : 1][TMW]) {
+#pragma unroll 1
+        for (int ky = 0; ky < 3; ++ky) {
+          const int grp = j * 3 + ky, buf = grp & 1;  // (NGRP = 12 is even: the buffer parity restarts every chunk)
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          __syncthreads();  // this tap's weight tile is complete; the patch is visible
+          auto feed = [&]() {
+            if (grp < NGRP - 1)
+              issue_b(cc, grp + 1, buf ^ 1);
+            else if (cc + 1 < nchunks)
+              issue_b(cc + 1, 0, buf ^ 1);
+            if (grp == NGRP - 2 && cc + 1 < nchunks) load_a(cc + 1);
+          };
+          wino_mma(j, ky, buf, aj, feed);
+        }
+      };
+      comp(0, wacc[0]);
+      comp(1, wacc[WINO ? 1 : 0]);
+      comp(2, wacc[WINO ? 2 : 0]);
+      comp(3, wacc[WINO ? 3 : 0]);
+    }
+  } else if constexpr (GL) {
     issue_b(0, 0, 0);
     for (int cc = 0; cc < nchunks; ++cc) {
       __syncthreads();  // every wave is done reading the previous chunk's patch
@@ -461,6 +578,94 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
       bv.y = o4 + 1 < Nout ? bias[o4 + 1] : 0.f;
       bv.z = o4 + 2 < Nout ? bias[o4 + 2] : 0.f;
       bv.w = o4 + 3 < Nout ? bias[o4 + 3] : 0.f;
+    }
+    if constexpr (WINO) {
+      // output transform A^T in fp32, m1 and m2 first; lane (lr, kg) owns pixels x0 = tx0 + 2 (lr & 7), x0 + 1 of row
+      // ty0 + wm * TM + 2 * tm + (lr >> 3)
+      const int xw = tx0 + 2 * (lr & 7);
+      if (relu & 2) {
+        // fused 2x2 / stride-2 max-pool: columns x0, x0 + 1 are this lane's pair, rows y, y + 1 are lanes l, l ^ 8
+#pragma unroll
+        for (int tm = 0; tm < TMW; ++tm) {
+          const int y = ty0 + wm * TM + 2 * tm + (lr >> 3);
+          const f32x4v m0 = wacc[0][tn][tm], m1 = wacc[WINO ? 1 : 0][tn][tm], m2 = wacc[WINO ? 2 : 0][tn][tm],
+                       m3 = wacc[WINO ? 3 : 0][tn][tm];
+          const f32x4v y0 = m0 + (m1 + m2), y1 = (m1 - m2) - m3;
+          float v[4];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float m = fmaxf(y0[r], y1[r]);
+            v[r] = fmaxf(m, __shfl_xor(m, 8, 64));
+          }
+          if ((lr >> 3) == 0 && y < H && xw < W && o4 < Nout) {
+            const int Hp = H >> 1, Wp = W >> 1;
+            float4 o = make_float4(v[0] + bv.x, v[1] + bv.y, v[2] + bv.z, v[3] + bv.w);
+            if (relu & 1) {
+              o.x = fmaxf(o.x, 0.f);
+              o.y = fmaxf(o.y, 0.f);
+              o.z = fmaxf(o.z, 0.f);
+              o.w = fmaxf(o.w, 0.f);
+            }
+            *reinterpret_cast<float4*>(dst + ((int64_t)img * Hp * Wp + (int64_t)(y >> 1) * Wp + (xw >> 1)) * Ns + o4) = o;
+          }
+        }
+        continue;
+      }
+      float4 mk[TMW][2];
+      if (mask != nullptr) {
+#pragma unroll
+        for (int tm = 0; tm < TMW; ++tm) {
+          const int y = ty0 + wm * TM + 2 * tm + (lr >> 3);
+#pragma unroll
+          for (int e = 0; e < 2; ++e) {
+            const bool ok = y < H && xw + e < W && o4 < Nout;
+            mk[tm][e] = ok ? *reinterpret_cast<const float4*>(mask + (rowbase + (int64_t)y * W + xw + e) * Ns + o4)
+                           : make_float4(0.f, 0.f, 0.f, 0.f);
+          }
+        }
+      }
+      double ds = 0.0, dq = 0.0;
+#pragma unroll
+      for (int tm = 0; tm < TMW; ++tm) {
+        const int y = ty0 + wm * TM + 2 * tm + (lr >> 3);
+        const f32x4v m0 = wacc[0][tn][tm], m1 = wacc[WINO ? 1 : 0][tn][tm], m2 = wacc[WINO ? 2 : 0][tn][tm],
+                     m3 = wacc[WINO ? 3 : 0][tn][tm];
+        const f32x4v yv[2] = {m0 + (m1 + m2), (m1 - m2) - m3};
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          if (y < H && xw + e < W && o4 < Nout) {
+            float4 o = make_float4(yv[e][0] + bv.x, yv[e][1] + bv.y, yv[e][2] + bv.z, yv[e][3] + bv.w);
+            if (relu & 1) {
+              o.x = fmaxf(o.x, 0.f);
+              o.y = fmaxf(o.y, 0.f);
+              o.z = fmaxf(o.z, 0.f);
+              o.w = fmaxf(o.w, 0.f);
+            }
+            if (mask != nullptr) {
+              o.x = (mk[tm][e].x > 0.f) ? o.x : 0.f;
+              o.y = (mk[tm][e].y > 0.f) ? o.y : 0.f;
+              o.z = (mk[tm][e].z > 0.f) ? o.z : 0.f;
+              o.w = (mk[tm][e].w > 0.f) ? o.w : 0.f;
+            }
+            *reinterpret_cast<float4*>(dst + (rowbase + (int64_t)y * W + xw + e) * Ns + o4) = o;
+            ds += (double)((o.x + o.y) + (o.z + o.w));
+            dq += (double)((o.x * o.x + o.y * o.y) + (o.z * o.z + o.w * o.w));
+          }
+        }
+      }
+      if (gn_ws != nullptr) {  // as below: reduce over the 16 lanes of a k-group and the pair kg, kg ^ 1
+#pragma unroll
+        for (int sh = 1; sh <= 16; sh <<= 1) {
+          ds += __shfl_xor(ds, sh, 64);
+          dq += __shfl_xor(dq, sh, 64);
+        }
+        if (lr == 0 && (kg & 1) == 0) {
+          double* r = gn_red + (wm * (BN / 8) + ((o4 - n0) >> 3)) * 2;
+          r[0] = ds;
+          r[1] = dq;
+        }
+      }
+      continue;
     }
     if (relu & 2) {
       // fused 2x2 / stride-2 max-pool (frozen VGG stages): rows y, y+1 are accumulator tiles tm, tm+1 of this lane,
@@ -582,22 +787,23 @@ struct ConvArgs {
   double* gn_ws;
 };
 
-template <int NP, int BN, int TH, int NT, int KS, int TPB = 1, bool GL = false>
+template <int NP, int BN, int TH, int NT, int KS, int TPB = 1, bool GL = false, bool WINO = false>
 static void launch_v2(const ConvArgs& a) {
   constexpr int HALO = KS / 2;
   TileTab2 tt;
   make_tiles_v2(a.od, &tt, TH);
   const int tiles = tt.tile_off[a.od->n_levels];
   const int n_tiles = (a.Nout + BN - 1) / BN;
-  constexpr size_t sh = (size_t)(NP * (TH + 2 * HALO) * (V2_TW + 2 * HALO) * 32 + 2 * NP * TPB * BN * 32) * sizeof(__bf16);
+  constexpr int PWK = WINO ? 32 : V2_TW + 2 * HALO;
+  constexpr size_t sh = (size_t)(NP * (TH + 2 * HALO) * PWK * 32 + 2 * NP * TPB * BN * 32) * sizeof(__bf16);
   static_assert(sh <= 160 * 1024, "LDS: 160 KB per CU");
   static bool done = false;
   if (!done) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<NP, BN, TH, NT, KS, TPB, GL>),
+    hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<NP, BN, TH, NT, KS, TPB, GL, WINO>),
                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
     done = true;
   }
-  hipLaunchKernelGGL((conv_split_kernel<NP, BN, TH, NT, KS, TPB, GL>), dim3(tiles * n_tiles), dim3(NT), sh, a.st, a.x, *a.od,
+  hipLaunchKernelGGL((conv_split_kernel<NP, BN, TH, NT, KS, TPB, GL, WINO>), dim3(tiles * n_tiles), dim3(NT), sh, a.st, a.x, *a.od,
                      a.Cs, a.w[0], a.w[1], a.w[2], a.Csw, a.bias, a.mask, a.y, a.Nout, a.Ns, a.relu, tt, n_tiles, *a.sd,
                      a.map, a.gn_ws);
 }
@@ -726,6 +932,25 @@ int conv3x3_split_launch(int np, const float* x, const scan_pyramid_t* d, int32_
       break;
   }
   SCAN_LAUNCH_CHECK("conv3x3_bf16x3");
+  return 0;
+}
+
+// scan_tune "conv_wino": 1 (default) = three-piece 3x3 launches with more than 64 output channels and whole K chunks run the
+// Winograd F(2,3) instance (conv_split_kernel<..., WINO>: 128-channel tile, 16 x 16 pixels) on Winograd planes
+// (scan_weight_split modes 2 / 3, ops.py decides with scan_conv3x3_bf16x6_wino); 0 = every launch on the direct kernels as
+// before, bit for bit.  The <= 64-channel instances and two pieces stay on the direct kernels.  Measurements: DESIGN.md
+// section 3.1.
+int g_scan_conv_wino = 1;
+extern "C" int scan_conv3x3_bf16x6_wino(int32_t Nout, int32_t Csw) { return g_scan_conv_wino && Nout > 64 && Csw % 32 == 0 ? 1 : 0; }
+
+int conv3x3_wino_launch(const float* x, const scan_pyramid_t* d, int32_t Cs, const void* w0, const void* w1, const void* w2,
+                        int32_t Csw, const float* bias, const float* mask, float* y, int32_t Nout, int32_t Ns, int32_t relu,
+                        void* stream, double* gn_ws) {
+  SCAN_CHECK_ARG(Nout > 64 && Csw % 32 == 0, "conv3x3_wino_bf16x6: needs Nout > 64 and Csw %% 32 == 0 (Nout=%d Csw=%d)", Nout, Csw);
+  ConvArgs a{x, d, d, Cs, {reinterpret_cast<const __bf16*>(w0), reinterpret_cast<const __bf16*>(w1),
+                           reinterpret_cast<const __bf16*>(w2)}, Csw, bias, mask, y, Nout, Ns, relu, 0, as_stream(stream), gn_ws};
+  launch_v2<3, 128, 16, 512, 3, 1, true, true>(a);
+  SCAN_LAUNCH_CHECK("conv3x3_wino_bf16x6");
   return 0;
 }
 

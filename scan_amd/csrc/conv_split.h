@@ -55,6 +55,17 @@ __device__ __forceinline__ void split1_np(float v, __bf16 (&q)[NP]) {
   }
 }
 
+// Winograd F(2,3) filter transform of one tap row (g0, g1, g2) = taps kx = 0..2: component j of G g,
+// G = [1 0 0; 1/2 1/2 1/2; 1/2 -1/2 1/2; 0 0 1], in fp64 and rounded ONCE to fp32 (the split that follows is exact)
+__device__ __forceinline__ float wino_g(int j, double g0, double g1, double g2) {
+  const double v = j == 0 ? g0 : j == 1 ? 0.5 * (g0 + g1 + g2) : j == 2 ? 0.5 * (g0 - g1 + g2) : g2;
+  float f = (float)v;
+  // the split that follows must round THIS fp32 value: without the (empty) barrier the compiler folds fp64 -> fp32 -> bf16 into
+  // one fp64 -> bf16 rounding in some callers, and the pieces of a bf16 tie then differ between the batched and the single split
+  asm("" : "+v"(f));
+  return f;
+}
+
 // buffer descriptor from wave-uniform inputs, made PROVABLY uniform for the compiler (cdna_hip_programming.md T20): a
 // descriptor it cannot prove uniform gets a waterfall loop around every load
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc_b(const void* base, int bytes) {

@@ -106,7 +106,8 @@ void invalidate_weight_cache() {
   ++g_plane_epoch;
   plane_cache().clear();
 }
-// three bf16 planes of packed weights wp [O][T][Cs]; mode 0: forward [O][T][csw]; mode 1: data gradient [Cs][T][csw]
+// three bf16 planes of packed weights wp [O][T][Cs]; mode 0: forward [O][T][csw]; mode 1: data gradient [Cs][T][csw];
+// modes 2 / 3: their Winograd F(2,3) planes (T = 9 -> 12 taps per row) for scan_conv3x3_wino_bf16x6
 Planes split3_uncached(const at::Tensor& wp, int mode, int64_t cs_src);
 Planes split3(const at::Tensor& wp, int mode, int64_t cs_src, const at::Tensor& owner = at::Tensor()) {
   // owner: defined when wp is a VIEW of the weight tensor (pack_weight of a channels_last weight with C % 4 == 0: shares its storage
@@ -131,9 +132,9 @@ Planes split3_uncached(const at::Tensor& wp, int mode, int64_t cs_src) {
   const int64_t o = wp.size(0), t = wp.size(1), cs = wp.size(2);
   const int64_t rnd = t == 9 ? 32 : 8;  // 3x3: whole 32-channel K chunks (LDS-DMA weight tiles); 1x1: 8-element granule
   Planes pl;
-  const int64_t rows = mode == 0 ? o : cs;
-  pl.csw = round_up(mode == 0 ? cs : std::max(o, cs_src), rnd);
-  for (auto& q : pl.p) q = at::empty({rows, t, pl.csw}, wp.options().dtype(at::kBFloat16));
+  const int64_t rows = (mode & 1) == 0 ? o : cs;
+  pl.csw = round_up((mode & 1) == 0 ? cs : std::max(o, cs_src), rnd);
+  for (auto& q : pl.p) q = at::empty({rows, mode >= 2 ? 12 : t, pl.csw}, wp.options().dtype(at::kBFloat16));
   check(scan_weight_split3(wp.data_ptr<float>(), (int32_t)o, (int32_t)t, (int32_t)cs, mode, pl.p[0].data_ptr(), pl.p[1].data_ptr(),
                            pl.p[2].data_ptr(), (int32_t)pl.csw, cur_stream(wp)),
         "scan_weight_split3");
@@ -181,6 +182,15 @@ at::Tensor conv_rows_forward(const at::Tensor& xr, const at::Tensor& wp, const a
           "scan_conv_smallcin_bf16x6");
     return y;
   }
+  // the Winograd instance takes the launches scan_amd.ops gives it (same planes, same kernel: bit-identical to the Python path)
+  if (g.k == 3 && scan_conv3x3_bf16x6_wino((int32_t)g.cout, (int32_t)round_up(g.cs, 32))) {
+    const Planes pl = split3(wp, 2, g.cs, owner);
+    check(scan_conv3x3_wino_bf16x6(xr.data_ptr<float>(), &xd, (int32_t)g.cs, pl.p[0].data_ptr(), pl.p[1].data_ptr(), pl.p[2].data_ptr(),
+                                   (int32_t)pl.csw, opt_ptr(bias), nullptr, y.data_ptr<float>(), (int32_t)g.cout, (int32_t)g.ns,
+                                   relu ? 1 : 0, gn_sums.defined() ? reinterpret_cast<float*>(gn_sums.data_ptr()) : nullptr, 1, st),
+          "scan_conv3x3_wino_bf16x6");
+    return y;
+  }
   const Planes pl = split3(wp, 0, g.cs, owner);
   if (g.k == 3) {
     if (gn_sums.defined())
@@ -219,8 +229,15 @@ std::vector<at::Tensor> conv_rows_backward(const at::Tensor& xr, const at::Tenso
                               (int32_t)g.cs, 3, 2, nullptr, st),
             "scan_conv2d_dgrad");
     } else {
-      const Planes pl = split3(wp, 1, g.ns, owner);  // flipped + transposed planes: the data gradient is the forward kernel on dY
-      if (g.k == 3)
+      const bool wino = g.k == 3 && scan_conv3x3_bf16x6_wino((int32_t)g.cs, (int32_t)round_up(std::max(g.cout, g.ns), 32));
+      // flipped + transposed planes: the data gradient is the forward kernel on dY
+      const Planes pl = split3(wp, wino ? 3 : 1, g.ns, owner);
+      if (wino)
+        check(scan_conv3x3_wino_bf16x6(dyr.data_ptr<float>(), &yd, (int32_t)g.ns, pl.p[0].data_ptr(), pl.p[1].data_ptr(), pl.p[2].data_ptr(),
+                                       (int32_t)pl.csw, nullptr, nullptr, dx.data_ptr<float>(), (int32_t)g.cs, (int32_t)g.cs, 0, nullptr, 0,
+                                       st),
+              "scan_conv3x3_wino_bf16x6 (data gradient)");
+      else if (g.k == 3)
         check(scan_conv3x3_bf16x6(dyr.data_ptr<float>(), &yd, (int32_t)g.ns, pl.p[0].data_ptr(), pl.p[1].data_ptr(), pl.p[2].data_ptr(),
                                   (int32_t)pl.csw, nullptr, nullptr, dx.data_ptr<float>(), (int32_t)g.cs, (int32_t)g.cs, 0, st),
               "scan_conv3x3_bf16x6 (data gradient)");

@@ -389,32 +389,40 @@ def _conv_split(x, shape, wp, cout, rows_out, cs_src, mode, bias, relu, ns, name
         rows, csw, nout = O, rnd(cs_w), O
     else:
         rows, csw, nout = cs_w, rnd(max(O, cs_src)), cs_w
+    # a 3x3 launch whose Nout is 128-wide tiles plus a <= 64-channel remainder splits in two (below)
+    rem = nout % 128
+    split_rem = T == 9 and not gn_sums and not pool and nout > 128 and 0 < rem <= 64 and cs_src >= 512 and rows_out >= 100000
+    # the Winograd F(2,3) kernel (scan_tune conv_wino) reads planes of its own: split modes 2 / 3, 12 taps per row
+    wino = npc == 3 and T == 9 and not split_rem and query("scan_conv3x3_bf16x6_wino", nout, csw) == 1
+    smode, TP = (mode + 2, 12) if wino else (mode, T)
     hit = None
     if cache_key is not None and SPLIT_EPOCH is not None:
-        key = (cache_key, mode, csw, npc)
+        key = (cache_key, smode, csw, npc)
         hit = _split_cache.get(key)
-        if hit is not None and (hit[0] != SPLIT_EPOCH or tuple(hit[1][0].shape) != (rows, T, csw)):
+        if hit is not None and (hit[0] != SPLIT_EPOCH or tuple(hit[1][0].shape) != (rows, TP, csw)):
             hit = None
     if hit is not None:
         planes = hit[1]
         # planes written on another stream (e.g. the target pass on its side stream) must be complete
         torch.cuda.current_stream().wait_event(hit[2])
     else:
-        planes = tuple(torch.empty((rows, T, csw), dtype=torch.bfloat16, device=x.device) for _ in range(npc))
+        planes = tuple(torch.empty((rows, TP, csw), dtype=torch.bfloat16, device=x.device) for _ in range(npc))
         if npc == 3:
-            call("scan_weight_split3", _ptr(wp), O, T, cs_w, mode, _ptr(planes[0]), _ptr(planes[1]), _ptr(planes[2]), csw, st)
+            call("scan_weight_split3", _ptr(wp), O, T, cs_w, smode, _ptr(planes[0]), _ptr(planes[1]), _ptr(planes[2]), csw, st)
         else:
             call("scan_weight_split", _ptr(wp), O, T, cs_w, mode, _ptr(planes[0]), _ptr(planes[1]), csw, st)
         if cache_key is not None and SPLIT_EPOCH is not None:
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream())
-            _split_cache[(cache_key, mode, csw, npc)] = (SPLIT_EPOCH, planes, ev)
+            _split_cache[(cache_key, smode, csw, npc)] = (SPLIT_EPOCH, planes, ev)
             if _active_plan is not None and param is not None and wp.data_ptr() == cache_key == param.data_ptr():
-                _active_plan.add((cache_key, mode, csw, npc), param, O, T, cs_w, mode, rows, csw, planes)
+                _active_plan.add((cache_key, smode, csw, npc), param, O, T, cs_w, smode, rows, csw, planes)
     wptrs = [_ptr(t) for t in planes]
     y = out if out is not None else (x.new_zeros if ns != nout else x.new_empty)((rows_out, ns))
     if kernel_timer.enabled:  # label the record with the template instance the launch takes (64 / 128 / 256 channels)
-        if T == 9:
+        if wino:  # 3128: the Winograd instance (128-channel tile); its roofline counts direct-conv FLOPs
+            inst = 3128
+        elif T == 9:
             inst = query("scan_conv3x3_%s_instance" % sfx, (dst_shape or shape).ref(), nout)
         elif npc == 3:
             inst = query("scan_conv1x1_bf16x6_instance", (dst_shape or shape).ref(), nout, csw)
@@ -423,7 +431,14 @@ def _conv_split(x, shape, wp, cout, rows_out, cs_src, mode, bias, relu, ns, name
         ev = kernel_timer.begin("%s_bn%d" % (name, inst), flops)
     else:
         ev = None
-    if gn_sums:
+    if wino:
+        if gn_sums:
+            sums, cleared = _ws_f64(shape.n_levels * shape.n_images * 32 * 2, x.device)
+            _gn_sums.clear()
+            _gn_sums[y.data_ptr()] = sums
+        call("scan_conv3x3_wino_bf16x6", _ptr(x), shape.ref(), cs_src, *wptrs, csw, _ptr(bias), _ptr(mask), _ptr(y), nout, ns,
+             int(bool(relu)) | (2 if pool else 0), _ptr(sums) if gn_sums else None, 0 if not gn_sums or cleared else 1, st)
+    elif gn_sums:
         sums, cleared = _ws_f64(shape.n_levels * shape.n_images * 32 * 2, x.device)
         if npc == 3:
             call("scan_conv3x3_gn_bf16x6", _ptr(x), shape.ref(), cs_src, *wptrs, csw, _ptr(bias), _ptr(y), nout, ns,
@@ -441,8 +456,7 @@ def _conv_split(x, shape, wp, cout, rows_out, cs_src, mode, bias, relu, ns, name
              _ptr(y), (dst_shape or shape).ref(), nout, ns, int(bool(relu)), cmap, st)
     else:
         fn = "scan_conv3x3_" + sfx
-        rem = nout % 128
-        if nout > 128 and 0 < rem <= 64 and cs_src >= 512 and rows_out >= 100000:
+        if split_rem:
             # 128-wide output tiles plus a small remainder (data gradient of the 264-channel discriminator input at
             # P3, K = 1024): the remainder columns go through the 64-channel instance instead of a third, almost empty
             # 128-wide tile (2022 -> 1794 us).  With a short K loop or few rows the extra launch costs more than the
