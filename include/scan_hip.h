@@ -76,6 +76,12 @@ int scan_abi_version(void);
  *                 operands, no faster in the training step: profiles/r06_wgrad_tile_ab.txt).
  *   "wgrad_wgs"   768 (default): workgroups a weight-gradient launch aims at (tiles x split-K slabs); 512 / 640 / 896 / 1024
  *                 / 1280 / 1536 are 2...25 % slower on the 256- and 512-channel layers (bf16x3).
+ *   "wgrad_wino"  1 (default): the bf16x6 3x3 weight gradient on that kernel's 32 x 64 tile runs Winograd F(2,3) across rows:
+ *                 the K walk goes over row pairs, a workgroup owns one of four components instead of one of three ky, a third
+ *                 fewer MFMAs; transforms in fp32 on the loaded rows (one rounding per value), G^T on the fp64 slab sums.
+ *                 Slabs then hold 12 taps: scan_conv3x3_wgrad_bf16x6_ws_floats follows the knob, so size the workspace
+ *                 AFTER setting it.  0: the direct kernel and split-K plan, bit for bit.  bf16x3, wgrad_v6 = 0 and
+ *                 wgrad_tile = 0 are always direct.
  *   "gconv_mfma"  0 (default): the grouped class-branch conv runs on fp32 FMAs; 1: tap products and data gradient on the
  *                 fp32 matrix cores (same products, different summation order; measured no faster in the step).
  *   "reduce_blocks" 2048 (default): most workgroups a loss-reduction kernel is launched with (each ends in one or two float
@@ -326,7 +332,10 @@ int scan_conv3x3_pool2_bf16x6(const float* x, const scan_pyramid_t* d, int32_t C
 int scan_conv_smallcin_bf16x6(const float* x, int32_t N, int32_t H, int32_t W, const float* w, const float* bias,
                               float* y, int32_t Cout, int32_t Cout_s, int32_t ksize, int32_t stride, int32_t relu,
                               void* stream);
-/* weight gradients: x and dy are split inside the kernel, no planes; Cout_s % 4 == 0 */
+/* weight gradients: x and dy are split inside the kernel, no planes; Cout_s % 4 == 0.  The 3x3 workspace holds the split-K
+ * slabs -- [splits][Cout][9][Cs] floats, or [splits][Cout][12][Cs] when the launch takes the Winograd form (scan_tune
+ * "wgrad_wino") -- followed by [splits][Cout] bias slabs: always ask scan_conv3x3_wgrad_bf16x6_ws_floats, under the knob
+ * values the launch will run with. */
 int64_t scan_conv3x3_wgrad_bf16x6_ws_floats(const scan_pyramid_t* d, int32_t Cs, int32_t Cout);
 int scan_conv3x3_wgrad_bf16x6(const float* x, const scan_pyramid_t* d, int32_t Cs, const float* dy, int32_t Cout,
                               int32_t Cout_s, float* dw, float* db, int32_t accumulate, float* ws, void* stream);

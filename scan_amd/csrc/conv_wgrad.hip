@@ -566,12 +566,26 @@ __device__ __forceinline__ void wgrad_mma_v6_pipe(const W6Lane& w, f32x4v (&acc)
 #define W6_BOUNDS __launch_bounds__(768, 3)
 #define W6_THREADS 768
 #endif
-template <int NP, int WKC, int KX, int TOM, int TCW>
+//
+// WINO (three pieces, 3x3): F(2,3) applied ACROSS ROWS.  The K walk runs over row PAIRS (y0, y0 + 1), y0 even, of one image
+// of one level, and the workgroup owns one Winograd component j where the direct form owns one ky.  With e0, e1 = dY rows
+// y0, y0 + 1 and d_i = X row y0 - 1 + i (the kx column shift is the consumers' LDS row shift as before)
+//     M0 = e0 (d0 - d2)    M1 = (e0 + e1)(d1 + d2)    M2 = (e0 - e1)(d2 - d1)    M3 = (-e1)(d1 - d3)
+//     dW[ky=0] = M0 + (M1 + M2) / 2    dW[ky=1] = (M1 - M2) / 2    dW[ky=2] = M3 + (M1 + M2) / 2
+// each M_j summed over all row pairs and columns: four products per row pair instead of six.  Only the producers change:
+// they load the partner row where the component has one, form the sum or difference in fp32 (one rounding per value, as the
+// forward kernel's B^T d) and split and write that.  Rows outside the image and the missing partner of an odd height come
+// back as zeros from the range-checked descriptors, which is the right padding by linearity.  The slabs hold 12 taps
+// (j * 3 + kx); slab_bias_reduce_wino_kernel applies G^T to the fp64 sums.  The bias gradient rides in the j = 1 workgroups of
+// c-tile 0, which see both rows of every pair, from the RAW values.
+template <int NP, int WKC, int KX, int TOM, int TCW, bool WINO = false>
 __global__ W6_BOUNDS void conv_wgrad_v6_kernel(
     const float* __restrict__ x, scan_pyramid_t d, int Cs, const float* __restrict__ dy, int Nout, int Ns,
     float* __restrict__ slab, float* __restrict__ bias_slab, ChunkTab ct, int n_tiles, int c_tiles,
     int chunks_per_split, int splits, int prio) {
-  constexpr int HALO = KX / 2, T = KX * KX;
+  static_assert(!WINO || KX == 3, "F(2,3) across rows is a 3x3 form");
+  constexpr int HALO = KX / 2, T = WINO ? 4 * KX : KX * KX;
+  constexpr int NKY = WINO ? 4 : KX;                  // row taps (direct) or Winograd components handed to separate workgroups
   constexpr int TOMAX = TOM, TCMAX = TCW;             // 16 x 16 tiles per consumer wave along o and c
   constexpr int WOC = 128 / (16 * TOM);               // consumer waves along o (x 128 / (16 * TCW) along c = 8)
   static_assert(WOC * (128 / (16 * TCW)) == 8, "eight consumer waves cover the 128 x 128 tile");
@@ -591,8 +605,8 @@ __global__ W6_BOUNDS void conv_wgrad_v6_kernel(
   const int split = __builtin_amdgcn_readfirstlane(qq / n_tiles) * 8 + xcd;
   const int c_tile = __builtin_amdgcn_readfirstlane(tile % c_tiles);
   tile = __builtin_amdgcn_readfirstlane(tile / c_tiles);
-  const int ky = __builtin_amdgcn_readfirstlane(tile % KX);
-  const int o_tile = __builtin_amdgcn_readfirstlane(tile / KX);
+  const int ky = __builtin_amdgcn_readfirstlane(tile % NKY);  // WINO: the component j
+  const int o_tile = __builtin_amdgcn_readfirstlane(tile / NKY);
   const int o0 = o_tile * 128, c0 = c_tile * 128;
   const long long total_chunks = ct.chunk_off[d.n_levels];
   const long long ch_begin = (long long)split * chunks_per_split;
@@ -619,26 +633,52 @@ __global__ W6_BOUNDS void conv_wgrad_v6_kernel(
       if (i < d.n_levels && ch_begin >= ct.chunk_off[i]) lvl = i;
     int segs = lvl_pick(ct.segs, lvl), H = lvl_pick(d.h, lvl), W = lvl_pick(d.w, lvl);
     long long row0 = lvl_pick64(d.row_off, lvl);
-    int seg, n, y;
+    int seg, n, y;  // WINO: y is the even first row of the pair; a level has (H + 1) / 2 chunk rows per image
     {
       const long long r = (nch > 0 ? ch_begin : 0) - ct.chunk_off[lvl];
       const long long rowl = r / segs;
+      const int HR = WINO ? (H + 1) / 2 : H;
       seg = __builtin_amdgcn_readfirstlane((int)(r - rowl * segs));
-      n = __builtin_amdgcn_readfirstlane((int)(rowl / H));
-      y = __builtin_amdgcn_readfirstlane((int)(rowl - (long long)(rowl / H) * H));
+      n = __builtin_amdgcn_readfirstlane((int)(rowl / HR));
+      y = __builtin_amdgcn_readfirstlane((int)(rowl - (long long)(rowl / HR) * HR)) * (WINO ? 2 : 1);
     }
+    // WINO: the staged value of either operand is sp * p + sq * q of a first row p and a partner row q (signs +-1: the
+    // products are exact, one rounding per value); rows relative to y0:
+    //     j   dY p   dY q   sp  sq  |  X p   X q   sq        (X: sp = 1)
+    //     0    0      -      1   .  |  -1    +1    -1
+    //     1    0     +1      1   1  |   0    +1     1
+    //     2    0     +1      1  -1  |  +1     0    -1
+    //     3   +1      -     -1   .  |   0    +2    -1
+    // the partner dY row exists for j = 1, 2 only (wave-uniform branch around its loads; its registers stay zero otherwise)
+    const bool a2 = WINO && (ky == 1 || ky == 2);
+    const int ya_p = (WINO && ky == 3) ? 1 : 0;
+    const int yb_p = WINO ? (ky == 0 ? -1 : (ky == 2 ? 1 : 0)) : ky - HALO;
+    const int yb_q = WINO ? (ky == 3 ? 2 : (ky == 2 ? 0 : 1)) : 0;
+    const float sa_p = (WINO && ky == 3) ? -1.f : 1.f, s_q = (WINO && ky != 1) ? -1.f : 1.f;
     float4 ra[NA], rb[NB];
+    float4 ra2[WINO ? NA : 1], rb2[WINO ? NB : 1];
+    if constexpr (WINO) {
+#pragma unroll
+      for (int i = 0; i < NA; ++i) ra2[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
     float4 bsum = make_float4(0.f, 0.f, 0.f, 0.f);
     __amdgpu_buffer_rsrc_t ra_src, rb_src;
+    [[maybe_unused]] __amdgpu_buffer_rsrc_t ra2_src, rb2_src;  // WINO only: the partner rows
     bool left_edge = false;
     auto prepare = [&](bool live) {  // descriptors of the chunk at (lvl, n, y, seg); !live: zero records
       const int x0 = seg * WKC;
       const long long rowbase = row0 + ((long long)n * H + y) * W;
       const int kmax = (W - x0 < WKC) ? W - x0 : WKC;
-      ra_src = uniform_rsrc_b(dy + (rowbase + x0) * Ns, live ? kmax * Ns * 4 : 0);
-      const int yy = y + ky - HALO;
       const int jmax = (W - x0 + HALO < WKC + KX - 1) ? W - x0 + HALO : WKC + KX - 1;
-      const float* bbase = x + (rowbase + (long long)(ky - HALO) * W + x0 - HALO) * Cs;  // never dereferenced outside
+      if constexpr (WINO) {
+        ra_src = uniform_rsrc_b(dy + (rowbase + (long long)ya_p * W + x0) * Ns, (live && y + ya_p < H) ? kmax * Ns * 4 : 0);
+        ra2_src = uniform_rsrc_b(dy + (rowbase + W + x0) * Ns, (live && y + 1 < H) ? kmax * Ns * 4 : 0);
+        rb2_src = uniform_rsrc_b(x + (rowbase + (long long)yb_q * W + x0 - HALO) * Cs, (live && y + yb_q < H) ? jmax * Cs * 4 : 0);
+      } else {
+        ra_src = uniform_rsrc_b(dy + (rowbase + x0) * Ns, live ? kmax * Ns * 4 : 0);
+      }
+      const int yy = y + yb_p;
+      const float* bbase = x + (rowbase + (long long)yb_p * W + x0 - HALO) * Cs;  // never dereferenced outside
       rb_src = uniform_rsrc_b(bbase, (live && yy >= 0 && yy < H) ? jmax * Cs * 4 : 0);
       left_edge = seg == 0;
     };
@@ -646,6 +686,13 @@ __global__ W6_BOUNDS void conv_wgrad_v6_kernel(
 #pragma unroll
       for (int i = 0; i < NA; ++i)
         ra[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(ra_src, (int)offa, PRG * i * Ns * 4, 0));
+      if constexpr (WINO) {
+        if (a2) {
+#pragma unroll
+          for (int i = 0; i < NA; ++i)
+            ra2[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(ra2_src, (int)offa, PRG * i * Ns * 4, 0));
+        }
+      }
     };
     auto load_b = [&]() {
 #pragma unroll
@@ -653,12 +700,14 @@ __global__ W6_BOUNDS void conv_wgrad_v6_kernel(
         unsigned off = i == NB - 1 ? offb_last : offb;
         if (KX > 1 && i == 0) off = (left_edge && rr < HALO) ? BAD : off;  // pixel x0 - HALO + j left of the image
         rb[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rb_src, (int)off, PRG * i * Cs * 4, 0));
+        if constexpr (WINO)
+          rb2[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rb2_src, (int)off, PRG * i * Cs * 4, 0));
       }
     };
     auto advance = [&]() {
       if (++seg == segs) {
         seg = 0;
-        if (++y == H) {
+        if (WINO ? (y += 2) >= H : ++y == H) {
           y = 0;
           if (++n == d.n_images) {
             n = 0;
@@ -677,10 +726,17 @@ __global__ W6_BOUNDS void conv_wgrad_v6_kernel(
 #pragma unroll
       for (int i = 0; i < NA; ++i) {
         const int off = wsw6(rr + PRG * i, 4 * q4);
+        float4 va = ra[i];
+        if constexpr (WINO) {
+          va.x = __builtin_fmaf(s_q, ra2[i].x, sa_p * ra[i].x);
+          va.y = __builtin_fmaf(s_q, ra2[i].y, sa_p * ra[i].y);
+          va.z = __builtin_fmaf(s_q, ra2[i].z, sa_p * ra[i].z);
+          va.w = __builtin_fmaf(s_q, ra2[i].w, sa_p * ra[i].w);
+        }
 #ifdef SCAN_EXP_WGRAD_NOSPLIT  // TIMING EXPERIMENT (make exp_wgrad_nosplit, never in libscan_hip.so): no conversion work
-        for (int p = 0; p < NP; ++p) pc[p] = __builtin_bit_cast(bf16x4, make_float2(ra[i].x, ra[i].y));
+        for (int p = 0; p < NP; ++p) pc[p] = __builtin_bit_cast(bf16x4, make_float2(va.x, va.y));
 #else
-        split4_np<NP>(ra[i], pc);
+        split4_np<NP>(va, pc);
 #endif
 #pragma unroll
         for (int p = 0; p < NP; ++p) *reinterpret_cast<bf16x4*>(As + p * WKC * W6ROW + off) = pc[p];
@@ -689,6 +745,12 @@ __global__ W6_BOUNDS void conv_wgrad_v6_kernel(
           bsum.y += ra[i].y;
           bsum.z += ra[i].z;
           bsum.w += ra[i].w;
+          if constexpr (WINO) {  // j = 1: both RAW rows of the pair, not their rounded sum
+            bsum.x += ra2[i].x;
+            bsum.y += ra2[i].y;
+            bsum.z += ra2[i].z;
+            bsum.w += ra2[i].w;
+          }
         }
       }
     };
@@ -700,10 +762,17 @@ __global__ W6_BOUNDS void conv_wgrad_v6_kernel(
         const int j = rr + PRG * i;
         if (j < WKC + KX - 1) {
           const int off = wsw6(j, 4 * q4);
+          float4 vb = rb[i];
+          if constexpr (WINO) {
+            vb.x = __builtin_fmaf(s_q, rb2[i].x, rb[i].x);
+            vb.y = __builtin_fmaf(s_q, rb2[i].y, rb[i].y);
+            vb.z = __builtin_fmaf(s_q, rb2[i].z, rb[i].z);
+            vb.w = __builtin_fmaf(s_q, rb2[i].w, rb[i].w);
+          }
 #ifdef SCAN_EXP_WGRAD_NOSPLIT
-          for (int p = 0; p < NP; ++p) pc[p] = __builtin_bit_cast(bf16x4, make_float2(rb[i].x, rb[i].y));
+          for (int p = 0; p < NP; ++p) pc[p] = __builtin_bit_cast(bf16x4, make_float2(vb.x, vb.y));
 #else
-          split4_np<NP>(rb[i], pc);
+          split4_np<NP>(vb, pc);
 #endif
 #pragma unroll
           for (int p = 0; p < NP; ++p) *reinterpret_cast<bf16x4*>(Bs + p * (WKC + KX - 1) * W6ROW + off) = pc[p];
@@ -932,14 +1001,79 @@ __global__ __launch_bounds__(256) void slab_bias_reduce_kernel(const float* __re
   }
 }
 
-// chunk table and split-K plan of a launch; wk = pixels per K chunk of the kernel that will run
+// The Winograd reduction: slabs [split][o][j * 3 + kx][Cs] of the four components, splits summed in order in fp64 as above,
+// G^T applied to the fp64 sums (dW[ky=0] = M0 + (M1 + M2) / 2, dW[ky=1] = (M1 - M2) / 2, dW[ky=2] = M3 + (M1 + M2) / 2), ONE
+// rounding to fp32, the usual [o][ky * 3 + kx][Cs] gradient out.  A thread owns the float4 column of one (o, kx).
+__global__ __launch_bounds__(256) void slab_bias_reduce_wino_kernel(const float* __restrict__ slab, int splits, int Cout, int Cs,
+                                                                    float* __restrict__ dw, const float* __restrict__ bs,
+                                                                    float* __restrict__ db, int accumulate) {
+  const int wblocks = gridDim.x - (db ? 1 : 0);
+  if ((int)blockIdx.x < wblocks) {
+    const int cs4 = Cs >> 2;
+    const int64_t items = (int64_t)Cout * 3 * cs4, n = (int64_t)Cout * 12 * Cs;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (int64_t)wblocks * blockDim.x) {
+      const int c4 = (int)(i % cs4);
+      const int kx = (int)((i / cs4) % 3);
+      const int64_t o = i / (3 * cs4);
+      double m[4][4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) m[j][e] = 0.0;
+      const float* base = slab + (o * 12 + kx) * Cs + 4 * c4;
+      for (int k = 0; k < splits; ++k)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float4 v = *reinterpret_cast<const float4*>(base + (int64_t)k * n + (int64_t)j * 3 * Cs);
+          m[j][0] += (double)v.x;
+          m[j][1] += (double)v.y;
+          m[j][2] += (double)v.z;
+          m[j][3] += (double)v.w;
+        }
+      float r[3][4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const double h = 0.5 * (m[1][e] + m[2][e]);
+        r[0][e] = (float)(m[0][e] + h);
+        r[1][e] = (float)(0.5 * (m[1][e] - m[2][e]));
+        r[2][e] = (float)(m[3][e] + h);
+      }
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky) {
+        float4* d = reinterpret_cast<float4*>(dw + (o * 9 + ky * 3 + kx) * Cs + 4 * c4);
+        float4 s = make_float4(r[ky][0], r[ky][1], r[ky][2], r[ky][3]);
+        if (accumulate) {
+          const float4 old = *d;
+          s.x += old.x;
+          s.y += old.y;
+          s.z += old.z;
+          s.w += old.w;
+        }
+        *d = s;
+      }
+    }
+  } else {
+    for (int i = threadIdx.x; i < Cout; i += blockDim.x) {
+      double s = 0.0;
+      for (int k = 0; k < splits; ++k) s += (double)bs[(int64_t)k * Cout + i];
+      db[i] = accumulate ? db[i] + (float)s : (float)s;
+    }
+  }
+}
+
+// scan_tune "wgrad_wino": 1 (default) = the three-piece 3x3 launches of the producer / consumer kernel on its 32 x 64 tile run
+// F(2,3) across rows (a third fewer MFMAs); 0 = the direct form, bit for bit the kernels and split-K plan without it
+int g_scan_wgrad_wino = 1;
+
+// chunk table and split-K plan of a launch; wk = pixels per K chunk of the kernel that will run; wino: chunks are row PAIRS
+// and a tile group has four components where the direct form has KX row taps
 static void wgrad_plan(const scan_pyramid_t* d, int Cs, int Cout, int KX, int wk, ChunkTab* ct, int* n_tiles, int* c_tiles,
-                       int* splits, int* cps) {
+                       int* splits, int* cps, bool wino = false) {
   ct->chunk_off[0] = 0;
   for (int l = 0; l < SCAN_MAX_LEVELS; ++l) {
     if (l < d->n_levels) {
       ct->segs[l] = (d->w[l] + wk - 1) / wk;
-      ct->chunk_off[l + 1] = ct->chunk_off[l] + (long long)d->n_images * d->h[l] * ct->segs[l];
+      ct->chunk_off[l + 1] = ct->chunk_off[l] + (long long)d->n_images * (wino ? (d->h[l] + 1) / 2 : d->h[l]) * ct->segs[l];
     } else {
       ct->segs[l] = 1;
       ct->chunk_off[l + 1] = ct->chunk_off[l];
@@ -947,7 +1081,7 @@ static void wgrad_plan(const scan_pyramid_t* d, int Cs, int Cout, int KX, int wk
   }
   const long long chunks = ct->chunk_off[d->n_levels];
   *c_tiles = (Cs + 127) / 128;
-  *n_tiles = ((Cout + 127) / 128) * KX * *c_tiles;
+  *n_tiles = ((Cout + 127) / 128) * (wino ? 4 : KX) * *c_tiles;
   // ~3 workgroups per CU in total.  Swept on the device (tower layer, two pieces, us): 256 -> 499, 512 -> 428, 768 -> 355,
   // 1024 -> 414, 1536 -> 411, 2304 -> 486: fewer splits lengthen each workgroup's serial chunk chain, more splits
   // cost slab traffic and leave partial rounds
@@ -967,11 +1101,16 @@ static void wgrad_plan(const scan_pyramid_t* d, int Cs, int Cout, int KX, int wk
 // pixels per K chunk of the kernel a 3x3 launch with np pieces takes
 static inline int wgrad3_wk(int np) { return (g_scan_wgrad_v6 && np == 3) ? 32 : WK; }
 
+// whether a 3x3 launch with np pieces takes the Winograd form: three pieces on the producer / consumer kernel's 32 x 64 tile (the
+// one with the temporary accumulator); wgrad_tile = 0 and wgrad_v6 = 0 keep their direct kernels
+static inline bool wgrad3_wino(int np) { return np == 3 && g_scan_wgrad_v6 && g_scan_wgrad_wino && g_scan_wgrad_tile != 0; }
+
 static int64_t wgrad3_ws_floats(int np, const scan_pyramid_t* d, int32_t Cs, int32_t Cout) {
   ChunkTab ct;
   int nt, ctl, sp, cps;
-  wgrad_plan(d, Cs, Cout, 3, wgrad3_wk(np), &ct, &nt, &ctl, &sp, &cps);
-  return (int64_t)sp * Cout * 9 * Cs + (int64_t)sp * Cout;
+  const bool wino = wgrad3_wino(np);
+  wgrad_plan(d, Cs, Cout, 3, wgrad3_wk(np), &ct, &nt, &ctl, &sp, &cps, wino);
+  return (int64_t)sp * Cout * (wino ? 12 : 9) * Cs + (int64_t)sp * Cout;  // slabs of 12 (j * 3 + kx) or 9 taps + bias slabs
 }
 extern "C" int64_t scan_conv3x3_wgrad_bf16x3_ws_floats(const scan_pyramid_t* d, int32_t Cs, int32_t Cout) {
   return wgrad3_ws_floats(2, d, Cs, Cout);
@@ -996,19 +1135,25 @@ static int wgrad3_launch(const float* x, const scan_pyramid_t* d, int32_t Cs, co
   constexpr int WK6 = NP == 3 ? 32 : WK;
   ChunkTab ct;
   int nt, ctl, sp, cps;
-  wgrad_plan(d, Cs, Cout, 3, wgrad3_wk(NP), &ct, &nt, &ctl, &sp, &cps);
+  const bool wino = wgrad3_wino(NP);
+  wgrad_plan(d, Cs, Cout, 3, wgrad3_wk(NP), &ct, &nt, &ctl, &sp, &cps, wino);
   hipStream_t st = as_stream(stream);
-  float* bias_slab = db ? ws + (int64_t)sp * Cout * 9 * Cs : nullptr;
+  float* bias_slab = db ? ws + (int64_t)sp * Cout * (wino ? 12 : 9) * Cs : nullptr;
   if (g_scan_wgrad_v6) {
-    constexpr size_t sh6 = (size_t)2 * W6STAGE(NP, WK6, 3) * sizeof(__bf16);
+    constexpr size_t sh6 = (size_t)2 * W6STAGE(NP, WK6, 3) * sizeof(__bf16);  // the Winograd instance stages the same LDS image
     static_assert(sh6 <= 160 * 1024, "LDS: 160 KB per CU");
     static bool done = false;
     if (!done) {
       set_lds(conv_wgrad_v6_kernel<NP, WK6, 3, 4, 2>, sh6);
       set_lds(conv_wgrad_v6_kernel<NP, WK6, 3, 2, 4>, sh6);
+      if constexpr (NP == 3) set_lds(conv_wgrad_v6_kernel<NP, WK6, 3, 2, 4, true>, sh6);
       done = true;
     }
-    if ((g_scan_wgrad_tile == 0 || g_scan_wgrad_tile == 1) ? g_scan_wgrad_tile == 1 : NP == 3)
+    if (wino) {  // only ever true for NP == 3 (wgrad3_wino)
+      if constexpr (NP == 3)
+        hipLaunchKernelGGL((conv_wgrad_v6_kernel<NP, WK6, 3, 2, 4, true>), dim3(nt * sp), dim3(W6_THREADS), sh6, st, x, *d, Cs, dy, Cout,
+                           Cout_s, ws, bias_slab, ct, nt, ctl, cps, sp, g_scan_wgrad_prio);
+    } else if ((g_scan_wgrad_tile == 0 || g_scan_wgrad_tile == 1) ? g_scan_wgrad_tile == 1 : NP == 3)
       hipLaunchKernelGGL((conv_wgrad_v6_kernel<NP, WK6, 3, 2, 4>), dim3(nt * sp), dim3(W6_THREADS), sh6, st, x, *d, Cs, dy, Cout, Cout_s,
                          ws, bias_slab, ct, nt, ctl, cps, sp, g_scan_wgrad_prio);
     else
@@ -1028,8 +1173,12 @@ static int wgrad3_launch(const float* x, const scan_pyramid_t* d, int32_t Cs, co
   SCAN_LAUNCH_CHECK(name);
   // one launch reduces the weight slabs and (last block) the bias slabs
   const int64_t n = (int64_t)Cout * 9 * Cs;
-  hipLaunchKernelGGL(slab_bias_reduce_kernel, dim3(grid_for(n / 4, 256) + (db ? 1 : 0)), dim3(256), 0, st, ws, sp, n, dw,
-                     bias_slab, Cout, db, accumulate);
+  if (wino)
+    hipLaunchKernelGGL(slab_bias_reduce_wino_kernel, dim3(grid_for((int64_t)Cout * 3 * (Cs / 4), 256) + (db ? 1 : 0)), dim3(256), 0,
+                       st, ws, sp, Cout, Cs, dw, bias_slab, db, accumulate);
+  else
+    hipLaunchKernelGGL(slab_bias_reduce_kernel, dim3(grid_for(n / 4, 256) + (db ? 1 : 0)), dim3(256), 0, st, ws, sp, n, dw,
+                       bias_slab, Cout, db, accumulate);
   SCAN_LAUNCH_CHECK("slab_bias_reduce");
   return 0;
 }

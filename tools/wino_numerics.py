@@ -13,6 +13,9 @@ Samples are output PAIRS (x, x + 1) of one output channel; inputs ~ N(0, 1), wei
 GPU test.  Prints per case the rms and worst error relative to the largest sampled output, and the ratios to fp32.
 
     python tools/wino_numerics.py [--samples 4096] [--seed 0]
+
+--wgrad: the same question for the 3x3 WEIGHT gradient with F(2,3) applied across rows (csrc/conv_wgrad.hip, wgrad_wino), see
+emulate_wgrad.  profiles/r08_wgrad_wino_numerics.txt is its output; tests/test_wgrad_wino_numerics.py pins it.
 """
 import argparse
 
@@ -101,11 +104,113 @@ def emulate(cin, n, seed):
     return res
 
 
+# ---- weight gradient, F(2,3) across rows -------------------------------------------------------------------------------
+# One sample is one (o, c, kx) of one image: dY column e[y][x] and X column d[y][x] (rows -1 and H are zero padding), and
+# the three gradients dW[ky] = sum_{y, x} e[y][x] d[y + ky - 1][x].  K runs over 32-pixel chunks of a row (direct) or of a
+# row pair (Winograd), split into slabs of `cps` chunks as wgrad_plan does; the slabs are summed in fp64.
+WGRAD_CLASSES = ("gauss", "relu_sparse", "relu_smooth_sparse")
+WGRAD_GEOM = dict(H=64, W=512, cps_direct=256, cps_wino=171, fp32_chain=9376)  # conv3_x chains: 64 / 48 / 56 splits of 4 x 256 x 512
+
+
+def wgrad_inputs(cls, n, H, W, rs):
+    e = rs.standard_normal((n, H, W)).astype(np.float32)
+    d = rs.standard_normal((n, H, W)).astype(np.float32)
+    if cls != "gauss":
+        # post-ReLU activations, and a gradient that is zero on nine pixels of ten
+        if cls == "relu_smooth_sparse":  # neighbouring rows nearly equal: d2 - d1 cancels, d1 + d2 does not
+            base = rs.standard_normal((n, 1, W)).astype(np.float32)
+            d = base + 0.1 * d
+        d = np.maximum(d, 0).astype(np.float32)
+        e = (e * (rs.random_sample((n, H, W)) < 0.1)).astype(np.float32)
+    return e, d
+
+
+def tchain(ap, bp, cps):
+    """split-K slabs of the three-piece kernels with the per-step temporary (wgrad_mma_v6_pipe): ap, bp [n, chunks, 32] fp32
+    operands; per chunk the six piece products (32-term sums exact, one rounding per MFMA) are summed from zero, smallest
+    first, and the temporary is added to the fp32 running sum once.  Returns the fp64 sum of the fp32 slabs."""
+    a3, b3 = split3(ap), split3(bp)
+    prods = [(a3[i] * b3[s - i]).sum(-1) for s in (2, 1, 0) for i in range(s, -1, -1)]  # [n, chunks] each, exact
+    n, chunks = prods[0].shape
+    total = np.zeros(n)
+    for c0 in range(0, chunks, cps):
+        acc = np.zeros(n)
+        for k in range(c0, min(c0 + cps, chunks)):
+            tmp = np.zeros(n)
+            for p in prods:
+                tmp = f32(tmp + p[:, k])
+            acc = f32(acc + tmp)
+        total += acc
+    return total
+
+
+def emulate_wgrad(cls, n, seed, H=None, W=None, cps_direct=None, cps_wino=None, fp32_chain=None):
+    geo = dict(WGRAD_GEOM)
+    geo.update({k: v for k, v in dict(H=H, W=W, cps_direct=cps_direct, cps_wino=cps_wino, fp32_chain=fp32_chain).items() if v})
+    H, W = geo["H"], geo["W"]
+    assert H % 2 == 0 and W % 32 == 0
+    rs = np.random.RandomState(seed)
+    e, d = wgrad_inputs(cls, n, H, W, rs)
+    dp = np.zeros((n, H + 2, W), np.float32)   # row y of the image is dp[:, y + 1]
+    dp[:, 1:-1] = d
+    e64, dp64 = e.astype(np.float64), dp.astype(np.float64)
+    ref = np.stack([(e64 * dp64[:, ky:ky + H]).sum((1, 2)) for ky in range(3)], 1)
+
+    # fp32 FMA chain over the pixels in memory order, split-K as the fp32-MFMA kernel plans it
+    y32 = np.zeros((n, 3))
+    for ky in range(3):
+        ef, df = e64.reshape(n, -1), dp64[:, ky:ky + H].reshape(n, -1)
+        for p0 in range(0, H * W, geo["fp32_chain"]):
+            acc = np.zeros(n)
+            for p in range(p0, min(p0 + geo["fp32_chain"], H * W)):
+                acc = f32(acc + ef[:, p] * df[:, p])
+            y32[:, ky] += acc
+    y32 = f32(y32)
+
+    # today's direct kernel: chunks walk rows, 32 pixels each
+    ydir = f32(np.stack([tchain(e.reshape(n, -1, 32), dp[:, ky:ky + H].reshape(n, -1, 32), geo["cps_direct"])
+                         for ky in range(3)], 1))
+
+    # F(2,3) across rows: A e and B^T d in fp32 (one rounding per value), four component chains over row pairs, G^T on the
+    # fp64 slab sums, one rounding to fp32
+    e0, e1 = e64[:, 0::2], e64[:, 1::2]
+    d0, d1, d2, d3 = (dp64[:, i:i + H:2] for i in range(4))
+    comps = ((e0, d0 - d2), (e0 + e1, d1 + d2), (e0 - e1, d2 - d1), (-e1, d1 - d3))
+    M = [tchain(f32(a).astype(np.float32).reshape(n, -1, 32), f32(b).astype(np.float32).reshape(n, -1, 32), geo["cps_wino"])
+         for a, b in comps]
+    ywin = f32(np.stack([M[0] + 0.5 * (M[1] + M[2]), 0.5 * (M[1] - M[2]), M[3] + 0.5 * (M[1] + M[2])], 1))
+
+    scale = np.abs(ref).max()
+    res = {}
+    for name, y in (("fp32", y32), ("direct", ydir), ("wino", ywin)):
+        err = np.abs(y - ref) / scale
+        res[name] = (float(np.sqrt((err ** 2).mean())), float(err.max()))
+    return res
+
+
+def wgrad_table(samples, seed, classes=WGRAD_CLASSES, **geo):
+    lines = []
+    for cls in classes:
+        i = WGRAD_CLASSES.index(cls)
+        r = emulate_wgrad(cls, samples, seed + i, **geo)
+        lines.append("%-19s rms fp32 %.3e direct %.3e wino %.3e | max fp32 %.3e direct %.3e wino %.3e | wino/fp32 rms %.3f max %.3f"
+                     % (cls, r["fp32"][0], r["direct"][0], r["wino"][0], r["fp32"][1], r["direct"][1], r["wino"][1],
+                        r["wino"][0] / r["fp32"][0], r["wino"][1] / r["fp32"][1]))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--samples", type=int, default=4096)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--wgrad", action="store_true", help="weight gradient, F(2,3) across rows")
     a = ap.parse_args()
+    if a.wgrad:
+        print("# 3x3 weight gradient, distance from fp64 relative to the largest sampled element; %d samples x 3 ky, geometry %s"
+              % (a.samples, WGRAD_GEOM))
+        for line in wgrad_table(a.samples, a.seed):
+            print(line)
+        return
     for cin in CASES:
         r = emulate(cin, a.samples, a.seed + cin)
         print("Cin %4d  rms fp32 %.3e direct %.3e wino %.3e | rms ratio direct %.3f wino %.3f | worst ratio direct %.3f wino %.3f"
