@@ -82,6 +82,11 @@ int scan_abi_version(void);
  *                 Slabs then hold 12 taps: scan_conv3x3_wgrad_bf16x6_ws_floats follows the knob, so size the workspace
  *                 AFTER setting it.  0: the direct kernel and split-K plan, bit for bit.  bf16x3, wgrad_v6 = 0 and
  *                 wgrad_tile = 0 are always direct.
+ *   "wino_tpb"    (bf16x6, next to "conv_wino": the Winograd F(2,3) forward / data-gradient instance, scan_conv3x3_wino_bf16x6)
+ *                 weight taps per barrier interval: 2 (default) = the patch is staged in component pairs and the LDS that frees
+ *                 holds two taps per weight buffer -- 8 barriers per 32-channel chunk, 96 MFMAs per wave between them; 1 (and
+ *                 any other value) = one tap per interval, 13 barriers per chunk.  Same results bit for bit
+ *                 (tests/test_gpu_wino_schedule.py); the GroupNorm sums agree up to the order of their fp64 atomics.
  *   "gconv_mfma"  0 (default): the grouped class-branch conv runs on fp32 FMAs; 1: tap products and data gradient on the
  *                 fp32 matrix cores (same products, different summation order; measured no faster in the step).
  *   "reduce_blocks" 2048 (default): most workgroups a loss-reduction kernel is launched with (each ends in one or two float

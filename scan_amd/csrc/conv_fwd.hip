@@ -41,8 +41,17 @@ struct TileTab2 {
 // 16-byte slot swizzle of a 64-byte row: k-group kg of row idx lives at slot kg ^ swz(idx)
 __device__ __forceinline__ int swz(int idx) { return (idx >> 1) & 2; }
 // ... of the Winograd patch (column j * 8 + t of patch row r): an MFMA fragment reads pairs t = 0..7 of TWO adjacent rows
-// (2048 B apart), so the row parity flips the slot as well -- the 16 lanes of a ds_read_b128 group hit 16 distinct slots
+// (2048 B apart; 1024 B with the 16-column patch of the two-tap schedule), so the row parity flips the slot as well -- the
+// 16 lanes of a ds_read_b128 group hit 16 distinct slots.  Only the address modulo 256 B enters: (t & 3) * 64 + slot * 16
+// for any row stride that is a multiple of 256 B, so one function serves both patch widths (SQ_LDS_BANK_CONFLICT is the
+// same count under both schedules: profiles/r09_wino_fwd_counters.txt)
 __device__ __forceinline__ int wsw(int t, int r) { return ((t >> 1) & 2) ^ (r & 1); }
+
+// a compile-time int as a lambda argument
+template <int V>
+struct IntC {
+  static constexpr int value = V;
+};
 
 // The weight plane slot I of a thread reads from, WITHOUT a run-time table: slot = tid + NT * I lies in plane slot / PL, and
 // for every instance that is one compile-time plane or one of two neighbours.  (Written as a nested select on the run-time
@@ -105,6 +114,9 @@ __device__ __forceinline__ void mma_pieces(const bf16x8 (&w)[NP], const bf16x8 (
 // staging, then split); the weight planes hold G g in 12 taps j * 3 + ky (scan_weight_split modes 2 / 3).  The MFMA
 // B operand is 16 "pixels" = 8 pairs x 2 rows of one component, so the four accumulator sets share one lane map and the
 // output transform stays in registers.  Numerics: tools/wino_numerics.py, DESIGN.md section 3.1.
+// WINO with TPB = 2 (scan_tune "wino_tpb"): the loop is component outer, ky inner, so the patch is staged in component pairs
+// (16 columns: 54 KB instead of 108) and the LDS that frees holds two taps per weight buffer (96 KB): 150 KB, 8 barriers per
+// 32-channel chunk instead of 13, 96 MFMAs per wave between them, the same products in the same order.
 template <int NP, int BN, int TH, int NT, int KS, int TPB = 1, bool GL = false, bool WINO = false>
 __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
     const float* __restrict__ src, scan_pyramid_t d, int Cs, const __bf16* __restrict__ w0, const __bf16* __restrict__ w1,
@@ -113,7 +125,8 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
     double* __restrict__ gn_ws) {
   constexpr int HALO = KS / 2, NTAPS = KS * KS;
   constexpr int PH = TH + 2 * HALO;
-  constexpr int PWK = WINO ? 32 : V2_TW + 2 * HALO;  // patch columns per row: halo pixels, or 4 components x 8 pairs
+  constexpr int WJ = WINO ? (TPB == 2 ? 2 : 4) : 1;  // Winograd components the patch holds at a time (TPB = 2: a component pair)
+  constexpr int PWK = WINO ? WJ * 8 : V2_TW + 2 * HALO;  // patch columns per row: halo pixels, or WJ components x 8 pairs
   constexpr int NPATCH = PH * PWK;
   constexpr int WTAPS = WINO ? 12 : NTAPS;            // weight taps per plane row
   constexpr int WAVES = NT / 64;
@@ -129,9 +142,9 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
   constexpr int NGRP = WTAPS / TPB;                   // barrier intervals per chunk
   static_assert(NP == 2 || NP == 3, "two or three pieces per operand");
   static_assert(TM * WM_WAVES == TH && (TM % 2) == 0, "tile rows must split evenly (and pair up for the fused pool)");
-  static_assert(NTAPS % TPB == 0, "taps per barrier must divide the tap count");
+  static_assert(WTAPS % TPB == 0, "taps per barrier must divide the tap count");
   static_assert(BSLOTS % 64 == 0, "a wave's 64 weight segments lie in one plane (and past the end only as a whole wave)");
-  static_assert(!WINO || (GL && KS == 3 && TPB == 1 && NP == 3 && TM % 2 == 0), "Winograd: three pieces, 3x3, LDS-DMA weights");
+  static_assert(!WINO || (GL && KS == 3 && (TPB == 1 || TPB == 2) && NP == 3 && TM % 2 == 0), "Winograd: three pieces, 3x3, LDS-DMA weights");
 
   extern __shared__ __align__(16) unsigned char smem_raw[];
   __bf16* As = reinterpret_cast<__bf16*>(smem_raw);  // [NP plane][NPATCH][32]
@@ -217,6 +230,21 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
   auto load_a = [&](int cc) {
     const int soff = cc * (V2_CK * 4);
     const bool kill = tail_bad && cc == nchunks - 1;
+    if constexpr (WINO && TPB == 2) {
+      // slot i, halo pixel k lie (i * (NT / 64) * W + k) * Cs floats behind slot 0's first pixel for every lane: one per-lane
+      // offset (or BAD), the rest rides in the scalar offset with the chunk -- one VGPR instead of twelve through the K loop
+      unsigned vk = vok;
+      asm volatile("" : "+v"(vk));
+#pragma unroll
+      for (int i = 0; i < ASLOTS; ++i)
+#pragma unroll
+        for (int k = 0; k < AK; ++k) {
+          const bool ok = ((vk >> (4 * i + k)) & 1) && !kill;
+          ra[i][k] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(a_src, (int)(ok ? voff[0] : BAD),
+                                                                                      soff + (i * (NT / 64) * W + k) * Cs * 4, 0));
+        }
+      return;
+    }
 #pragma unroll
     for (int i = 0; i < ASLOTS; ++i)
 #pragma unroll
@@ -225,9 +253,11 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
         ra[i][k] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(a_src, (int)(kill ? BAD : off), soff, 0));
       }
   };
-  auto store_a = [&]() {
+  auto store_a = [&](auto half_c) {
     if constexpr (WINO) {
+      constexpr int half = decltype(half_c)::value;
       // B^T d in fp32 (one rounding per value), then the exact split; component j of pair t goes to patch column j * 8 + t
+      // (TPB = 2: the patch holds components 2 half, 2 half + 1 in columns 0..15; both halves come from the same ra)
 #pragma unroll
       for (int i = 0; i < ASLOTS; ++i) {
         const int slot = tid + NT * i;
@@ -240,9 +270,9 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
                                make_float4(d1.x - d3.x, d1.y - d3.y, d1.z - d3.z, d1.w - d3.w)};
           const int sl = (((c4 >> 1) ^ wsw(t, py)) << 3) + ((c4 & 1) << 2);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
+          for (int j = 0; j < WJ; ++j) {
             bf16x4 pc[NP];
-            split4_np<NP>(u[j], pc);
+            split4_np<NP>(u[WJ == 4 ? j : 2 * half + j], pc);
             const int off = (py * PWK + j * 8 + t) * 32 + sl;
 #pragma unroll
             for (int p = 0; p < NP; ++p) *reinterpret_cast<bf16x4*>(As + p * NPATCH * 32 + off) = pc[p];
@@ -444,10 +474,11 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
     }
   };
 
-  // Winograd: one barrier interval per weight tap (j, ky); the MFMA B fragment of lane (lr, kg) is pair lr & 7 of patch
-  // row wm * TM + 2 * tm + (lr >> 3) + ky, component j
-  auto wino_mma = [&](int j, int ky, int buf, f32x4v (&aj)[WINO ? TN : 1][TMW], auto&& mid) {
-    const __bf16* bt = Bs + (buf * NP) * BN * 32 + w_off;
+  // Winograd: TPB weight taps (j, ky) per barrier interval; the MFMA B fragment of lane (lr, kg) is pair lr & 7 of patch
+  // row wm * TM + 2 * tm + (lr >> 3) + ky, component j (= its patch column block; TPB = 2: j & 1).  tt: the tap's slot in the
+  // weight buffer; with_mid: the tap that carries the interval's mid()
+  auto wino_mma = [&](int j, int ky, int buf, f32x4v (&aj)[WINO ? TN : 1][TMW], auto&& mid, int tt = 0, bool with_mid = true) {
+    const __bf16* bt = Bs + ((buf * TPB + tt) * NP) * BN * 32 + w_off;
     const int prow = wm * TM + (lr >> 3) + ky, t = lr & 7;
     const int p_off = (prow * PWK + j * 8 + t) * 32 + ((kg ^ wsw(t, prow)) << 3);
     bf16x8 pf[NP][TMW];
@@ -456,12 +487,30 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
 #pragma unroll
       for (int tm = 0; tm < TMW; ++tm)
         pf[p][tm] = *reinterpret_cast<const bf16x8*>(As + p * NPATCH * 32 + p_off + tm * 2 * PWK * 32);
+    if constexpr (TPB == 2) {
+      // the weight fragments of channel tile tn + 1 are read in front of tile tn's MFMAs (two register sets), pinned there:
+      // left alone the scheduler sinks every read to its first use and both waves of a SIMD wait out the LDS latency per tile
+      bf16x8 wf2[2][NP];
+      read_w(bt, 0, wf2[0]);
+#pragma unroll
+      for (int tn = 0; tn < TN; ++tn) {
+        if (tn + 1 < TN) read_w(bt, tn + 1, wf2[(tn + 1) & 1]);
+        __builtin_amdgcn_sched_barrier(0);
+        mma_pieces<NP, TMW>(wf2[tn & 1], pf, aj[tn]);
+        __builtin_amdgcn_sched_barrier(0);
+        if (with_mid && tn == 0) {
+          mid();
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      return;
+    }
 #pragma unroll
     for (int tn = 0; tn < TN; ++tn) {
       bf16x8 wf[NP];
       read_w(bt, tn, wf);
       mma_pieces<NP, TMW>(wf, pf, aj[tn]);
-      if (tn == (SCAN_CONV_MID >= 0 ? SCAN_CONV_MID : 0)) {
+      if (with_mid && tn == (SCAN_CONV_MID >= 0 ? SCAN_CONV_MID : 0)) {
         __builtin_amdgcn_sched_barrier(0);
         mid();
         __builtin_amdgcn_sched_barrier(0);
@@ -470,11 +519,44 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
   };
 
   load_a(0);
-  if constexpr (WINO) {
+  if constexpr (WINO && TPB == 2) {
+    // two taps per barrier interval: the patch is staged in component pairs (half the columns, which pays for the second
+    // tap's weight tiles in LDS), six intervals of taps (2 g, 2 g + 1) = j * 3 + ky in the order of the TPB = 1 loop below --
+    // every accumulator sees the same products in the same order, bit for bit.  8 barriers per chunk instead of 13, 96
+    // MFMAs per wave between them.  ra stays live until the second store; the next chunk's loads follow it in the fourth
+    // interval and have two more to land.
+    issue_b(0, 0, 0);
+    for (int cc = 0; cc < nchunks; ++cc) {
+      auto ivl = [&](auto g_c, int j0, int ky0, f32x4v (&a0)[WINO ? TN : 1][TMW], int j1, int ky1, f32x4v (&a1)[WINO ? TN : 1][TMW]) {
+        constexpr int g = decltype(g_c)::value, buf = g & 1;  // (NGRP = 6 is even: the buffer parity restarts every chunk)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();  // this interval's weight tiles are complete; the patch half is visible
+        auto feed = [&]() {
+          if (g < NGRP - 1)
+            issue_b(cc, g + 1, buf ^ 1);
+          else if (cc + 1 < nchunks)
+            issue_b(cc + 1, 0, buf ^ 1);
+          if (g == NGRP / 2 && cc + 1 < nchunks) load_a(cc + 1);
+        };
+        wino_mma(j0, ky0, buf, a0, feed, 0, true);
+        wino_mma(j1, ky1, buf, a1, no_mid, 1, false);
+      };
+      auto phase = [&](auto half_c, f32x4v (&a0)[WINO ? TN : 1][TMW], f32x4v (&a1)[WINO ? TN : 1][TMW]) {
+        __syncthreads();  // every wave is done reading the previous patch half
+        constexpr int half = decltype(half_c)::value;
+        store_a(half_c);
+        ivl(IntC<3 * half + 0>{}, 0, 0, a0, 0, 1, a0);
+        ivl(IntC<3 * half + 1>{}, 0, 2, a0, 1, 0, a1);  // the middle interval spans both components
+        ivl(IntC<3 * half + 2>{}, 1, 1, a1, 1, 2, a1);
+      };
+      phase(IntC<0>{}, wacc[0], wacc[WINO ? 1 : 0]);
+      phase(IntC<1>{}, wacc[WINO ? 2 : 0], wacc[WINO ? 3 : 0]);
+    }
+  } else if constexpr (WINO) {
     issue_b(0, 0, 0);
     for (int cc = 0; cc < nchunks; ++cc) {
       __syncthreads();  // every wave is done reading the previous chunk's patch
-      store_a();
+      store_a(IntC<0>{});
       auto comp = [&](int j, f32x4v (&aj)[WINO ? TN : 1][TMW]) {
 #pragma unroll 1
         for (int ky = 0; ky < 3; ++ky) {
@@ -503,7 +585,7 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
 #ifdef SCAN_EXP_FWD_NOFEED
       if (cc == 0 || !(SCAN_EXP_FWD_NOFEED & 2))
 #endif
-      store_a();
+      store_a(IntC<0>{});
       if (NGRP == 1 && cc + 1 < nchunks) load_a(cc + 1);
 #pragma unroll 1
       for (int grp = 0; grp < NGRP; ++grp) {
@@ -544,7 +626,7 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
     load_b(0, 0);
     for (int cc = 0; cc < nchunks; ++cc) {
       __syncthreads();  // every wave is done reading the previous chunk's patch
-      store_a();
+      store_a(IntC<0>{});
       if (cc + 1 < nchunks) load_a(cc + 1);
 #pragma unroll 1
       for (int grp = 0; grp < NGRP; ++grp) {
@@ -562,7 +644,14 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
 
   // ---- epilogue.  C/D map of 16x16: column = lane & 15 = pixel x of tile row tm, row = 4 * (lane >> 4) + reg = output
   // channel inside channel tile tn: one lane owns four consecutive channels of one pixel
-  const int x = tx0 + lr;
+  // (two-tap Winograd instance: the lane roles are derived again here instead of living in registers through the K loop)
+  constexpr bool RELANE = WINO && TPB == 2;
+  int tid2 = tid;
+  if constexpr (RELANE) asm volatile("" : "+v"(tid2));
+  const int etid = RELANE ? tid2 : tid;
+  const int ewm = RELANE ? (tid2 >> 6) / WN_WAVES : wm, ewn = RELANE ? (tid2 >> 6) % WN_WAVES : wn;
+  const int elr = RELANE ? tid2 & 15 : lr, ekg = RELANE ? (tid2 & 63) >> 4 : kg;
+  const int x = tx0 + elr;
   // GroupNorm sums leave the workgroup as ONE fp64 atomic pair per group (not one per wave and group): every tile of a frame
   // adds to the same 64 doubles, and same-address device-scope atomics serialise -- with a pair per wave the towers' forward
   // ran 20 % behind their data gradient (same kernel, same shape, no sums).  The waves' partials meet in the LDS the main
@@ -571,7 +660,7 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
   if (gn_ws != nullptr) __syncthreads();
 #pragma unroll
   for (int tn = 0; tn < TN; ++tn) {
-    const int o4 = n0 + wn * 16 * TN + tn * 16 + 4 * kg;
+    const int o4 = n0 + ewn * 16 * TN + tn * 16 + 4 * ekg;
     float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
     if (bias != nullptr) {
       bv.x = o4 + 0 < Nout ? bias[o4 + 0] : 0.f;
@@ -580,14 +669,14 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
       bv.w = o4 + 3 < Nout ? bias[o4 + 3] : 0.f;
     }
     if constexpr (WINO) {
-      // output transform A^T in fp32, m1 and m2 first; lane (lr, kg) owns pixels x0 = tx0 + 2 (lr & 7), x0 + 1 of row
-      // ty0 + wm * TM + 2 * tm + (lr >> 3)
-      const int xw = tx0 + 2 * (lr & 7);
+      // output transform A^T in fp32, m1 and m2 first; lane (elr, ekg) owns pixels x0 = tx0 + 2 (elr & 7), x0 + 1 of row
+      // ty0 + ewm * TM + 2 * tm + (elr >> 3)
+      const int xw = tx0 + 2 * (elr & 7);
       if (relu & 2) {
         // fused 2x2 / stride-2 max-pool: columns x0, x0 + 1 are this lane's pair, rows y, y + 1 are lanes l, l ^ 8
 #pragma unroll
         for (int tm = 0; tm < TMW; ++tm) {
-          const int y = ty0 + wm * TM + 2 * tm + (lr >> 3);
+          const int y = ty0 + ewm * TM + 2 * tm + (elr >> 3);
           const f32x4v m0 = wacc[0][tn][tm], m1 = wacc[WINO ? 1 : 0][tn][tm], m2 = wacc[WINO ? 2 : 0][tn][tm],
                        m3 = wacc[WINO ? 3 : 0][tn][tm];
           const f32x4v y0 = m0 + (m1 + m2), y1 = (m1 - m2) - m3;
@@ -597,7 +686,7 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
             const float m = fmaxf(y0[r], y1[r]);
             v[r] = fmaxf(m, __shfl_xor(m, 8, 64));
           }
-          if ((lr >> 3) == 0 && y < H && xw < W && o4 < Nout) {
+          if ((elr >> 3) == 0 && y < H && xw < W && o4 < Nout) {
             const int Hp = H >> 1, Wp = W >> 1;
             float4 o = make_float4(v[0] + bv.x, v[1] + bv.y, v[2] + bv.z, v[3] + bv.w);
             if (relu & 1) {
@@ -615,7 +704,7 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
       if (mask != nullptr) {
 #pragma unroll
         for (int tm = 0; tm < TMW; ++tm) {
-          const int y = ty0 + wm * TM + 2 * tm + (lr >> 3);
+          const int y = ty0 + ewm * TM + 2 * tm + (elr >> 3);
 #pragma unroll
           for (int e = 0; e < 2; ++e) {
             const bool ok = y < H && xw + e < W && o4 < Nout;
@@ -627,7 +716,7 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
       double ds = 0.0, dq = 0.0;
 #pragma unroll
       for (int tm = 0; tm < TMW; ++tm) {
-        const int y = ty0 + wm * TM + 2 * tm + (lr >> 3);
+        const int y = ty0 + ewm * TM + 2 * tm + (elr >> 3);
         const f32x4v m0 = wacc[0][tn][tm], m1 = wacc[WINO ? 1 : 0][tn][tm], m2 = wacc[WINO ? 2 : 0][tn][tm],
                      m3 = wacc[WINO ? 3 : 0][tn][tm];
         const f32x4v yv[2] = {m0 + (m1 + m2), (m1 - m2) - m3};
@@ -653,14 +742,14 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
           }
         }
       }
-      if (gn_ws != nullptr) {  // as below: reduce over the 16 lanes of a k-group and the pair kg, kg ^ 1
+      if (gn_ws != nullptr) {  // as below: reduce over the 16 lanes of a k-group and the pair ekg, ekg ^ 1
 #pragma unroll
         for (int sh = 1; sh <= 16; sh <<= 1) {
           ds += __shfl_xor(ds, sh, 64);
           dq += __shfl_xor(dq, sh, 64);
         }
-        if (lr == 0 && (kg & 1) == 0) {
-          double* r = gn_red + (wm * (BN / 8) + ((o4 - n0) >> 3)) * 2;
+        if (elr == 0 && (ekg & 1) == 0) {
+          double* r = gn_red + (ewm * (BN / 8) + ((o4 - n0) >> 3)) * 2;
           r[0] = ds;
           r[1] = dq;
         }
@@ -673,14 +762,14 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
       const int Hp = H >> 1, Wp = W >> 1;
 #pragma unroll
       for (int tm = 0; tm < TM; tm += 2) {
-        const int y = ty0 + wm * TM + tm;
+        const int y = ty0 + ewm * TM + tm;
         float v[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const float m = fmaxf(acc[tn][tm][r], acc[tn][tm + 1][r]);
           v[r] = fmaxf(m, __shfl_xor(m, 1, 64));
         }
-        if ((lr & 1) == 0 && y < H && x < W && o4 < Nout) {
+        if ((elr & 1) == 0 && y < H && x < W && o4 < Nout) {
           float4 o = make_float4(v[0] + bv.x, v[1] + bv.y, v[2] + bv.z, v[3] + bv.w);
           if (relu & 1) {
             o.x = fmaxf(o.x, 0.f);
@@ -698,7 +787,7 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
     if (mask != nullptr) {
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm) {
-        const int y = ty0 + wm * TM + tm;
+        const int y = ty0 + ewm * TM + tm;
         const bool ok = y < H && x < W && o4 < Nout;
         mk[tm] = ok ? *reinterpret_cast<const float4*>(mask + (rowbase + (int64_t)y * W + x) * Ns + o4)
                     : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -707,7 +796,7 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
     double ds = 0.0, dq = 0.0;  // fp32 over a pixel's four channels, fp64 from there on: the same for every instance
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm) {
-      const int y = ty0 + wm * TM + tm;
+      const int y = ty0 + ewm * TM + tm;
       if (y < H && x < W && o4 < Nout) {
         float4 o = make_float4(acc[tn][tm][0] + bv.x, acc[tn][tm][1] + bv.y, acc[tn][tm][2] + bv.z,
                                acc[tn][tm][3] + bv.w);
@@ -732,15 +821,15 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
       }
     }
     if (gn_ws != nullptr) {
-      // GroupNorm(32) sums of the 256-channel output: a group = 8 channels = the lane-group pair kg, kg ^ 1; reduce
+      // GroupNorm(32) sums of the 256-channel output: a group = 8 channels = the lane-group pair ekg, ekg ^ 1; reduce
       // over the 16 pixels (lanes) and that pair, one fp64 atomic pair per group and wave
 #pragma unroll
       for (int sh = 1; sh <= 16; sh <<= 1) {
         ds += __shfl_xor(ds, sh, 64);
         dq += __shfl_xor(dq, sh, 64);
       }
-      if (lr == 0 && (kg & 1) == 0) {
-        double* r = gn_red + (wm * (BN / 8) + ((o4 - n0) >> 3)) * 2;
+      if (elr == 0 && (ekg & 1) == 0) {
+        double* r = gn_red + (ewm * (BN / 8) + ((o4 - n0) >> 3)) * 2;
         r[0] = ds;
         r[1] = dq;
       }
@@ -748,12 +837,12 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
   }
   if (gn_ws != nullptr) {
     __syncthreads();
-    if (tid < BN / 8 * 2) {
-      const int g = n0 / 8 + (tid >> 1);
+    if (etid < BN / 8 * 2) {
+      const int g = n0 / 8 + (etid >> 1);
       double v = 0.0;
 #pragma unroll
-      for (int w = 0; w < WM_WAVES; ++w) v += gn_red[w * (BN / 8) * 2 + tid];
-      if (g * 8 < Nout) atomicAdd(&gn_ws[((int64_t)(lvl * d.n_images + img) * 32 + g) * 2 + (tid & 1)], v);
+      for (int w = 0; w < WM_WAVES; ++w) v += gn_red[w * (BN / 8) * 2 + etid];
+      if (g * 8 < Nout) atomicAdd(&gn_ws[((int64_t)(lvl * d.n_images + img) * 32 + g) * 2 + (etid & 1)], v);
     }
   }
 }
@@ -794,7 +883,7 @@ static void launch_v2(const ConvArgs& a) {
   make_tiles_v2(a.od, &tt, TH);
   const int tiles = tt.tile_off[a.od->n_levels];
   const int n_tiles = (a.Nout + BN - 1) / BN;
-  constexpr int PWK = WINO ? 32 : V2_TW + 2 * HALO;
+  constexpr int PWK = WINO ? (TPB == 2 ? 16 : 32) : V2_TW + 2 * HALO;  // as in the kernel
   constexpr size_t sh = (size_t)(NP * (TH + 2 * HALO) * PWK * 32 + 2 * NP * TPB * BN * 32) * sizeof(__bf16);
   static_assert(sh <= 160 * 1024, "LDS: 160 KB per CU");
   static bool done = false;
@@ -941,6 +1030,11 @@ int conv3x3_split_launch(int np, const float* x, const scan_pyramid_t* d, int32_
 // before, bit for bit.  The <= 64-channel instances and two pieces stay on the direct kernels.  Measurements: DESIGN.md
 // section 3.1.
 int g_scan_conv_wino = 1;
+// scan_tune "wino_tpb": weight taps per barrier interval of the Winograd instance -- 2 (default) = the patch staged in
+// component pairs, two taps and 96 MFMAs per wave between barriers, 8 barriers per 32-channel chunk; 1 = one tap per
+// interval, 13 barriers per chunk (the schedule of rounds 7 and 8).  Same results bit for bit.  Measurements: DESIGN.md
+// section 3.1.
+int g_scan_wino_tpb = 2;
 extern "C" int scan_conv3x3_bf16x6_wino(int32_t Nout, int32_t Csw) { return g_scan_conv_wino && Nout > 64 && Csw % 32 == 0 ? 1 : 0; }
 
 int conv3x3_wino_launch(const float* x, const scan_pyramid_t* d, int32_t Cs, const void* w0, const void* w1, const void* w2,
@@ -949,7 +1043,10 @@ int conv3x3_wino_launch(const float* x, const scan_pyramid_t* d, int32_t Cs, con
   SCAN_CHECK_ARG(Nout > 64 && Csw % 32 == 0, "conv3x3_wino_bf16x6: needs Nout > 64 and Csw %% 32 == 0 (Nout=%d Csw=%d)", Nout, Csw);
   ConvArgs a{x, d, d, Cs, {reinterpret_cast<const __bf16*>(w0), reinterpret_cast<const __bf16*>(w1),
                            reinterpret_cast<const __bf16*>(w2)}, Csw, bias, mask, y, Nout, Ns, relu, 0, as_stream(stream), gn_ws};
-  launch_v2<3, 128, 16, 512, 3, 1, true, true>(a);
+  if (g_scan_wino_tpb == 2)
+    launch_v2<3, 128, 16, 512, 3, 2, true, true>(a);
+  else
+    launch_v2<3, 128, 16, 512, 3, 1, true, true>(a);
   SCAN_LAUNCH_CHECK("conv3x3_wino_bf16x6");
   return 0;
 }
