@@ -93,7 +93,12 @@ int scan_abi_version(void);
  *                 atomics on one cache line); the IoU and CKA forward kernels take half of it.  Same sums up to the order of
  *                 the atomics.
  *   "dbscan_bf16x3" 1 (default): scan_dbscan_prepare's pairwise-distance GEMM runs as bf16x3 with a wider exact re-check
- *                 band; 0: exact fp32 matrix cores.  Same neighbour bits (pairs inside the band are decided in fp64). */
+ *                 band; 0: exact fp32 matrix cores.  Same neighbour bits (pairs inside the band are decided in fp64).
+ *   "deterministic" 0 (default): the callers of this library (scan_amd.ops, scan_amd.layers, the compiled scan_ops module) use
+ *                 the atomic loss / GroupNorm reductions; 1: they call the *_ordered entry points below and take GroupNorm
+ *                 statistics from scan_groupnorm_stats_ordered instead of a conv epilogue, so that a training step is
+ *                 reproducible bit for bit.  The library only stores this knob: NO existing entry point changes its
+ *                 signature or its behaviour with it, a C caller chooses by the symbol it calls. */
 #define SCAN_TUNE_UNKNOWN (-2147483647 - 1)
 int scan_tune(const char* key, int value);
 /* read-only: the current value of a knob (nothing is written), SCAN_TUNE_UNKNOWN for an unknown key */
@@ -174,6 +179,36 @@ int scan_cka_bce_forward_loss(const float* logits, const float* act, int64_t M, 
                               void* stream);
 int scan_cka_bce_backward_loss(const float* logits, const float* act, int64_t M, int32_t Cf, float target,
                                const float* g_loss, const float* sums, float* d_logits, void* stream);
+
+/* ---- Ordered forms of this header's loss reductions -- sigmoid focal, IoU, BCE, CKA BCE, softmax focal (no reference counterpart; the reference gets run-to-run equality from
+ *      cudnn.deterministic + its seeds, tools/train_net_da.py setup_seed) ----
+ * The entry points above end in one float atomic per workgroup: their sums depend on the order the workgroups finish in
+ * (~1e-7 relative between two runs).  Each *_ordered twin computes the same sums from the same kernel compiled with the
+ * atomics replaced: workgroup b stores its partial sums to slot ws[b][...] (ordinary stores), and a one-workgroup launch
+ * behind it adds the slots in a fixed order (lane l of a wave adds slots l, l + 64, ... ascending, the 64 lane sums go
+ * through a fixed shuffle tree) and writes -- not adds -- the result where the atomic form leaves it; the CKA loss form
+ * also writes out[2 Cf + 1], its ticket word out[2 Cf] is left alone.  The result is a function of the inputs, the shape
+ * and scan_tune "reduce_blocks" only.  ws: at least the matching *_ordered_ws_floats floats (asked under the knob values
+ * the launch runs with), one per call in flight, need not be cleared; M == 0 / P == 0 leave out as it is, so clear it as
+ * for the atomic form.  All other arguments as the twin; scan_sigmoid_focal_loss_forward_ordered requires loss_sum. */
+int64_t scan_sigmoid_focal_loss_ordered_ws_floats(int64_t M, int32_t C);
+int scan_sigmoid_focal_loss_forward_ordered(const float* logits, const int32_t* targets, int64_t M, int32_t C,
+                                            float gamma, float alpha, float* losses, float* loss_sum, float* ws,
+                                            void* stream);
+int64_t scan_iou_loss_ordered_ws_floats(int64_t P);
+int scan_iou_loss_forward_ordered(const float* pred, const float* target, const float* weight, int64_t P, float* out2,
+                                  float* ws, void* stream);
+int64_t scan_bce_logits_ordered_ws_floats(int64_t M);
+int scan_bce_logits_forward_ordered(const float* logits, const float* targets, float const_target, const float* weight,
+                                    int64_t w_stride, int64_t M, float* out2, float* ws, void* stream);
+int64_t scan_cka_bce_ordered_ws_floats(int64_t M, int32_t Cf);
+int scan_cka_bce_forward_ordered(const float* logits, const float* act, int64_t M, int32_t Cf, float target, float* out,
+                                 float* ws, void* stream);
+int scan_cka_bce_forward_loss_ordered(const float* logits, const float* act, int64_t M, int32_t Cf, float target,
+                                      float* out, float* ws, void* stream);
+int64_t scan_softmax_focal_ordered_ws_floats(int64_t M);
+int scan_softmax_focal_forward_ordered(const float* logits, const int64_t* labels, int64_t M, int32_t K, float gamma,
+                                       float* loss_sum, float* ws, void* stream);
 
 /* ---- y = alpha * x  (GradientReversalFunction: forward alpha = 1 copy, backward alpha = -lambda;
  *      discriminator/layer.py:6-24) ---- */
@@ -408,6 +443,25 @@ int scan_groupnorm_relu_backward_ld(const float* x, const float* beta, const flo
                                     const scan_pyramid_t* d, int32_t C, int32_t G, const float* stats, const float* gamma,
                                     int32_t relu, float* dx, float* dgamma, float* dbeta, int32_t accumulate, float* ws,
                                     void* stream);
+/* Ordered forms (scan_tune "deterministic"): scan_groupnorm_stats and the backward add the fp64 sums of the 256-row chunks
+ * of a (level, image) with atomics, and a double sum in another order can round to another float.  Here every workgroup
+ * stores its sums to its own slot -- ws = fp64 [level * N + image][chunk][group][2], then [workgroup][C][2] for dgamma /
+ * dbeta (backward only) -- and the consuming kernel (the statistics' final kernel; the backward's apply kernel) adds the
+ * chunks of a (level, image), and all workgroups for dgamma / dbeta, in ascending order.  ws: 16-byte aligned,
+ * scan_groupnorm_ordered_ws_floats floats, never cleared (accumulate has bit 0 only).  Same arguments otherwise; a conv whose
+ * output goes through these is launched WITHOUT epilogue sums (scan_conv3x3_bf16x6 and friends, not the _gn_ forms, whose
+ * epilogue sums are atomic), followed by scan_groupnorm_stats_ordered and scan_groupnorm_relu_forward. */
+int64_t scan_groupnorm_ordered_ws_floats(const scan_pyramid_t* d, int32_t C, int32_t G);
+int scan_groupnorm_stats_ordered(const float* x, const scan_pyramid_t* d, int32_t C, int32_t G, float eps, float* stats,
+                                 float* ws, void* stream);
+int scan_groupnorm_relu_backward_ordered(const float* x, const float* beta, const float* dy, const scan_pyramid_t* d,
+                                         int32_t C, int32_t G, const float* stats, const float* gamma, int32_t relu,
+                                         float* dx, float* dgamma, float* dbeta, int32_t accumulate, float* ws,
+                                         void* stream);
+int scan_groupnorm_relu_backward_ld_ordered(const float* x, const float* beta, const float* dy, int32_t lddy,
+                                            const scan_pyramid_t* d, int32_t C, int32_t G, const float* stats,
+                                            const float* gamma, int32_t relu, float* dx, float* dgamma, float* dbeta,
+                                            int32_t accumulate, float* ws, void* stream);
 
 /* ---- the source pass's ground-truth plan on the device (reference rpn/fcos/loss.py:40-133: FCOS location -> GT
  *      assignment and centerness targets; :428-463: graph-node sampling of the source branch).  Rows = pyramid rows

@@ -167,6 +167,24 @@ SIGNATURES = {
                                                        c_vp, c_vp]),
     "scan_resize_bilinear_u8": (ctypes.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp,
                                                c_i32, c_vp]),
+    # ordered (bit-reproducible) forms of the reductions, scan_tune "deterministic": the twin's arguments + ws before stream
+    "scan_sigmoid_focal_loss_ordered_ws_floats": (c_i64, [c_i64, c_i32]),
+    "scan_sigmoid_focal_loss_forward_ordered": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp]),
+    "scan_iou_loss_ordered_ws_floats": (c_i64, [c_i64]),
+    "scan_iou_loss_forward_ordered": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "scan_bce_logits_ordered_ws_floats": (c_i64, [c_i64]),
+    "scan_bce_logits_forward_ordered": (ctypes.c_int, [c_vp, c_vp, c_f32, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "scan_cka_bce_ordered_ws_floats": (c_i64, [c_i64, c_i32]),
+    "scan_cka_bce_forward_ordered": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i32, c_f32, c_vp, c_vp, c_vp]),
+    "scan_cka_bce_forward_loss_ordered": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i32, c_f32, c_vp, c_vp, c_vp]),
+    "scan_softmax_focal_ordered_ws_floats": (c_i64, [c_i64]),
+    "scan_softmax_focal_forward_ordered": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i32, c_f32, c_vp, c_vp, c_vp]),
+    "scan_groupnorm_ordered_ws_floats": (c_i64, [_PD, c_i32, c_i32]),
+    "scan_groupnorm_stats_ordered": (ctypes.c_int, [c_vp, _PD, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp]),
+    "scan_groupnorm_relu_backward_ordered": (ctypes.c_int, [c_vp, c_vp, c_vp, _PD, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
+                                                            c_i32, c_vp, c_vp]),
+    "scan_groupnorm_relu_backward_ld_ordered": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, _PD, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp,
+                                                               c_vp, c_vp, c_i32, c_vp, c_vp]),
     "scan_normalize_image_u8": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_f32),
                                                ctypes.POINTER(c_f32), c_vp, c_i32, c_i32, c_i32, c_vp]),
 }

@@ -36,6 +36,9 @@ extern int g_scan_wgrad_wino;
 extern int g_scan_gconv_mfma;
 extern int g_scan_dbscan_bf16x3;
 extern int g_scan_reduce_blocks;
+// "deterministic": read by the callers (scan_amd.ops, scan_amd.layers, scan_ops._ops), which then take the *_ordered entry
+// points; no entry point of the library changes its behaviour with it
+int g_scan_deterministic = 0;
 
 struct Knob {
   const char* key;
@@ -50,6 +53,7 @@ static Knob* knob_table(int* count) {
       {"wgrad_tile", &g_scan_wgrad_tile, 0},   {"wgrad_wgs", &g_scan_wgrad_wgs, 0},     {"gconv_mfma", &g_scan_gconv_mfma, 0},
       {"dbscan_bf16x3", &g_scan_dbscan_bf16x3, 0}, {"reduce_blocks", &g_scan_reduce_blocks, 0}, {"conv1x1", &g_scan_conv1x1, 0},
       {"conv_wino", &g_scan_conv_wino, 0},     {"wgrad_wino", &g_scan_wgrad_wino, 0},   {"wino_tpb", &g_scan_wino_tpb, 0},
+      {"deterministic", &g_scan_deterministic, 0},
   };
   static bool init = false;
   if (!init) {  // the values the library was built with: knobs are only ever written through scan_tune below

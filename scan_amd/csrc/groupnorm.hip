@@ -23,6 +23,8 @@ struct GnBlock {
   int il;        // image-level index
   int hw;
   bool first;    // first row chunk of its (level, image)
+  int blk0;      // block of that first chunk; the (level, image) owns blocks [blk0, blk0 + nchunk)
+  int nchunk;
 };
 __device__ __forceinline__ GnBlock gn_block(const scan_pyramid_t& d, const GnTab& t) {
   GnBlock b;
@@ -34,6 +36,8 @@ __device__ __forceinline__ GnBlock gn_block(const scan_pyramid_t& d, const GnTab
   const int n = r / t.per_img[lvl], chunk = r - n * t.per_img[lvl];
   b.il = lvl * d.n_images + n;
   b.first = chunk == 0;
+  b.blk0 = blockIdx.x - chunk;
+  b.nchunk = t.per_img[lvl];
   b.hw = d.h[lvl] * d.w[lvl];
   const int64_t start = (int64_t)chunk * GN_RPB;
   b.rows = (int)((b.hw - start) < GN_RPB ? (b.hw - start) : GN_RPB);
@@ -41,6 +45,13 @@ __device__ __forceinline__ GnBlock gn_block(const scan_pyramid_t& d, const GnTab
   return b;
 }
 
+// Ordered forms (scan_tune "deterministic", the *_ordered entry points).  ORD = false: the fp64 sums of all row chunks meet
+// in one accumulator per (level, image, group) / per channel replica through atomics, so their order -- and with it the last
+// bit of the rounded result -- follows the arrival of the blocks.  ORD = true: every block stores its sums to its own slot
+// ws[blockIdx.x][...] and the kernel that consumes them adds the slots of a (level, image) in ascending chunk order; blocks are
+// numbered level-major / image / chunk, so the workspace is the ragged [level * N + image][chunk][group][2].  Nothing is
+// cleared: every block of the grid writes every one of its slots.
+template <bool ORD>
 __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__ x, scan_pyramid_t d, GnTab tab, int G,
                                                        double* __restrict__ ws) {
   __shared__ double red[4][32][2];
@@ -72,8 +83,13 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__
     const int g = threadIdx.x;
     const double ss = red[0][g][0] + red[1][g][0] + red[2][g][0] + red[3][g][0];
     const double qq = red[0][g][1] + red[1][g][1] + red[2][g][1] + red[3][g][1];
-    atomicAdd(&ws[((int64_t)b.il * G + g) * 2 + 0], ss);
-    atomicAdd(&ws[((int64_t)b.il * G + g) * 2 + 1], qq);
+    if (ORD) {
+      ws[((int64_t)blockIdx.x * G + g) * 2 + 0] = ss;
+      ws[((int64_t)blockIdx.x * G + g) * 2 + 1] = qq;
+    } else {
+      atomicAdd(&ws[((int64_t)b.il * G + g) * 2 + 0], ss);
+      atomicAdd(&ws[((int64_t)b.il * G + g) * 2 + 1], qq);
+    }
   }
 }
 
@@ -83,15 +99,29 @@ __device__ __forceinline__ float gn_affine(float v, float mean, float rstd, floa
   return __fmaf_rn((v - mean) * rstd, ga, be);
 }
 
-__global__ void gn_stats_final_kernel(const double* __restrict__ ws, scan_pyramid_t d, int G, float eps,
+// ORD: ws holds gn_stats_kernel<true>'s per-block sums; tab locates the chunks of each (level, image)
+template <bool ORD>
+__global__ void gn_stats_final_kernel(const double* __restrict__ ws, scan_pyramid_t d, GnTab tab, int G, float eps,
                                       float* __restrict__ stats) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const int total = d.n_levels * d.n_images * G;
   if (i >= total) return;
   const int il = i / G, lvl = il / d.n_images;
   const double cnt = (double)d.h[lvl] * d.w[lvl] * (GN_C / G);
-  const double mean = ws[2 * i] / cnt;
-  double var = ws[2 * i + 1] / cnt - mean * mean;
+  double s = 0.0, q = 0.0;
+  if (ORD) {
+    const int g = i - il * G, n = il - lvl * d.n_images;
+    const int64_t blk0 = tab.blk_off[lvl] + (int64_t)n * tab.per_img[lvl];
+    for (int ch = 0; ch < tab.per_img[lvl]; ++ch) {
+      s += ws[((blk0 + ch) * G + g) * 2];
+      q += ws[((blk0 + ch) * G + g) * 2 + 1];
+    }
+  } else {
+    s = ws[2 * i];
+    q = ws[2 * i + 1];
+  }
+  const double mean = s / cnt;
+  double var = q / cnt - mean * mean;
   if (var < 0) var = 0;
   stats[2 * i] = (float)mean;
   stats[2 * i + 1] = (float)(1.0 / sqrt(var + (double)eps));
@@ -169,6 +199,7 @@ __device__ __forceinline__ float4 gn_masked(const float4 xv, float4 gv, float me
   return gv;
 }
 
+template <bool ORD>
 __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const float* __restrict__ x, const float* __restrict__ beta,
                                                             const float* __restrict__ dy, scan_pyramid_t d, GnTab tab,
                                                             int G, const float* __restrict__ stats,
@@ -228,15 +259,29 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const float* __restr
   __syncthreads();
   if (threadIdx.x < 32) {
     const int gg = threadIdx.x;
-    atomicAdd(&ws_g[((int64_t)b.il * G + gg) * 2 + 0], redg[0][gg][0] + redg[1][gg][0] + redg[2][gg][0] + redg[3][gg][0]);
-    atomicAdd(&ws_g[((int64_t)b.il * G + gg) * 2 + 1], redg[0][gg][1] + redg[1][gg][1] + redg[2][gg][1] + redg[3][gg][1]);
+    const double s1g = redg[0][gg][0] + redg[1][gg][0] + redg[2][gg][0] + redg[3][gg][0];
+    const double s2g = redg[0][gg][1] + redg[1][gg][1] + redg[2][gg][1] + redg[3][gg][1];
+    if (ORD) {  // ws_g [block][G][2]
+      ws_g[((int64_t)blockIdx.x * G + gg) * 2 + 0] = s1g;
+      ws_g[((int64_t)blockIdx.x * G + gg) * 2 + 1] = s2g;
+    } else {
+      atomicAdd(&ws_g[((int64_t)b.il * G + gg) * 2 + 0], s1g);
+      atomicAdd(&ws_g[((int64_t)b.il * G + gg) * 2 + 1], s2g);
+    }
   }
   const int c = threadIdx.x;  // 256 threads == 256 channels
-  double* rep = ws_c + (int64_t)(blockIdx.x % GN_REP) * 2 * GN_C;
-  atomicAdd(&rep[2 * c + 0], ((double)redc[0][c][0] + (double)redc[1][c][0]) + ((double)redc[2][c][0] + (double)redc[3][c][0]));
-  atomicAdd(&rep[2 * c + 1], ((double)redc[0][c][1] + (double)redc[1][c][1]) + ((double)redc[2][c][1] + (double)redc[3][c][1]));
+  const double dgc = ((double)redc[0][c][0] + (double)redc[1][c][0]) + ((double)redc[2][c][0] + (double)redc[3][c][0]);
+  const double dbc = ((double)redc[0][c][1] + (double)redc[1][c][1]) + ((double)redc[2][c][1] + (double)redc[3][c][1]);
+  if (ORD) {  // ws_c [block][C][2]
+    *reinterpret_cast<double2*>(ws_c + ((int64_t)blockIdx.x * GN_C + c) * 2) = make_double2(dgc, dbc);
+  } else {
+    double* rep = ws_c + (int64_t)(blockIdx.x % GN_REP) * 2 * GN_C;
+    atomicAdd(&rep[2 * c + 0], dgc);
+    atomicAdd(&rep[2 * c + 1], dbc);
+  }
 }
 
+template <bool ORD>
 __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float* __restrict__ x, const float* __restrict__ beta,
                                                            const float* __restrict__ dy, scan_pyramid_t d, GnTab tab,
                                                            int G, const float* __restrict__ stats,
@@ -249,10 +294,19 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float* __restri
     // dbeta here instead of in a one-block launch of its own (256 threads == 256 channels)
     const int c = threadIdx.x;
     double sa = 0.0, sb = 0.0;
+    if (ORD) {  // every block's slot, ascending
+#pragma unroll 8
+      for (int r = 0; r < (int)gridDim.x; ++r) {
+        const double2 v = *reinterpret_cast<const double2*>(ws_c + ((int64_t)r * GN_C + c) * 2);
+        sa += v.x;
+        sb += v.y;
+      }
+    } else {
 #pragma unroll
-    for (int r = 0; r < GN_REP; ++r) {
-      sa += ws_c[(int64_t)r * 2 * GN_C + 2 * c];
-      sb += ws_c[(int64_t)r * 2 * GN_C + 2 * c + 1];
+      for (int r = 0; r < GN_REP; ++r) {
+        sa += ws_c[(int64_t)r * 2 * GN_C + 2 * c];
+        sb += ws_c[(int64_t)r * 2 * GN_C + 2 * c + 1];
+      }
     }
     const float a = (float)sa, bb = (float)sb;
     dgamma[c] = accumulate ? dgamma[c] + a : a;
@@ -263,8 +317,18 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float* __restri
   const int g = lane >> 1;
   const float mean = stats[((int64_t)b.il * G + g) * 2], rstd = stats[((int64_t)b.il * G + g) * 2 + 1];
   const float inv_cnt = 1.0f / ((float)b.hw * (GN_C / G));
-  const float S1 = (float)ws_g[((int64_t)b.il * G + g) * 2] * inv_cnt;
-  const float S2 = (float)ws_g[((int64_t)b.il * G + g) * 2 + 1] * inv_cnt;
+  double s1 = 0.0, s2 = 0.0;
+  if (ORD) {  // the chunks of this (level, image), ascending
+    for (int ch = 0; ch < b.nchunk; ++ch) {
+      s1 += ws_g[((int64_t)(b.blk0 + ch) * G + g) * 2];
+      s2 += ws_g[((int64_t)(b.blk0 + ch) * G + g) * 2 + 1];
+    }
+  } else {
+    s1 = ws_g[((int64_t)b.il * G + g) * 2];
+    s2 = ws_g[((int64_t)b.il * G + g) * 2 + 1];
+  }
+  const float S1 = (float)s1 * inv_cnt;
+  const float S2 = (float)s2 * inv_cnt;
   const float4 ga = *reinterpret_cast<const float4*>(gamma + 4 * lane);
   const float4 be = relu ? *reinterpret_cast<const float4*>(beta + 4 * lane) : make_float4(0.f, 0.f, 0.f, 0.f);
   const int64_t base = b.row0 * GN_C + 4 * lane;
@@ -329,9 +393,9 @@ extern "C" int scan_groupnorm_stats(const float* x, const scan_pyramid_t* d, int
   }
   GnTab tab;
   const int nblk = gn_tab(d, &tab);
-  hipLaunchKernelGGL(gn_stats_kernel, dim3(nblk), dim3(256), 0, st, x, *d, tab, G, wsd);
+  hipLaunchKernelGGL(gn_stats_kernel<false>, dim3(nblk), dim3(256), 0, st, x, *d, tab, G, wsd);
   SCAN_LAUNCH_CHECK("gn_stats");
-  hipLaunchKernelGGL(gn_stats_final_kernel, dim3((total + 255) / 256), dim3(256), 0, st, wsd, *d, G, eps, stats);
+  hipLaunchKernelGGL(gn_stats_final_kernel<false>, dim3((total + 255) / 256), dim3(256), 0, st, wsd, *d, tab, G, eps, stats);
   SCAN_LAUNCH_CHECK("gn_stats_final");
   return 0;
 }
@@ -342,8 +406,10 @@ extern "C" int scan_groupnorm_stats_from_sums(const float* ws, const scan_pyrami
   if (gn_check(d, C, G, "groupnorm_stats_from_sums")) return -1;
   SCAN_CHECK_ARG(ws && stats, "groupnorm_stats_from_sums: null pointer");
   const int total = d->n_levels * d->n_images * G;
-  hipLaunchKernelGGL(gn_stats_final_kernel, dim3((total + 255) / 256), dim3(256), 0, as_stream(stream),
-                     reinterpret_cast<const double*>(ws), *d, G, eps, stats);
+  GnTab tab;
+  gn_tab(d, &tab);
+  hipLaunchKernelGGL(gn_stats_final_kernel<false>, dim3((total + 255) / 256), dim3(256), 0, as_stream(stream),
+                     reinterpret_cast<const double*>(ws), *d, tab, G, eps, stats);
   SCAN_LAUNCH_CHECK("gn_stats_final");
   return 0;
 }
@@ -418,10 +484,10 @@ extern "C" int scan_groupnorm_relu_backward_ld(const float* x, const float* beta
   }
   GnTab tab;
   const int nblk = gn_tab(d, &tab);
-  hipLaunchKernelGGL(gn_bwd_reduce_kernel, dim3(nblk), dim3(256), 0, st, x, beta, dy, *d, tab, G, stats, gamma, relu, ws_g, ws_c,
+  hipLaunchKernelGGL(gn_bwd_reduce_kernel<false>, dim3(nblk), dim3(256), 0, st, x, beta, dy, *d, tab, G, stats, gamma, relu, ws_g, ws_c,
                      lddy);
   SCAN_LAUNCH_CHECK("gn_bwd_reduce");
-  hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(nblk), dim3(256), 0, st, x, beta, dy, *d, tab, G, stats, gamma, relu, ws_g, dx,
+  hipLaunchKernelGGL(gn_bwd_apply_kernel<false>, dim3(nblk), dim3(256), 0, st, x, beta, dy, *d, tab, G, stats, gamma, relu, ws_g, dx,
                      ws_c, dgamma, dbeta, accumulate & 1, lddy);
   SCAN_LAUNCH_CHECK("gn_bwd_apply");
   return 0;
@@ -433,4 +499,60 @@ extern "C" int scan_groupnorm_relu_backward(const float* x, const float* beta, c
                                             void* stream) {
   return scan_groupnorm_relu_backward_ld(x, beta, dy, C, d, C, G, stats, gamma, relu, dx, dgamma, dbeta, accumulate, ws,
                                          stream);
+}
+
+// ---- ordered forms: the same kernels with ORD = true, per-block partial sums in ws instead of atomics ----
+// doubles: the backward's [blocks][G][2] + [blocks][C][2] (the statistics need the first part only)
+extern "C" int64_t scan_groupnorm_ordered_ws_floats(const scan_pyramid_t* d, int32_t C, int32_t G) {
+  GnTab tab;
+  const int64_t nblk = gn_tab(d, &tab);
+  return 2 * (nblk * G * 2 + nblk * C * 2);
+}
+
+extern "C" int scan_groupnorm_stats_ordered(const float* x, const scan_pyramid_t* d, int32_t C, int32_t G, float eps,
+                                            float* stats, float* ws, void* stream) {
+  if (gn_check(d, C, G, "groupnorm_stats_ordered")) return -1;
+  SCAN_CHECK_ARG(x && stats && ws, "groupnorm_stats_ordered: null pointer");
+  hipStream_t st = as_stream(stream);
+  double* wsd = reinterpret_cast<double*>(ws);
+  const int total = d->n_levels * d->n_images * G;
+  GnTab tab;
+  const int nblk = gn_tab(d, &tab);
+  if (nblk > 0) {
+    hipLaunchKernelGGL(gn_stats_kernel<true>, dim3(nblk), dim3(256), 0, st, x, *d, tab, G, wsd);
+    SCAN_LAUNCH_CHECK("gn_stats_ordered");
+  }
+  hipLaunchKernelGGL(gn_stats_final_kernel<true>, dim3((total + 255) / 256), dim3(256), 0, st, wsd, *d, tab, G, eps, stats);
+  SCAN_LAUNCH_CHECK("gn_stats_final_ordered");
+  return 0;
+}
+
+extern "C" int scan_groupnorm_relu_backward_ld_ordered(const float* x, const float* beta, const float* dy, int32_t lddy,
+                                                       const scan_pyramid_t* d, int32_t C, int32_t G, const float* stats,
+                                                       const float* gamma, int32_t relu, float* dx, float* dgamma,
+                                                       float* dbeta, int32_t accumulate, float* ws, void* stream) {
+  if (gn_check(d, C, G, "groupnorm_relu_backward_ordered") || gn_ld_check(lddy, C, "groupnorm_relu_backward_ordered")) return -1;
+  SCAN_CHECK_ARG(x && dy && stats && gamma && dx && dgamma && dbeta && ws && (beta || !relu),
+                 "groupnorm_relu_backward_ordered: null pointer");
+  hipStream_t st = as_stream(stream);
+  GnTab tab;
+  const int nblk = gn_tab(d, &tab);
+  SCAN_CHECK_ARG(nblk > 0, "groupnorm_relu_backward_ordered: empty pyramid");
+  double* ws_g = reinterpret_cast<double*>(ws);
+  double* ws_c = ws_g + (int64_t)nblk * G * 2;
+  hipLaunchKernelGGL(gn_bwd_reduce_kernel<true>, dim3(nblk), dim3(256), 0, st, x, beta, dy, *d, tab, G, stats, gamma, relu, ws_g,
+                     ws_c, lddy);
+  SCAN_LAUNCH_CHECK("gn_bwd_reduce_ordered");
+  hipLaunchKernelGGL(gn_bwd_apply_kernel<true>, dim3(nblk), dim3(256), 0, st, x, beta, dy, *d, tab, G, stats, gamma, relu, ws_g, dx,
+                     ws_c, dgamma, dbeta, accumulate & 1, lddy);
+  SCAN_LAUNCH_CHECK("gn_bwd_apply_ordered");
+  return 0;
+}
+
+extern "C" int scan_groupnorm_relu_backward_ordered(const float* x, const float* beta, const float* dy,
+                                                    const scan_pyramid_t* d, int32_t C, int32_t G, const float* stats,
+                                                    const float* gamma, int32_t relu, float* dx, float* dgamma, float* dbeta,
+                                                    int32_t accumulate, float* ws, void* stream) {
+  return scan_groupnorm_relu_backward_ld_ordered(x, beta, dy, C, d, C, G, stats, gamma, relu, dx, dgamma, dbeta, accumulate, ws,
+                                                 stream);
 }

@@ -97,7 +97,21 @@ __device__ __forceinline__ void focal_rowcol(int64_t q, int C, const int* __rest
   }
 }
 
-template <int CT, bool G2>
+// ------------------------------------------------------------------ ordered reductions (scan_tune "deterministic")
+// Every reducing kernel below ends in one line: the block's partial sum goes to `dst`.  ORD = false (the product default):
+// a float atomic on dst[k] -- fastest, but the sum then depends on the order the blocks arrive in.  ORD = true (the *_ordered
+// entry points): an ordinary store to the block's own slot dst[blockIdx.x][k] of a caller-supplied workspace, which
+// ordered_sum_kernel -- a launch of its own behind the kernel -- adds up in a fixed order.  A second launch, not the
+// last-arriving block: stream order makes every slot visible to it with no fence, ticket or device-scope read-back (the
+// per-XCD L2s are not coherent: a last block would have to read 2,048 slots back past its own L2), and no block ever
+// depends on another.
+template <bool ORD>
+__device__ __forceinline__ void block_result(float* __restrict__ dst, int k, int ncols, float v) {
+  if (ORD) dst[(int64_t)blockIdx.x * ncols + k] = v;
+  else atomicAdd(dst + k, v);
+}
+
+template <int CT, bool G2, bool ORD = false>
 __global__ __launch_bounds__(256) void focal_fwd_kernel(const float* __restrict__ logits,
                                                         const int* __restrict__ targets, int64_t total, int C,
                                                         float gamma, float alpha, float* __restrict__ losses,
@@ -135,11 +149,11 @@ __global__ __launch_bounds__(256) void focal_fwd_kernel(const float* __restrict_
   }
   if (loss_sum != nullptr) {
     const float s = block_sum_256(acc, red);
-    if (threadIdx.x == 0) atomicAdd(loss_sum, s);
+    if (threadIdx.x == 0) block_result<ORD>(loss_sum, 0, 1, s);
   }
 }
 
-template <int CT, bool G2>
+template <int CT, bool G2, bool ORD = false>  // ORD: unused, FOCAL_DISPATCH names every kernel with three arguments
 __global__ __launch_bounds__(256) void focal_bwd_kernel(const float* __restrict__ logits,
                                                         const int* __restrict__ targets,
                                                         const float* __restrict__ d_losses, float d_scale,
@@ -196,19 +210,19 @@ static inline int grid_reduce(int64_t work_items, int block, bool light = false)
   return (int)g;
 }
 
-#define FOCAL_DISPATCH(KERNEL, GRID, ...)                                                                           \
+#define FOCAL_DISPATCH(KERNEL, ORD, GRID, ...)                                                                          \
   do {                                                                                                              \
     const bool g2 = gamma == 2.0f;                                                                                  \
     const bool al = (total & 3) == 0;                                                                               \
     if (C == 8 && al) {                                                                                             \
-      if (g2) hipLaunchKernelGGL((KERNEL<8, true>), dim3(GRID), dim3(256), 0, as_stream(stream), __VA_ARGS__);      \
-      else hipLaunchKernelGGL((KERNEL<8, false>), dim3(GRID), dim3(256), 0, as_stream(stream), __VA_ARGS__);        \
+      if (g2) hipLaunchKernelGGL((KERNEL<8, true, ORD>), dim3(GRID), dim3(256), 0, as_stream(stream), __VA_ARGS__);      \
+      else hipLaunchKernelGGL((KERNEL<8, false, ORD>), dim3(GRID), dim3(256), 0, as_stream(stream), __VA_ARGS__);        \
     } else if (C == 1 && al && (reinterpret_cast<uintptr_t>(targets) & 15) == 0) {                                  \
-      if (g2) hipLaunchKernelGGL((KERNEL<1, true>), dim3(GRID), dim3(256), 0, as_stream(stream), __VA_ARGS__);      \
-      else hipLaunchKernelGGL((KERNEL<1, false>), dim3(GRID), dim3(256), 0, as_stream(stream), __VA_ARGS__);        \
+      if (g2) hipLaunchKernelGGL((KERNEL<1, true, ORD>), dim3(GRID), dim3(256), 0, as_stream(stream), __VA_ARGS__);      \
+      else hipLaunchKernelGGL((KERNEL<1, false, ORD>), dim3(GRID), dim3(256), 0, as_stream(stream), __VA_ARGS__);        \
     } else {                                                                                                        \
-      if (g2) hipLaunchKernelGGL((KERNEL<0, true>), dim3(GRID), dim3(256), 0, as_stream(stream), __VA_ARGS__);      \
-      else hipLaunchKernelGGL((KERNEL<0, false>), dim3(GRID), dim3(256), 0, as_stream(stream), __VA_ARGS__);        \
+      if (g2) hipLaunchKernelGGL((KERNEL<0, true, ORD>), dim3(GRID), dim3(256), 0, as_stream(stream), __VA_ARGS__);      \
+      else hipLaunchKernelGGL((KERNEL<0, false, ORD>), dim3(GRID), dim3(256), 0, as_stream(stream), __VA_ARGS__);        \
     }                                                                                                               \
   } while (0)
 
@@ -221,7 +235,7 @@ extern "C" int scan_sigmoid_focal_loss_forward(const float* logits, const int32_
   SCAN_CHECK_ARG(logits && targets, "sigmoid_focal_loss_forward: null input");
   const int64_t total = M * C;
   const int grid = loss_sum ? grid_reduce((total + 3) / 4, 256) : grid_for((total + 3) / 4, 256);
-  FOCAL_DISPATCH(focal_fwd_kernel, grid, logits, targets, total, C, gamma, alpha, losses, loss_sum);
+  FOCAL_DISPATCH(focal_fwd_kernel, false, grid, logits, targets, total, C, gamma, alpha, losses, loss_sum);
   SCAN_LAUNCH_CHECK("focal_fwd");
   return 0;
 }
@@ -234,7 +248,7 @@ extern "C" int scan_sigmoid_focal_loss_backward(const float* logits, const int32
   SCAN_CHECK_ARG(logits && targets && d_logits, "sigmoid_focal_loss_backward: null pointer");
   const int64_t total = M * C;
   const int grid = grid_for((total + 3) / 4, 256);
-  FOCAL_DISPATCH(focal_bwd_kernel, grid, logits, targets, d_losses, d_scale, total, C, gamma, alpha, d_logits);
+  FOCAL_DISPATCH(focal_bwd_kernel, false, grid, logits, targets, d_losses, d_scale, total, C, gamma, alpha, d_logits);
   SCAN_LAUNCH_CHECK("focal_bwd");
   return 0;
 }
@@ -257,6 +271,7 @@ __device__ __forceinline__ IouTerms iou_terms(const float4 p, const float4 t) {
   return r;
 }
 
+template <bool ORD>
 __global__ __launch_bounds__(256) void iou_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ target,
                                                       const float* __restrict__ weight, int64_t P,
                                                       float* __restrict__ out2) {
@@ -272,8 +287,8 @@ __global__ __launch_bounds__(256) void iou_fwd_kernel(const float* __restrict__ 
   const float sn = block_sum_256(num, red);
   const float sd = block_sum_256(den, red);
   if (threadIdx.x == 0) {
-    atomicAdd(out2, sn);
-    atomicAdd(out2 + 1, sd);
+    block_result<ORD>(out2, 0, 2, sn);
+    block_result<ORD>(out2, 1, 2, sd);
   }
 }
 
@@ -306,7 +321,7 @@ extern "C" int scan_iou_loss_forward(const float* pred, const float* target, con
   SCAN_CHECK_ARG(P >= 0 && out2, "iou_loss_forward: bad arguments");
   if (P == 0) return 0;
   SCAN_CHECK_ARG(pred && target, "iou_loss_forward: null input");
-  hipLaunchKernelGGL(iou_fwd_kernel, dim3(grid_reduce(P, 256, true)), dim3(256), 0, as_stream(stream), pred, target, weight, P,
+  hipLaunchKernelGGL(iou_fwd_kernel<false>, dim3(grid_reduce(P, 256, true)), dim3(256), 0, as_stream(stream), pred, target, weight, P,
                      out2);
   SCAN_LAUNCH_CHECK("iou_fwd");
   return 0;
@@ -326,7 +341,7 @@ extern "C" int scan_iou_loss_backward(const float* pred, const float* target, co
 // ------------------------------------------------------------------ BCE with logits (optionally weighted)
 // VEC: logits / targets / weight (unit stride) read as float4 -- four times fewer load instructions for the same bytes (the
 // scalar form ran at 0.25 of the HBM roof at M = 2^24, bound by load issue: profiles/r04_pointwise_roofline.json)
-template <bool VEC>
+template <bool VEC, bool ORD = false>
 __global__ __launch_bounds__(256) void bce_fwd_kernel(const float* __restrict__ logits,
                                                       const float* __restrict__ targets, float const_target,
                                                       const float* __restrict__ weight, int64_t w_stride, int64_t M,
@@ -361,8 +376,8 @@ __global__ __launch_bounds__(256) void bce_fwd_kernel(const float* __restrict__ 
   const float sn = block_sum_256(num, red);
   const float sd = block_sum_256(den, red);
   if (threadIdx.x == 0) {
-    atomicAdd(out2, sn);
-    atomicAdd(out2 + 1, sd);
+    block_result<ORD>(out2, 0, 2, sn);
+    block_result<ORD>(out2, 1, 2, sd);
   }
 }
 
@@ -432,6 +447,7 @@ __device__ __forceinline__ void cka_finish(float* __restrict__ out, int Cf, floa
     fin[1] = s / (float)Cf;
   }
 }
+template <bool ORD>
 __global__ __launch_bounds__(256) void cka_fwd_kernel(const float* __restrict__ logits, const float* __restrict__ act,
                                                       int64_t M, int Cf, float t, float* __restrict__ out,
                                                       float* __restrict__ fin) {
@@ -457,17 +473,18 @@ __global__ __launch_bounds__(256) void cka_fwd_kernel(const float* __restrict__ 
       const float sn = block_sum_256(num[c], red);
       const float sd = block_sum_256(den[c], red);
       if (threadIdx.x == 0) {
-        atomicAdd(out + 2 * c, sn);
-        atomicAdd(out + 2 * c + 1, sd);
+        block_result<ORD>(out, 2 * c, 2 * Cf, sn);
+        block_result<ORD>(out, 2 * c + 1, 2 * Cf, sd);
       }
     }
   }
-  if (fin != nullptr) cka_finish(out, Cf, fin);
+  if (!ORD && fin != nullptr) cka_finish(out, Cf, fin);  // ORD: ordered_sum_kernel forms the loss
 }
 
 // Cf == 8 (Cityscapes): a thread owns one float4 of logits = half a row, i.e. ALWAYS the same four classes (the grid
 // stride is even), so its eight partial sums stay in registers; the act-map row (9 floats, unaligned) is read by the two
 // lanes of a row as 4 + 4 scalars of one contiguous wave-wide segment.  Even / odd lanes are reduced separately.
+template <bool ORD>
 __global__ __launch_bounds__(256) void cka_fwd8_kernel(const float* __restrict__ logits, const float* __restrict__ act,
                                                        int64_t M, float t, float* __restrict__ out,
                                                        float* __restrict__ fin) {
@@ -500,8 +517,9 @@ __global__ __launch_bounds__(256) void cka_fwd8_kernel(const float* __restrict__
     }
   }
   __syncthreads();
-  if (threadIdx.x < 16) atomicAdd(out + threadIdx.x, red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]);
-  if (fin != nullptr) cka_finish(out, 8, fin);
+  if (threadIdx.x < 16)
+    block_result<ORD>(out, threadIdx.x, 16, red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]);
+  if (!ORD && fin != nullptr) cka_finish(out, 8, fin);
 }
 
 // sums == nullptr: g [Cf] are the per-class coefficients; else g [1] is the gradient of the loss scalar and the
@@ -530,9 +548,9 @@ static int cka_forward_launch(const float* logits, const float* act, int64_t M, 
   SCAN_CHECK_ARG(logits && act, "cka_bce_forward: null input");
   if (Cf == 8 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0) {
     int g = grid_reduce(M * 2, 256, true);
-    hipLaunchKernelGGL(cka_fwd8_kernel, dim3(g), dim3(256), 0, as_stream(stream), logits, act, M, target, out, fin);
+    hipLaunchKernelGGL(cka_fwd8_kernel<false>, dim3(g), dim3(256), 0, as_stream(stream), logits, act, M, target, out, fin);
   } else {
-    hipLaunchKernelGGL(cka_fwd_kernel, dim3(grid_reduce(M, 256)), dim3(256), 0, as_stream(stream), logits, act, M, Cf,
+    hipLaunchKernelGGL(cka_fwd_kernel<false>, dim3(grid_reduce(M, 256)), dim3(256), 0, as_stream(stream), logits, act, M, Cf,
                        target, out, fin);
   }
   SCAN_LAUNCH_CHECK("cka_fwd");
@@ -606,7 +624,7 @@ extern "C" int scan_scale(const float* x, float alpha, float* y, int64_t n, void
 // conflict-free for odd K); LDS operations of one wave execute in order, so a wave-level fence is all that is needed.
 // Two 64-row batches are in flight per wave and iteration (the first cut -- 256 rows per workgroup between two
 // __syncthreads -- spent 72 % of its wave cycles parked: profiles/r03_pointwise_counters.txt).
-template <bool BWD>
+template <bool BWD, bool ORD = false>
 __global__ __launch_bounds__(256) void sfl_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
                                                   int64_t M, int K, float gamma, float d_scale,
                                                   float* __restrict__ loss_sum, float* __restrict__ d_logits) {
@@ -726,7 +744,7 @@ __global__ __launch_bounds__(256) void sfl_kernel(const float* __restrict__ logi
   }
   if (!BWD) {
     const float sum = block_sum_256(acc, red);
-    if (threadIdx.x == 0) atomicAdd(loss_sum, sum);
+    if (threadIdx.x == 0) block_result<ORD>(loss_sum, 0, 1, sum);
   }
 }
 
@@ -754,6 +772,150 @@ extern "C" int scan_softmax_focal_backward(const float* logits, const int64_t* l
                      d_scale, (float*)nullptr, d_logits);
   SCAN_LAUNCH_CHECK("sfl_bwd");
   return 0;
+}
+
+// ------------------------------------------------------------------ ordered forms of the loss reductions
+// Second stage: out[k] = sum over the blocks' slots part[b][k], b < nblk, in one fixed order -- lane l of the wave that owns
+// column k adds slots l, l + 64, l + 128, ... in ascending order, then the 64 lane sums go through wave_sum's fixed shuffle
+// tree.  One workgroup; the result is a function of the slots and of nblk alone.  fin != nullptr (CKA): the loss
+// fin[1] = sum_c (out[2c] / out[2c+1]) / Cf of cka_finish, from the sums just formed.
+__global__ __launch_bounds__(256) void ordered_sum_kernel(const float* __restrict__ part, int nblk, int ncols,
+                                                          float* __restrict__ out, int Cf, float* __restrict__ fin) {
+  __shared__ float tot[2 * CKA_MAXC];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  for (int k = wid; k < ncols; k += 4) {
+    float s = 0.f;
+    for (int b = lane; b < nblk; b += 64) s += part[(int64_t)b * ncols + k];
+    s = wave_sum(s);
+    if (lane == 0) {
+      tot[k] = s;
+      out[k] = s;
+    }
+  }
+  if (fin != nullptr) {
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      float s = 0.f;
+      for (int c = 0; c < Cf; ++c) s += tot[2 * c] / tot[2 * c + 1];
+      fin[1] = s / (float)Cf;
+    }
+  }
+}
+
+static int ordered_sum_launch(const float* part, int nblk, int ncols, float* out, int Cf, float* fin, void* stream,
+                              const char* who) {
+  hipLaunchKernelGGL(ordered_sum_kernel, dim3(1), dim3(256), 0, as_stream(stream), part, nblk, ncols, out, Cf, fin);
+  SCAN_LAUNCH_CHECK(who);
+  return 0;
+}
+
+// grids of the first stages: the ones the atomic entry points launch, under the current "reduce_blocks"
+static inline int sfl_fwd_grid(int64_t M) {
+  int64_t g = (M + 511) / 512;  // a workgroup iteration covers 4 waves x 2 batches x 64 rows
+  return (int)(g > 2048 ? 2048 : (g < 1 ? 1 : g));
+}
+static inline bool cka_is8(const float* logits, int32_t Cf) { return Cf == 8 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0; }
+
+extern "C" int64_t scan_sigmoid_focal_loss_ordered_ws_floats(int64_t M, int32_t C) {
+  return grid_reduce((M * C + 3) / 4, 256);
+}
+extern "C" int64_t scan_iou_loss_ordered_ws_floats(int64_t P) { return 2 * (int64_t)grid_reduce(P, 256, true); }
+// the scalar form's grid (the float4 form never launches more blocks)
+extern "C" int64_t scan_bce_logits_ordered_ws_floats(int64_t M) { return 2 * (int64_t)grid_reduce(M, 256); }
+// the larger of the two forms (Cf == 8 takes the float4 kernel only when logits is 16-byte aligned)
+extern "C" int64_t scan_cka_bce_ordered_ws_floats(int64_t M, int32_t Cf) {
+  const int g = std::max(grid_reduce(M, 256), Cf == 8 ? grid_reduce(M * 2, 256, true) : 0);
+  return 2 * (int64_t)Cf * g;
+}
+extern "C" int64_t scan_softmax_focal_ordered_ws_floats(int64_t M) { return sfl_fwd_grid(M); }
+
+extern "C" int scan_sigmoid_focal_loss_forward_ordered(const float* logits, const int32_t* targets, int64_t M, int32_t C,
+                                                       float gamma, float alpha, float* losses, float* loss_sum, float* ws,
+                                                       void* stream) {
+  SCAN_CHECK_ARG(M >= 0 && C > 0, "sigmoid_focal_loss_forward_ordered: bad shape M=%lld C=%d", (long long)M, C);
+  SCAN_CHECK_ARG(loss_sum && ws, "sigmoid_focal_loss_forward_ordered: loss_sum and ws are required");
+  if (M == 0) return 0;
+  SCAN_CHECK_ARG(logits && targets, "sigmoid_focal_loss_forward_ordered: null input");
+  const int64_t total = M * C;
+  const int grid = grid_reduce((total + 3) / 4, 256);
+  FOCAL_DISPATCH(focal_fwd_kernel, true, grid, logits, targets, total, C, gamma, alpha, losses, ws);
+  SCAN_LAUNCH_CHECK("focal_fwd_ordered");
+  return ordered_sum_launch(ws, grid, 1, loss_sum, 0, nullptr, stream, "focal_fwd_ordered_sum");
+}
+
+extern "C" int scan_iou_loss_forward_ordered(const float* pred, const float* target, const float* weight, int64_t P,
+                                             float* out2, float* ws, void* stream) {
+  SCAN_CHECK_ARG(P >= 0 && out2 && ws, "iou_loss_forward_ordered: bad arguments");
+  if (P == 0) return 0;
+  SCAN_CHECK_ARG(pred && target, "iou_loss_forward_ordered: null input");
+  const int grid = grid_reduce(P, 256, true);
+  hipLaunchKernelGGL(iou_fwd_kernel<true>, dim3(grid), dim3(256), 0, as_stream(stream), pred, target, weight, P, ws);
+  SCAN_LAUNCH_CHECK("iou_fwd_ordered");
+  return ordered_sum_launch(ws, grid, 2, out2, 0, nullptr, stream, "iou_fwd_ordered_sum");
+}
+
+extern "C" int scan_bce_logits_forward_ordered(const float* logits, const float* targets, float const_target,
+                                               const float* weight, int64_t w_stride, int64_t M, float* out2, float* ws,
+                                               void* stream) {
+  SCAN_CHECK_ARG(M >= 0 && out2 && ws, "bce_logits_forward_ordered: bad arguments");
+  if (M == 0) return 0;
+  SCAN_CHECK_ARG(logits, "bce_logits_forward_ordered: null input");
+  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+  int grid;
+  if (M >= 4096 && al16(logits) && (!targets || al16(targets)) && (!weight || (w_stride == 1 && al16(weight)))) {
+    grid = std::min(512, grid_reduce((M + 3) / 4, 256));
+    hipLaunchKernelGGL((bce_fwd_kernel<true, true>), dim3(grid), dim3(256), 0, as_stream(stream), logits, targets, const_target,
+                       weight, w_stride, M, ws);
+  } else {
+    grid = grid_reduce(M, 256);
+    hipLaunchKernelGGL((bce_fwd_kernel<false, true>), dim3(grid), dim3(256), 0, as_stream(stream), logits, targets, const_target,
+                       weight, w_stride, M, ws);
+  }
+  SCAN_LAUNCH_CHECK("bce_fwd_ordered");
+  return ordered_sum_launch(ws, grid, 2, out2, 0, nullptr, stream, "bce_fwd_ordered_sum");
+}
+
+static int cka_forward_ordered_launch(const float* logits, const float* act, int64_t M, int32_t Cf, float target, float* out,
+                                      float* fin, float* ws, void* stream) {
+  SCAN_CHECK_ARG(M >= 0 && Cf > 0 && Cf <= CKA_MAXC && out && ws, "cka_bce_forward_ordered: bad arguments (Cf=%d)", Cf);
+  if (M == 0) return 0;
+  SCAN_CHECK_ARG(logits && act, "cka_bce_forward_ordered: null input");
+  int grid;
+  if (cka_is8(logits, Cf)) {
+    grid = grid_reduce(M * 2, 256, true);
+    hipLaunchKernelGGL(cka_fwd8_kernel<true>, dim3(grid), dim3(256), 0, as_stream(stream), logits, act, M, target, ws,
+                       (float*)nullptr);
+  } else {
+    grid = grid_reduce(M, 256);
+    hipLaunchKernelGGL(cka_fwd_kernel<true>, dim3(grid), dim3(256), 0, as_stream(stream), logits, act, M, Cf, target, ws,
+                       (float*)nullptr);
+  }
+  SCAN_LAUNCH_CHECK("cka_fwd_ordered");
+  return ordered_sum_launch(ws, grid, 2 * Cf, out, Cf, fin, stream, "cka_fwd_ordered_sum");
+}
+
+extern "C" int scan_cka_bce_forward_ordered(const float* logits, const float* act, int64_t M, int32_t Cf, float target,
+                                            float* out, float* ws, void* stream) {
+  return cka_forward_ordered_launch(logits, act, M, Cf, target, out, nullptr, ws, stream);
+}
+
+// out: 2 * Cf + 2 floats as scan_cka_bce_forward_loss; the ticket word out[2 Cf] is not touched
+extern "C" int scan_cka_bce_forward_loss_ordered(const float* logits, const float* act, int64_t M, int32_t Cf, float target,
+                                                 float* out, float* ws, void* stream) {
+  SCAN_CHECK_ARG(M > 0, "cka_bce_forward_loss_ordered: needs at least one row (the loss is a ratio of sums)");
+  return cka_forward_ordered_launch(logits, act, M, Cf, target, out, out ? out + 2 * Cf : nullptr, ws, stream);
+}
+
+extern "C" int scan_softmax_focal_forward_ordered(const float* logits, const int64_t* labels, int64_t M, int32_t K,
+                                                  float gamma, float* loss_sum, float* ws, void* stream) {
+  SCAN_CHECK_ARG(M >= 0 && K > 0 && K <= SFL_MAXK && loss_sum && ws, "softmax_focal_forward_ordered: bad arguments (K=%d)", K);
+  if (M == 0) return 0;
+  SCAN_CHECK_ARG(logits && labels, "softmax_focal_forward_ordered: null input");
+  const int grid = sfl_fwd_grid(M);
+  hipLaunchKernelGGL((sfl_kernel<false, true>), dim3(grid), dim3(256), 0, as_stream(stream), logits, labels, M, K, gamma, 0.f, ws,
+                     (float*)nullptr);
+  SCAN_LAUNCH_CHECK("sfl_fwd_ordered");
+  return ordered_sum_launch(ws, grid, 1, loss_sum, 0, nullptr, stream, "sfl_fwd_ordered_sum");
 }
 
 // ------------------------------------------------------------------ fused SGD + momentum + weight decay

@@ -327,12 +327,40 @@ struct Conv2dFn : public torch::autograd::Function<Conv2dFn> {
 // ---- nn.GroupNorm(32, 256) (+ ReLU) on rows ------------------------------------------------------------------------------
 constexpr int kGroups = 32;
 
+// scan_tune "deterministic" (include/scan_hip.h), read at every call that chooses a reduction -- the library's knob is the
+// only copy of the switch, scan_amd.ops reads the same one: the ordered GroupNorm entry points, no conv-epilogue sums
+bool deterministic() { return scan_tune_get("deterministic") == 1; }
+
+// (mean, rstd) of rows xr -> stats, by the atomic or the ordered statistics kernels
+void gn_rows_stats(const at::Tensor& xr, const scan_pyramid_t& d, int32_t c, double eps, at::Tensor& stats) {
+  const bool det = deterministic();
+  const int64_t nws = det ? scan_groupnorm_ordered_ws_floats(&d, c, kGroups) : scan_groupnorm_ws_floats(&d, c, kGroups);
+  at::Tensor ws = at::empty({nws / 2 + 1}, xr.options().dtype(at::kDouble));
+  if (det)
+    check(scan_groupnorm_stats_ordered(xr.data_ptr<float>(), &d, c, kGroups, (float)eps, stats.data_ptr<float>(),
+                                       reinterpret_cast<float*>(ws.data_ptr()), cur_stream(xr)),
+          "scan_groupnorm_stats_ordered");
+  else
+    check(scan_groupnorm_stats(xr.data_ptr<float>(), &d, c, kGroups, (float)eps, stats.data_ptr<float>(),
+                               reinterpret_cast<float*>(ws.data_ptr()), cur_stream(xr)),
+          "scan_groupnorm_stats");
+}
+
 at::Tensor gn_rows_backward(const at::Tensor& xr, const at::Tensor& gamma, const at::Tensor& beta, const at::Tensor& stats,
                             const at::Tensor& dyr, const scan_pyramid_t& d, bool relu, at::Tensor& dgamma, at::Tensor& dbeta) {
   const int32_t C = (int32_t)xr.size(1);
   at::Tensor dx = at::empty_like(xr);
   dgamma = at::empty({C}, xr.options());
   dbeta = at::empty({C}, xr.options());
+  if (deterministic()) {
+    at::Tensor ws = at::empty({scan_groupnorm_ordered_ws_floats(&d, C, kGroups) / 2 + 1}, xr.options().dtype(at::kDouble));
+    check(scan_groupnorm_relu_backward_ordered(xr.data_ptr<float>(), beta.data_ptr<float>(), dyr.data_ptr<float>(), &d, C, kGroups,
+                                               stats.data_ptr<float>(), gamma.data_ptr<float>(), relu ? 1 : 0, dx.data_ptr<float>(),
+                                               dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), 0,
+                                               reinterpret_cast<float*>(ws.data_ptr()), cur_stream(xr)),
+          "scan_groupnorm_relu_backward_ordered");
+    return dx;
+  }
   at::Tensor ws = at::empty({scan_groupnorm_ws_floats(&d, C, kGroups) / 2 + 1}, xr.options().dtype(at::kDouble));
   check(scan_groupnorm_relu_backward(xr.data_ptr<float>(), beta.data_ptr<float>(), dyr.data_ptr<float>(), &d, C, kGroups,
                                      stats.data_ptr<float>(), gamma.data_ptr<float>(), relu ? 1 : 0, dx.data_ptr<float>(),
@@ -350,11 +378,8 @@ struct GroupNormReluFn : public torch::autograd::Function<GroupNormReluFn> {
     const scan_pyramid_t d = one_level(n, h, w);
     at::Tensor gc = gamma.contiguous(), bc = beta.contiguous();
     at::Tensor stats = at::empty({n * kGroups * 2}, xr.options()), y = at::empty_like(xr);
-    at::Tensor ws = at::empty({scan_groupnorm_ws_floats(&d, (int32_t)c, kGroups) / 2 + 1}, xr.options().dtype(at::kDouble));
     void* st = cur_stream(xr);
-    check(scan_groupnorm_stats(xr.data_ptr<float>(), &d, (int32_t)c, kGroups, (float)eps, stats.data_ptr<float>(),
-                               reinterpret_cast<float*>(ws.data_ptr()), st),
-          "scan_groupnorm_stats");
+    gn_rows_stats(xr, d, (int32_t)c, eps, stats);
     check(scan_groupnorm_relu_forward(xr.data_ptr<float>(), &d, (int32_t)c, kGroups, stats.data_ptr<float>(), gc.data_ptr<float>(),
                                       bc.data_ptr<float>(), relu ? 1 : 0, y.data_ptr<float>(), st),
           "scan_groupnorm_relu_forward");
@@ -384,12 +409,20 @@ struct ConvGnReluFn : public torch::autograd::Function<ConvGnReluFn> {
     at::Tensor wp = pack_weight(weight), gc = gamma.contiguous(), bc = beta.contiguous();
     at::Tensor cb = bias.defined() ? bias.contiguous() : bias;
     const scan_pyramid_t d = one_level(g.n, g.h, g.w);
-    at::Tensor sums = at::empty({g.n * kGroups * 2}, xr.options().dtype(at::kDouble));  // cleared by the conv launch
+    // deterministic mode: the conv runs without epilogue sums (they are atomic), the ordered statistics kernel reads its output
+    const bool det = deterministic();
+    at::Tensor sums = det ? at::Tensor() : at::empty({g.n * kGroups * 2}, xr.options().dtype(at::kDouble));  // cleared by the conv launch
     const bool wp_view = wp.data_ptr() == weight.data_ptr();
     at::Tensor c = conv_rows_forward(xr, wp, cb, g, false, sums, wp_view ? wp : at::Tensor());
     ctx->saved_data["wp_view"] = wp_view;
     at::Tensor stats = at::empty({g.n * kGroups * 2}, xr.options()), y = at::empty_like(c);
-    check(scan_groupnorm_relu_forward_from_sums(c.data_ptr<float>(), &d, 256, kGroups, reinterpret_cast<float*>(sums.data_ptr()),
+    if (det) {
+      gn_rows_stats(c, d, 256, eps, stats);
+      check(scan_groupnorm_relu_forward(c.data_ptr<float>(), &d, 256, kGroups, stats.data_ptr<float>(), gc.data_ptr<float>(),
+                                        bc.data_ptr<float>(), relu ? 1 : 0, y.data_ptr<float>(), cur_stream(xr)),
+            "scan_groupnorm_relu_forward");
+    } else
+      check(scan_groupnorm_relu_forward_from_sums(c.data_ptr<float>(), &d, 256, kGroups, reinterpret_cast<float*>(sums.data_ptr()),
                                                 (float)eps, gc.data_ptr<float>(), bc.data_ptr<float>(), relu ? 1 : 0, y.data_ptr<float>(),
                                                 stats.data_ptr<float>(), cur_stream(xr)),
           "scan_groupnorm_relu_forward_from_sums");

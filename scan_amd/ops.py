@@ -45,6 +45,25 @@ def pad4(c):
     return (c + 3) // 4 * 4
 
 
+# ----------------------------------------------------------------------------- deterministic mode
+# scan_tune "deterministic" (SCAN_TUNE=deterministic=1) lives in the library and is the only copy of the switch: it is read
+# at every call that chooses between an atomic reduction and its *_ordered twin -- here, in scan_amd.layers and in the
+# compiled scan_ops module -- never cached.  With it on, two runs from one seed end with the same bits.
+def deterministic():
+    return query("scan_tune_get", b"deterministic") == 1
+
+
+def set_deterministic(flag):
+    """switch the ordered reductions on / off; returns the previous setting (as scan_tune does)"""
+    return query("scan_tune", b"deterministic", 1 if flag else 0) == 1
+
+
+def _partials(name, like, *args):
+    """the per-workgroup slots of an *_ordered call (name: its *_ordered_ws_floats query): one fresh buffer per call, so
+    calls on side streams never share one; not cleared -- every workgroup of the launch writes all of its slots"""
+    return torch.empty((max(int(query(name, *args)), 1),), dtype=torch.float32, device=like.device)
+
+
 class KernelTimer:
     """Optional HIP-event timing of the MFMA conv launches on the stream they run on (bench.py uses it
     for the live roofline figure).  Disabled by default: no events are recorded."""
@@ -531,7 +550,10 @@ class _Conv2d(torch.autograd.Function):
                 y = _conv_split(x, shape, wp, cout, oshape.rows, cs, 0, bias, relu, cout_s,
                                     ("conv3x3_%s_fwd" if ksize == 3 else "conv1x1_%s_fwd") % tag, flops,
                                     cache_key=ckey, dst_shape=oshape, cmap=stride - 1, param=weight,
-                                    gn_sums=gn_sums and ksize == 3 and cout == 256 and cout_s == 256 and not relu,
+                                    # deterministic mode: the epilogue's sums are atomic -- groupnorm_relu then takes its
+                                    # statistics from the ordered stats kernel (one more read of y)
+                                    gn_sums=gn_sums and ksize == 3 and cout == 256 and cout_s == 256 and not relu
+                                    and not deterministic(),
                                     out=out)
         else:
             y = out if out is not None else (x.new_zeros if cout_s != cout else x.new_empty)((oshape.rows, cout_s))
@@ -901,6 +923,8 @@ class _GroupNormReLU(torch.autograd.Function):
         st = _stream()
         stats = x.new_empty((shape.n_levels * shape.n_images * 32 * 2,))
         sums = _gn_sums.pop(x.data_ptr(), None)
+        if sums is not None and deterministic():  # epilogue sums of a conv that ran before the mode was switched on
+            sums = None
         if out_buf is None:
             y, ldy = torch.empty_like(x), C
         else:  # normalise straight into the first C columns of a wider matrix (cat_into completes it)
@@ -918,9 +942,11 @@ class _GroupNormReLU(torch.autograd.Function):
             call("scan_groupnorm_relu_forward_from_sums_ld", _ptr(x), shape.ref(), C, 32, _ptr(sums), eps, _ptr(gamma),
                  _ptr(beta), int(relu), _ptr(y), ldy, _ptr(stats), st)
         else:
-            nws = query("scan_groupnorm_ws_floats", shape.ref(), C, 32)
+            det = deterministic()
+            nws = query("scan_groupnorm_ordered_ws_floats" if det else "scan_groupnorm_ws_floats", shape.ref(), C, 32)
             ws = torch.empty((nws // 2 + 1,), dtype=torch.float64, device=x.device)
-            call("scan_groupnorm_stats", _ptr(x), shape.ref(), C, 32, eps, _ptr(stats), _ptr(ws), st)
+            call("scan_groupnorm_stats_ordered" if det else "scan_groupnorm_stats", _ptr(x), shape.ref(), C, 32, eps,
+                 _ptr(stats), _ptr(ws), st)
             call("scan_groupnorm_relu_forward_ld", _ptr(x), shape.ref(), C, 32, _ptr(stats), _ptr(gamma), _ptr(beta),
                  int(relu), _ptr(y), ldy, st)
         ctx.save_for_backward(x, beta, gamma, stats)  # the backward recomputes the ReLU mask from x: y is not kept
@@ -939,12 +965,20 @@ class _GroupNormReLU(torch.autograd.Function):
         lddy = _col_slice_ld(dy, C)  # e.g. the first C columns of the class-branch conv's data gradient: read in place
         if lddy is None:
             dy, lddy = dy.contiguous(), C
-        nws = query("scan_groupnorm_ws_floats", shape.ref(), C, 32)
-        ws, cleared = _ws_f64(nws // 2 + 1, x.device)
         dx = torch.empty_like(x)
         direct = ctx.gbuf is not None
         dg = ctx.gbuf if direct else x.new_empty((C,))
         db = ctx.bbuf if direct else x.new_empty((C,))
+        if deterministic():  # per-block slots, all written by the launch: no zeroed pool slice needed
+            nws = query("scan_groupnorm_ordered_ws_floats", shape.ref(), C, 32)
+            ws = torch.empty((nws // 2 + 1,), dtype=torch.float64, device=x.device)
+            call("scan_groupnorm_relu_backward_ld_ordered", _ptr(x), _ptr(beta), _ptr(dy), lddy, shape.ref(), C, 32,
+                 _ptr(stats), _ptr(gamma), int(relu), _ptr(dx), _ptr(dg), _ptr(db), int(direct), _ptr(ws), _stream())
+            if direct:
+                return dx, None, None, None, None, None, None
+            return dx, dg, db, None, None, None, None
+        nws = query("scan_groupnorm_ws_floats", shape.ref(), C, 32)
+        ws, cleared = _ws_f64(nws // 2 + 1, x.device)
         call("scan_groupnorm_relu_backward_ld", _ptr(x), _ptr(beta), _ptr(dy), lddy, shape.ref(), C, 32, _ptr(stats),
              _ptr(gamma), int(relu), _ptr(dx), _ptr(dg), _ptr(db), int(direct) | (2 if cleared else 0), _ptr(ws), _stream())
         if direct:
@@ -1062,8 +1096,13 @@ class _SigmoidFocalSum(torch.autograd.Function):
             raise RuntimeError("targets must be int32")
         M, C = logits.shape
         out = logits.new_zeros((1,))
-        call("scan_sigmoid_focal_loss_forward", _ptr(logits), _ptr(targets), M, C, gamma, alpha, None, _ptr(out),
-             _stream())
+        if deterministic():
+            ws = _partials("scan_sigmoid_focal_loss_ordered_ws_floats", logits, M, C)
+            call("scan_sigmoid_focal_loss_forward_ordered", _ptr(logits), _ptr(targets), M, C, gamma, alpha, None, _ptr(out),
+                 _ptr(ws), _stream())
+        else:
+            call("scan_sigmoid_focal_loss_forward", _ptr(logits), _ptr(targets), M, C, gamma, alpha, None, _ptr(out),
+                 _stream())
         ctx.save_for_backward(logits, targets)
         ctx.cfg = (gamma, alpha)
         return out[0]
@@ -1116,7 +1155,11 @@ class _IouLoss(torch.autograd.Function):
         _chk(pred, target, weight)
         P = pred.shape[0]
         out = pred.new_zeros((2,))
-        call("scan_iou_loss_forward", _ptr(pred), _ptr(target), _ptr(weight), P, _ptr(out), _stream())
+        if deterministic():
+            ws = _partials("scan_iou_loss_ordered_ws_floats", pred, P)
+            call("scan_iou_loss_forward_ordered", _ptr(pred), _ptr(target), _ptr(weight), P, _ptr(out), _ptr(ws), _stream())
+        else:
+            call("scan_iou_loss_forward", _ptr(pred), _ptr(target), _ptr(weight), P, _ptr(out), _stream())
         ctx.save_for_backward(pred, target, weight, out)
         return out[0] / out[1]
 
@@ -1141,7 +1184,11 @@ class _BceLogitsMean(torch.autograd.Function):
         _chk(logits, targets)
         M = logits.numel()
         out = logits.new_zeros((2,))
-        call("scan_bce_logits_forward", _ptr(logits), _ptr(targets), 0.0, None, 0, M, _ptr(out), _stream())
+        if deterministic():
+            ws = _partials("scan_bce_logits_ordered_ws_floats", logits, M)
+            call("scan_bce_logits_forward_ordered", _ptr(logits), _ptr(targets), 0.0, None, 0, M, _ptr(out), _ptr(ws), _stream())
+        else:
+            call("scan_bce_logits_forward", _ptr(logits), _ptr(targets), 0.0, None, 0, M, _ptr(out), _stream())
         ctx.save_for_backward(logits, targets)
         return out[0] / M
 
@@ -1159,6 +1206,15 @@ def bce_with_logits_mean(logits, targets):
     return _BceLogitsMean.apply(logits.contiguous(), targets.contiguous())
 
 
+def _cka_forward_loss(logits, act, M, cf, target, out):
+    """out [2 cf + 2]: the per-class sums, a ticket word, the loss (atomic form: last block; ordered form: second launch)"""
+    if deterministic():
+        ws = _partials("scan_cka_bce_ordered_ws_floats", logits, M, cf)
+        call("scan_cka_bce_forward_loss_ordered", _ptr(logits), _ptr(act), M, cf, target, _ptr(out), _ptr(ws), _stream())
+    else:
+        call("scan_cka_bce_forward_loss", _ptr(logits), _ptr(act), M, cf, target, _ptr(out), _stream())
+
+
 class _CkaBce(torch.autograd.Function):
     """sum_c [ sum_m act[m,c+1] bce(logit[m,c], t) / sum_m act[m,c+1] ] / Cf -- one launch forward (the last block to
     finish forms the scalar), one launch backward (the kernel forms the per-class coefficients from the gradient of the
@@ -1171,7 +1227,7 @@ class _CkaBce(torch.autograd.Function):
         assert logits.shape[1] == cf and act.shape[1] == cf + 1
         out = _zeros_f32(2 * cf + 2, logits.device)
         if M > 0:
-            call("scan_cka_bce_forward_loss", _ptr(logits), _ptr(act), M, cf, target, _ptr(out), _stream())
+            _cka_forward_loss(logits, act, M, cf, target, out)
         ctx.save_for_backward(logits, act, out)
         ctx.cfg = (target, cf)
         return out[2 * cf + 1] if M > 0 else out[2 * cf + 1] / 0.0  # no rows: the reference's 0 / 0
@@ -1200,7 +1256,7 @@ class _CkaBcePair(torch.autograd.Function):
         outs = []
         for lo, hi, target in ((0, m, 1.0), (m, M, 0.0)):
             out = _zeros_f32(2 * cf + 2, logits.device)
-            call("scan_cka_bce_forward_loss", _ptr(logits[lo:hi]), _ptr(act[lo:hi]), hi - lo, cf, target, _ptr(out), _stream())
+            _cka_forward_loss(logits[lo:hi], act[lo:hi], hi - lo, cf, target, out)
             outs.append(out)
         ctx.save_for_backward(logits, act, outs[0], outs[1])
         ctx.cfg = (m, cf)
@@ -1266,7 +1322,11 @@ class _SoftmaxFocalMean(torch.autograd.Function):
             raise RuntimeError("labels must be int64")
         M, K = logits.shape
         out = logits.new_zeros((1,))
-        call("scan_softmax_focal_forward", _ptr(logits), _ptr(labels), M, K, gamma, _ptr(out), _stream())
+        if deterministic():
+            ws = _partials("scan_softmax_focal_ordered_ws_floats", logits, M)
+            call("scan_softmax_focal_forward_ordered", _ptr(logits), _ptr(labels), M, K, gamma, _ptr(out), _ptr(ws), _stream())
+        else:
+            call("scan_softmax_focal_forward", _ptr(logits), _ptr(labels), M, K, gamma, _ptr(out), _stream())
         ctx.save_for_backward(logits, labels)
         ctx.gamma = gamma
         return out[0] / M
