@@ -48,7 +48,7 @@ int scan_abi_version(void);
  *                 the launch keeps >= 2 workgroups per CU (rounds 2-4); 0: always 128-channel tiles.  Same results bit for bit.
  *   "conv_v2"     1 (default): bf16x3 forward / data-gradient convs run on the v_mfma_f32_16x16x32_bf16 kernel
  *                 (csrc/conv_fwd.hip); 0: on the independent v_mfma_f32_32x32x16_bf16 kernel kept for cross-checks
- *                 (csrc/conv_bf16x3.hip; same arithmetic, different summation order inside a 32-channel chunk).
+ *                 (csrc/conv_gen1.hip; same arithmetic, different summation order inside a 32-channel chunk).
  *   "conv_wg1024" (bf16x3) 1 (default): the 128- / 256-channel forward / dgrad instances run 16 waves per workgroup; 0: 8
  *                 waves; 2: 16 waves only for the 256-channel tile on multi-level pyramids.  Same results bit for bit.
  *   "conv_w8"     (bf16x3) 1 (default): the 256-channel LDS-DMA forward / dgrad tile runs on 8 waves (64 px x 128 ch per

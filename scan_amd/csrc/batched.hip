@@ -23,7 +23,7 @@
 //   modes 2 / 3 (Winograd F(2,3) planes of modes 0 / 1, 12 taps per row, T = 9): mode 2 as mode 0 (a thread reads the
 //          three source taps of its 8 plane elements), mode 3 as mode 1 with each tile element combined from the three
 //          source taps of its output tap on the read side.
-// Same element arithmetic as weight_split_kernel (conv_bf16x3.hip): bit-identical planes.
+// Same element arithmetic as weight_split_kernel (conv_api.hip): bit-identical planes.
 #define SPLIT_ELEMS_PER_BLOCK 2048
 #define SPLIT_TILE 64
 

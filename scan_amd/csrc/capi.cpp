@@ -4,6 +4,7 @@
 #include <string.h>
 
 #include "../../include/scan_hip.h"
+#include "conv_launch.h"
 
 static thread_local char g_err[512] = "";
 
@@ -17,25 +18,7 @@ extern "C" void scan_set_error(const char* fmt, ...) {
 extern "C" const char* scan_last_error(void) { return g_err; }
 extern "C" int scan_abi_version(void) { return 1; }
 
-// launch-selection knobs (scan_tune): defined next to the launch code that reads them
-extern int g_scan_conv_bn256;
-extern int g_scan_conv_v2;
-extern int g_scan_conv_wg1024;
-extern int g_scan_conv_w8;
-extern int g_scan_conv_tpb3;
-extern int g_scan_conv_bn64_th16;
-extern int g_scan_conv_glds;
-extern int g_scan_conv1x1;
-extern int g_scan_conv_wino;
-extern int g_scan_wino_tpb;
-extern int g_scan_wgrad_v6;
-extern int g_scan_wgrad_prio;
-extern int g_scan_wgrad_tile;
-extern int g_scan_wgrad_wgs;
-extern int g_scan_wgrad_wino;
-extern int g_scan_gconv_mfma;
-extern int g_scan_dbscan_bf16x3;
-extern int g_scan_reduce_blocks;
+// launch-selection knobs (scan_tune): defined next to the launch code that reads them, declared in conv_launch.h
 // "deterministic": read by the callers (scan_amd.ops, scan_amd.layers, scan_ops._ops), which then take the *_ordered entry
 // points; no entry point of the library changes its behaviour with it
 int g_scan_deterministic = 0;

@@ -21,9 +21,10 @@
 // History of the structure with its measurements: DESIGN.md section 3.1 (16x16x32 against 32x32x16: profiles/
 // r02_mfma_shape_experiment.txt; LDS-DMA weight tiles: r02_conv_instances.txt; buffer-load staging and the ablations that
 // located the remaining time: r03_conv_fwd.txt, r03_conv_exp.txt).
+#include "conv_launch.h"
 #include "conv_split.h"
 
-#define V2_TW 16
+#define V2_TW CONV_TILE_W
 #ifndef SCAN_CONV_MID
 #define SCAN_CONV_MID 0  // channel tile of a barrier interval behind whose MFMAs the LDS-DMA path feeds the next tile; -1: right behind the barrier
 #endif
@@ -31,12 +32,6 @@
 #define SCAN_CONV_PFA 1  // 8-wave LDS-DMA instance, NP = 2: patch fragments of the next tap prefetched in front of the barrier
 #endif
 #define V2_CK 32  // channels per K chunk = one k-step of v_mfma_f32_16x16x32_bf16
-
-struct TileTab2 {
-  int tile_off[SCAN_MAX_LEVELS + 1];
-  int tiles_x[SCAN_MAX_LEVELS];
-  int tiles_y[SCAN_MAX_LEVELS];
-};
 
 // 16-byte slot swizzle of a 64-byte row: k-group kg of row idx lives at slot kg ^ swz(idx)
 __device__ __forceinline__ int swz(int idx) { return (idx >> 1) & 2; }
@@ -420,11 +415,7 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
         bf16x8 wf[NP];
         read_w(bt, tn, wf);
         mma_pieces<NP, TM>(wf, pf, acc[tn]);
-#ifdef SCAN_EXP_MID_STAGGER  // timing experiment (make exp_mid_stagger): the second wave of a SIMD feeds half an interval later
-        if (tt == 0 && tn == ((wid >= WAVES / 2 && TN >= 8) ? SCAN_EXP_MID_STAGGER : SCAN_CONV_MID)) {
-#else
         if (tt == 0 && tn == SCAN_CONV_MID) {
-#endif
           __builtin_amdgcn_sched_barrier(0);
           mid();
           __builtin_amdgcn_sched_barrier(0);
@@ -582,9 +573,6 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
     issue_b(0, 0, 0);
     for (int cc = 0; cc < nchunks; ++cc) {
       __syncthreads();  // every wave is done reading the previous chunk's patch
-#ifdef SCAN_EXP_FWD_NOFEED
-      if (cc == 0 || !(SCAN_EXP_FWD_NOFEED & 2))
-#endif
       store_a(IntC<0>{});
       if (NGRP == 1 && cc + 1 < nchunks) load_a(cc + 1);
 #pragma unroll 1
@@ -595,14 +583,6 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();  // this tap's weight tile is complete; the patch is visible
         auto feed = [&]() {
-#ifdef SCAN_EXP_FWD_NOFEED  // TIMING EXPERIMENT (make exp_fwd_nofeed [M=1|2|3], WRONG results): bit 0 = no weight-tile DMA, bit 1 = no
-          // patch loads / conversion / LDS writes after the first chunk
-          if ((SCAN_EXP_FWD_NOFEED & 1) && !(SCAN_EXP_FWD_NOFEED & 2)) {
-            if (NGRP > 1 && grp == NGRP - 2 && cc + 1 < nchunks) load_a(cc + 1);
-            return;
-          }
-          if ((SCAN_EXP_FWD_NOFEED & 3) == 3) return;
-#endif
           // the other buffer was last read one tap ago: the next tap's tile goes there while this one is multiplied
           if (grp < NGRP - 1)
             issue_b(cc, grp + 1, buf ^ 1);
@@ -812,9 +792,6 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
           o.z = (mk[tm].z > 0.f) ? o.z : 0.f;
           o.w = (mk[tm].w > 0.f) ? o.w : 0.f;
         }
-#ifdef SCAN_EXP_FWD_NOSTORE  // TIMING EXPERIMENT (make exp_fwd_nostore, never in libscan_hip.so): the epilogue without its stores
-        if (o.x == 1.2345e30f)
-#endif
         *reinterpret_cast<float4*>(dst + (rowbase + (int64_t)y * W + x) * Ns + o4) = o;
         ds += (double)((o.x + o.y) + (o.z + o.w));
         dq += (double)((o.x * o.x + o.y * o.y) + (o.z * o.z + o.w * o.w));
@@ -847,40 +824,11 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
   }
 }
 
-static void make_tiles_v2(const scan_pyramid_t* d, TileTab2* tt, int TH) {
-  tt->tile_off[0] = 0;
-  for (int l = 0; l < SCAN_MAX_LEVELS; ++l) {
-    if (l < d->n_levels) {
-      tt->tiles_x[l] = (d->w[l] + V2_TW - 1) / V2_TW;
-      tt->tiles_y[l] = (d->h[l] + TH - 1) / TH;
-      tt->tile_off[l + 1] = tt->tile_off[l] + d->n_images * tt->tiles_x[l] * tt->tiles_y[l];
-    } else {
-      tt->tiles_x[l] = tt->tiles_y[l] = 1;
-      tt->tile_off[l + 1] = tt->tile_off[l];
-    }
-  }
-}
-
-struct ConvArgs {
-  const float* x;
-  const scan_pyramid_t* od;  // output pyramid (tiles are enumerated over it)
-  const scan_pyramid_t* sd;  // source pyramid (== od unless a stride-2 1x1 map is in play)
-  int32_t Cs;
-  const __bf16* w[3];
-  int32_t Csw;
-  const float* bias;
-  const float* mask;
-  float* y;
-  int32_t Nout, Ns, relu, map;
-  hipStream_t st;
-  double* gn_ws;
-};
-
 template <int NP, int BN, int TH, int NT, int KS, int TPB = 1, bool GL = false, bool WINO = false>
 static void launch_v2(const ConvArgs& a) {
   constexpr int HALO = KS / 2;
   TileTab2 tt;
-  make_tiles_v2(a.od, &tt, TH);
+  make_tiles(a.od, &tt, TH);
   const int tiles = tt.tile_off[a.od->n_levels];
   const int n_tiles = (a.Nout + BN - 1) / BN;
   constexpr int PWK = WINO ? (TPB == 2 ? 16 : 32) : V2_TW + 2 * HALO;  // as in the kernel
@@ -897,9 +845,27 @@ static void launch_v2(const ConvArgs& a) {
                      a.map, a.gn_ws);
 }
 
-// Instance choice for an output pyramid and channel count: 64 (8x16- or 16x16-pixel tiles, 256 threads), 128 or 256
+// ---- the instance picker: which instantiation above one (pieces, Nout, pyramid, knobs) tuple runs.  The launches
+// (conv_api.hip) and the scan_conv*_instance queries both go through pick3x3 / pick1x1, so the id a query reports is the id of
+// the kernel the launch takes.
+
+// does the 256-channel tile cost a round of 256 CUs?  (one workgroup per CU either way; a 256-channel workgroup runs twice as
+// long as a 128-channel one and reads half the fragments per MFMA): the wider tile whenever it does not -- conv5_x on 4 frames
+// (128 pixel tiles x 2: one full round of 256-channel workgroups instead of two of 128-channel ones), conv4_x on the 2 frames of
+// inference
+static bool wide_tile_costs_no_round(int64_t tiles, int32_t Nout) {
+  const int64_t r256 = (tiles * (Nout / 256) + 255) / 256 * 2, r128 = (tiles * (Nout / 128) + 255) / 256;
+  return r256 * 97 <= r128 * 100;  // (the wider tile is ~3 % faster per unit of work: a tie of many rounds goes to it)
+}
+static int64_t tiles16(const scan_pyramid_t* od) {
+  TileTab2 tt;
+  make_tiles(od, &tt, 16);
+  return tt.tile_off[od->n_levels];
+}
+
+// Channel tile of a 3x3 launch for an output pyramid and channel count: 64 (8x16- or 16x16-pixel tiles, 256 threads), 128 or 256
 // (16x16-pixel tiles; 256 when the channels fill 256-wide tiles and the launch keeps >= 2 workgroups per CU).
-int g_scan_conv_bn256 = 2;  // scan_tune "conv_bn256": 0 keeps every launch on the 128-channel instance, 1 = 256 when >= 512 workgroups result, 2 (default) = by rounds (below)
+int g_scan_conv_bn256 = 2;  // scan_tune "conv_bn256": 0 keeps every launch on the 128-channel instance, 1 = 256 when >= 512 workgroups result, 2 (default) = by rounds (above)
 // scan_tune "conv_wg1024" (two pieces only): 1 (default) = the 128- and 256-channel 3x3 instances run with 16 waves per
 // workgroup (each wave 32 px x 64 / 128 ch, <= 128 registers, four waves per SIMD) instead of 8 (64 px per wave, two per
 // SIMD); 0 = 8 waves; 2 = 16 waves only for the 256-channel tile on multi-level pyramids.  Same-process A/B per layer
@@ -928,100 +894,72 @@ int g_scan_conv_glds = 1;
 // MFMAs per wave and barrier instead of 48, half the weight-tile traffic per MFMA, halo 1.20 instead of 1.27; 142 KB of LDS,
 // one workgroup per CU as before: conv1_2 3257 -> 2918 us, tools/conv_bench.py).  Same results bit for bit.
 int g_scan_conv_bn64_th16 = 2;
-static int v2_instance(const scan_pyramid_t* od, int32_t Nout) {
+static int channel_tile3x3(const scan_pyramid_t* od, int32_t Nout) {
   if (Nout <= 64) return 64;
-  TileTab2 tt;
-  make_tiles_v2(od, &tt, 16);
-  const int64_t tiles = tt.tile_off[od->n_levels];
-  if (g_scan_conv_bn256 == 1 && Nout % 256 == 0 && tiles * (Nout / 256) >= 512) return 256;  // the rule of rounds 2-4
-  if (g_scan_conv_bn256 == 2 && Nout % 256 == 0) {
-    // rounds of 256 CUs (one workgroup per CU either way; a 256-channel workgroup runs twice as long as a 128-channel one and
-    // reads half the fragments per MFMA): the wider tile whenever it does not cost a round -- conv5_x on 4 frames (128 pixel
-    // tiles x 2: one full round of 256-channel workgroups instead of two of 128-channel ones), conv4_x on the 2 frames of inference
-    const int64_t r256 = (tiles * (Nout / 256) + 255) / 256 * 2, r128 = (tiles * (Nout / 128) + 255) / 256;
-    if (r256 * 97 <= r128 * 100) return 256;  // (the wider tile is ~3 % faster per unit of work: a tie of many rounds goes to it)
-  }
+  if (Nout % 256 != 0) return 128;
+  const int64_t tiles = tiles16(od);
+  if (g_scan_conv_bn256 == 1 && tiles * (Nout / 256) >= 512) return 256;  // the rule of rounds 2-4
+  if (g_scan_conv_bn256 == 2 && wide_tile_costs_no_round(tiles, Nout)) return 256;
   return 128;
 }
 
-// entry points used by the public functions of conv_bf16x3.hip.  np = pieces per operand (2: planes w0, w1; 3: w0, w1, w2)
-int conv3x3_split_launch(int np, const float* x, const scan_pyramid_t* d, int32_t Cs, const void* w0, const void* w1,
-                         const void* w2, int32_t Csw, const float* bias, const float* mask, float* y, int32_t Nout,
-                         int32_t Ns, int32_t relu, void* stream, double* gn_ws) {
-  ConvArgs a{x, d, d, Cs, {reinterpret_cast<const __bf16*>(w0), reinterpret_cast<const __bf16*>(w1),
-                           reinterpret_cast<const __bf16*>(w2)}, Csw, bias, mask, y, Nout, Ns, relu, 0, as_stream(stream), gn_ws};
-  const bool whole = g_scan_conv_glds && Csw % 32 == 0;
+// Ids.  Two pieces: 64 / 128 / 256 = the channel tile, 1128 / 1256 = the 128- / 256-channel tile run by 16-wave (1024-thread)
+// workgroups, 2256 = the 256-channel tile on the 8-wave LDS-DMA instance.  Three pieces (always 8 waves on the wider tiles):
+// 64 / 128 / 256 = the channel tile (64: 8x16-pixel tiles, 4 waves), 1064 = the 64-channel tile on 16x16-pixel tiles with 8
+// waves (single-level pyramids with sizes that are multiples of 16), 2064 = on 32x16-pixel tiles (H a multiple of 32).
+// An id does not say how the weight tiles are staged (GL) nor how many taps share a barrier (TPB): instances that differ only
+// there share the id.  One id covers two tile heights: 2064 without LDS-DMA (conv_glds = 0 or ragged K chunks) runs the 16x16-
+// pixel tile, the only 64-channel 8-wave instance with register staging -- the queries have always reported it so.
+#define INST(...) (&launch_v2<__VA_ARGS__>)  // template arguments of conv_split_kernel
+ConvInst pick3x3(int np, const scan_pyramid_t* d, int32_t Nout, bool whole_chunks) {
+  const int bn = channel_tile3x3(d, Nout);
+  const bool gl = g_scan_conv_glds && whole_chunks;
   const bool th16 = g_scan_conv_bn64_th16 && d->n_levels == 1 && d->h[0] % 16 == 0 && d->w[0] % 16 == 0;
   if (np == 3) {
     // three pieces: every 3x3 instance stages its weight tiles by LDS-DMA when the planes have whole K chunks (register
     // staging of three planes costs the 8-wave instances 24 registers and spills: 95-103 TFLOP/s against 215-246,
     // tools/conv_bench.py --variants conv_glds=0)
-    switch (v2_instance(d, Nout)) {
-      case 64:
-        if (whole && th16 && g_scan_conv_bn64_th16 == 2 && d->h[0] % 32 == 0)
-          launch_v2<3, 64, 32, 512, 3, 1, true>(a);
-        else if (whole && th16)
-          launch_v2<3, 64, 16, 512, 3, 1, true>(a);
-        else if (whole)
-          launch_v2<3, 64, 8, 256, 3, 1, true>(a);
-        else if (th16)
-          launch_v2<3, 64, 16, 512, 3>(a);
-        else
-          launch_v2<3, 64, 8, 256, 3>(a);
-        break;
-      case 256:
-        if (whole)
-          launch_v2<3, 256, 16, 512, 3, 1, true>(a);
-        else
-          launch_v2<3, 256, 16, 512, 3>(a);
-        break;
-      default:
-        if (whole)
-          launch_v2<3, 128, 16, 512, 3, 1, true>(a);
-        else
-          launch_v2<3, 128, 16, 512, 3>(a);
-        break;
-    }
-    SCAN_LAUNCH_CHECK("conv3x3_bf16x6");
-    return 0;
+    if (bn == 256) return {256, gl ? INST(3, 256, 16, 512, 3, 1, true) : INST(3, 256, 16, 512, 3)};
+    if (bn == 128) return {128, gl ? INST(3, 128, 16, 512, 3, 1, true) : INST(3, 128, 16, 512, 3)};
+    if (th16 && g_scan_conv_bn64_th16 == 2 && d->h[0] % 32 == 0)
+      return {2064, gl ? INST(3, 64, 32, 512, 3, 1, true) : INST(3, 64, 16, 512, 3)};
+    if (th16) return {1064, gl ? INST(3, 64, 16, 512, 3, 1, true) : INST(3, 64, 16, 512, 3)};
+    return {64, gl ? INST(3, 64, 8, 256, 3, 1, true) : INST(3, 64, 8, 256, 3)};
   }
-  switch (v2_instance(d, Nout)) {
-    case 64:
-      if (th16)
-        launch_v2<2, 64, 16, 256, 3>(a);
-      else if (g_scan_conv_tpb3 & 2)
-        launch_v2<2, 64, 8, 256, 3, 3>(a);
-      else
-        launch_v2<2, 64, 8, 256, 3>(a);
-      break;
-    case 256:
-      // (two pieces: LDS-DMA only on whole channel tiles, as measured in rounds 2 and 3; v2_instance returns 256 only then)
-      if (g_scan_conv_w8 && g_scan_conv_wg1024 == 1 && whole)
-        launch_v2<2, 256, 16, 512, 3, 1, true>(a);
-      else if ((g_scan_conv_wg1024 == 1 || (g_scan_conv_wg1024 == 2 && d->n_levels > 1)) && whole)
-        launch_v2<2, 256, 16, 1024, 3, 1, true>(a);
-      else if (g_scan_conv_wg1024 == 1 || (g_scan_conv_wg1024 == 2 && d->n_levels > 1))
-        launch_v2<2, 256, 16, 1024, 3>(a);
-      else
-        launch_v2<2, 256, 16, 512, 3>(a);
-      break;
-    default:
-      if (g_scan_conv_wg1024 == 1 && (g_scan_conv_tpb3 & 1) && whole && Nout % 128 == 0)
-        launch_v2<2, 128, 16, 1024, 3, 3, true>(a);
-      else if (g_scan_conv_wg1024 == 1 && (g_scan_conv_tpb3 & 1))
-        launch_v2<2, 128, 16, 1024, 3, 3>(a);
-      else if (g_scan_conv_wg1024 == 1 && whole && Nout % 128 == 0)
-        launch_v2<2, 128, 16, 1024, 3, 1, true>(a);
-      else if (g_scan_conv_wg1024 == 1)
-        launch_v2<2, 128, 16, 1024, 3>(a);
-      else if (g_scan_conv_tpb3 & 1)
-        launch_v2<2, 128, 16, 512, 3, 3>(a);
-      else
-        launch_v2<2, 128, 16, 512, 3>(a);
-      break;
+  const bool tpb3 = g_scan_conv_tpb3 & 1;
+  if (bn == 256) {
+    // (two pieces: LDS-DMA only on whole channel tiles, as measured in rounds 2 and 3; the channel tile is 256 only then)
+    const bool wg16 = g_scan_conv_wg1024 == 1 || (g_scan_conv_wg1024 == 2 && d->n_levels > 1);
+    if (g_scan_conv_w8 && g_scan_conv_wg1024 == 1 && gl) return {2256, INST(2, 256, 16, 512, 3, 1, true)};
+    if (wg16) return {1256, gl ? INST(2, 256, 16, 1024, 3, 1, true) : INST(2, 256, 16, 1024, 3)};
+    return {256, INST(2, 256, 16, 512, 3)};
   }
-  SCAN_LAUNCH_CHECK("conv3x3_bf16x3");
-  return 0;
+  if (bn == 128) {
+    if (g_scan_conv_wg1024 != 1) return {128, tpb3 ? INST(2, 128, 16, 512, 3, 3) : INST(2, 128, 16, 512, 3)};
+    if (gl && Nout % 128 == 0) return {1128, tpb3 ? INST(2, 128, 16, 1024, 3, 3, true) : INST(2, 128, 16, 1024, 3, 1, true)};
+    return {1128, tpb3 ? INST(2, 128, 16, 1024, 3, 3) : INST(2, 128, 16, 1024, 3)};
+  }
+  if (th16) return {64, INST(2, 64, 16, 256, 3)};
+  return {64, (g_scan_conv_tpb3 & 2) ? INST(2, 64, 8, 256, 3, 3) : INST(2, 64, 8, 256, 3)};
+}
+
+// scan_tune "conv1x1" (three pieces): bit 0 = the 1x1 instances stage their weight tiles by LDS-DMA (whole K chunks: Csw % 32 == 0),
+// bit 1 = the 256-channel tile when the channels fill it and it does not cost a round of 256 CUs (the 3x3 rule).  Default 3 (round 6).
+// Same results bit for bit
+// (tools/conv_bench.py --ksize 1 --variants conv1x1=0,conv1x1=1,conv1x1=3, ResNet-50 body + FPN laterals at the K2C bench shape, us):
+// forward 64 -> 256 @256x512 259 -> 217, 128 -> 512 172 -> 146, 256 -> 1024 120 -> 108, 512 -> 2048 111 -> 95, lateral 512 -> 256 225 -> 181;
+// data gradient 256 -> 64 267 -> 213, 512 -> 128 166 -> 136, 1024 -> 256 111 -> 96, 2048 -> 512 98 -> 84, lateral 259 -> 202; Cout <= 128: +- 2 %.
+// 1x1 convs are a sliver of the VGG step (FPN laterals) but a fifth of the ResNet-50 body's (BASELINE.json configs[3]: bottleneck
+// conv1 / conv3 / downsample).
+int g_scan_conv1x1 = 3;
+// ids: 64 / 128 = the register-staged tiles, 1128 / 1256 = the 128- / 256-channel tile with LDS-DMA weights (three pieces only)
+ConvInst pick1x1(int np, const scan_pyramid_t* yd, int32_t Nout, int32_t Csw) {
+  if (np == 2) return Nout <= 64 ? ConvInst{64, INST(2, 64, 8, 256, 1)} : ConvInst{128, INST(2, 128, 16, 512, 1)};
+  if (Nout <= 64) return {64, INST(3, 64, 8, 256, 1)};
+  if (!((g_scan_conv1x1 & 1) && Csw % 32 == 0)) return {128, INST(3, 128, 16, 512, 1)};
+  if ((g_scan_conv1x1 & 2) && Nout % 256 == 0 && wide_tile_costs_no_round(tiles16(yd), Nout))
+    return {1256, INST(3, 256, 16, 512, 1, 1, true)};
+  return {1128, INST(3, 128, 16, 512, 1, 1, true)};
 }
 
 // scan_tune "conv_wino": 1 (default) = three-piece 3x3 launches with more than 64 output channels and whole K chunks run the
@@ -1035,94 +973,10 @@ int g_scan_conv_wino = 1;
 // interval, 13 barriers per chunk (the schedule of rounds 7 and 8).  Same results bit for bit.  Measurements: DESIGN.md
 // section 3.1.
 int g_scan_wino_tpb = 2;
-extern "C" int scan_conv3x3_bf16x6_wino(int32_t Nout, int32_t Csw) { return g_scan_conv_wino && Nout > 64 && Csw % 32 == 0 ? 1 : 0; }
-
-int conv3x3_wino_launch(const float* x, const scan_pyramid_t* d, int32_t Cs, const void* w0, const void* w1, const void* w2,
-                        int32_t Csw, const float* bias, const float* mask, float* y, int32_t Nout, int32_t Ns, int32_t relu,
-                        void* stream, double* gn_ws) {
-  SCAN_CHECK_ARG(Nout > 64 && Csw % 32 == 0, "conv3x3_wino_bf16x6: needs Nout > 64 and Csw %% 32 == 0 (Nout=%d Csw=%d)", Nout, Csw);
-  ConvArgs a{x, d, d, Cs, {reinterpret_cast<const __bf16*>(w0), reinterpret_cast<const __bf16*>(w1),
-                           reinterpret_cast<const __bf16*>(w2)}, Csw, bias, mask, y, Nout, Ns, relu, 0, as_stream(stream), gn_ws};
+void conv3x3_wino_launch(const ConvArgs& a) {
   if (g_scan_wino_tpb == 2)
     launch_v2<3, 128, 16, 512, 3, 2, true, true>(a);
   else
     launch_v2<3, 128, 16, 512, 3, 1, true, true>(a);
-  SCAN_LAUNCH_CHECK("conv3x3_wino_bf16x6");
-  return 0;
 }
-
-// instance of a three-piece 1x1 launch: 64 / 128 = the register-staged tiles, 1128 / 1256 = the 128- / 256-channel tile with LDS-DMA weights
-static int conv1x1_instance3(const scan_pyramid_t* yd, int32_t Nout, int32_t Csw);
-// scan_tune "conv1x1" (three pieces): bit 0 = the 1x1 instances stage their weight tiles by LDS-DMA (whole K chunks), bit 1 = the
-// 256-channel tile when the channels fill it and it does not cost a round of 256 CUs.  Default 3 (round 6).  Same results bit for bit
-// (tools/conv_bench.py --ksize 1 --variants conv1x1=0,conv1x1=1,conv1x1=3, ResNet-50 body + FPN laterals at the K2C bench shape, us):
-// forward 64 -> 256 @256x512 259 -> 217, 128 -> 512 172 -> 146, 256 -> 1024 120 -> 108, 512 -> 2048 111 -> 95, lateral 512 -> 256 225 -> 181;
-// data gradient 256 -> 64 267 -> 213, 512 -> 128 166 -> 136, 1024 -> 256 111 -> 96, 2048 -> 512 98 -> 84, lateral 259 -> 202; Cout <= 128: +- 2 %.
-int g_scan_conv1x1 = 3;
-static int conv1x1_instance3(const scan_pyramid_t* yd, int32_t Nout, int32_t Csw) {
-  if (Nout <= 64) return 64;
-  if (!((g_scan_conv1x1 & 1) && Csw % 32 == 0)) return 128;
-  if ((g_scan_conv1x1 & 2) && Nout % 256 == 0) {
-    TileTab2 tt;
-    make_tiles_v2(yd, &tt, 16);
-    const int64_t tiles = tt.tile_off[yd->n_levels];
-    const int64_t r256 = (tiles * (Nout / 256) + 255) / 256 * 2, r128 = (tiles * (Nout / 128) + 255) / 256;
-    if (r256 * 97 <= r128 * 100) return 1256;
-  }
-  return 1128;
-}
-extern "C" int scan_conv1x1_bf16x6_instance(const scan_pyramid_t* yd, int32_t Nout, int32_t Csw) {
-  return yd ? conv1x1_instance3(yd, Nout, Csw) : -1;
-}
-
-int conv1x1_split_launch(int np, const float* x, const scan_pyramid_t* xd, int32_t Cs, const void* w0, const void* w1,
-                         const void* w2, int32_t Csw, const float* bias, const float* mask, float* y,
-                         const scan_pyramid_t* yd, int32_t Nout, int32_t Ns, int32_t relu, int32_t map, void* stream) {
-  ConvArgs a{x, yd, xd, Cs, {reinterpret_cast<const __bf16*>(w0), reinterpret_cast<const __bf16*>(w1),
-                             reinterpret_cast<const __bf16*>(w2)}, Csw, bias, mask, y, Nout, Ns, relu, map, as_stream(stream), nullptr};
-  // scan_tune "conv1x1": bit 0 = weight tiles by LDS-DMA (whole K chunks: Csw % 32 == 0), bit 1 = the 256-channel tile when the
-  // channels fill it and it does not cost a round of 256 CUs (the 3x3 rule, v2_instance).  1x1 convs are a sliver of the VGG step (FPN
-  // laterals) but a fifth of the ResNet-50 body's (BASELINE.json configs[3]: bottleneck conv1 / conv3 / downsample).
-  const int inst = np == 3 ? conv1x1_instance3(yd, Nout, Csw) : (Nout <= 64 ? 64 : 128);
-  const bool wide = inst == 1256, gl = inst >= 1000;
-  if (np == 3) {
-    if (Nout <= 64)
-      launch_v2<3, 64, 8, 256, 1>(a);
-    else if (wide)
-      launch_v2<3, 256, 16, 512, 1, 1, true>(a);
-    else if (gl)
-      launch_v2<3, 128, 16, 512, 1, 1, true>(a);
-    else
-      launch_v2<3, 128, 16, 512, 1>(a);
-  } else {
-    if (Nout <= 64)
-      launch_v2<2, 64, 8, 256, 1>(a);
-    else
-      launch_v2<2, 128, 16, 512, 1>(a);
-  }
-  SCAN_LAUNCH_CHECK("conv1x1_split");
-  return 0;
-}
-
-// which instance a 3x3 launch on pyramid d with Nout output channels takes (bench.py labels its timings with it):
-// two pieces: 64 / 128 / 256, or 1128 / 1256 for the 128- / 256-channel tile run by 16-wave (1024-thread) workgroups, 2256
-// for the 256-channel tile on the 8-wave LDS-DMA instance (Csw % 32 == 0 assumed: true for every 3x3 plane ops.py splits)
-extern "C" int scan_conv3x3_bf16x3_instance(const scan_pyramid_t* d, int32_t Nout) {
-  if (!d) return -1;
-  const int bn = v2_instance(d, Nout);
-  if (bn == 256 && g_scan_conv_w8 && g_scan_conv_wg1024 == 1 && g_scan_conv_glds) return 2256;
-  if (bn == 256 && (g_scan_conv_wg1024 == 1 || (g_scan_conv_wg1024 == 2 && d->n_levels > 1))) return 1256;
-  if (bn == 128 && g_scan_conv_wg1024 == 1) return 1128;
-  return bn;
-}
-
-// three pieces: the output-channel tile (64 / 128 / 256; 8 waves, LDS-DMA weight tiles), 1064 = the 64-channel tile on
-// 16x16-pixel tiles with 8 waves (single-level pyramids with sizes that are multiples of 16), 2064 = on 32x16-pixel tiles
-// (H a multiple of 32), 64 = on 8x16-pixel tiles, 4 waves
-extern "C" int scan_conv3x3_bf16x6_instance(const scan_pyramid_t* d, int32_t Nout) {
-  if (!d) return -1;
-  const int bn = v2_instance(d, Nout);
-  if (bn == 64 && g_scan_conv_bn64_th16 && d->n_levels == 1 && d->h[0] % 16 == 0 && d->w[0] % 16 == 0)
-    return (g_scan_conv_bn64_th16 == 2 && d->h[0] % 32 == 0) ? 2064 : 1064;  // (Csw % 32 == 0 assumed, as for the others)
-  return bn;
-}
+#undef INST

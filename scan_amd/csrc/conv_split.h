@@ -83,3 +83,25 @@ __device__ __forceinline__ int xcd_remap(int orig, int nwg) {
 }
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
+
+// Pixel tiles of a forward / data-gradient launch: every kernel generation cuts each level of each image into tiles of
+// TH x CONV_TILE_W pixels and enumerates them level by level (tile_off), images inside a level, rows of tiles inside an image.
+#define CONV_TILE_W 16
+struct TileTab2 {
+  int tile_off[SCAN_MAX_LEVELS + 1];
+  int tiles_x[SCAN_MAX_LEVELS];
+  int tiles_y[SCAN_MAX_LEVELS];
+};
+static inline void make_tiles(const scan_pyramid_t* d, TileTab2* tt, int TH) {
+  tt->tile_off[0] = 0;
+  for (int l = 0; l < SCAN_MAX_LEVELS; ++l) {
+    if (l < d->n_levels) {
+      tt->tiles_x[l] = (d->w[l] + CONV_TILE_W - 1) / CONV_TILE_W;
+      tt->tiles_y[l] = (d->h[l] + TH - 1) / TH;
+      tt->tile_off[l + 1] = tt->tile_off[l] + d->n_images * tt->tiles_x[l] * tt->tiles_y[l];
+    } else {
+      tt->tiles_x[l] = tt->tiles_y[l] = 1;
+      tt->tile_off[l + 1] = tt->tile_off[l];
+    }
+  }
+}

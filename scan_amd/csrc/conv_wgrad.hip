@@ -21,6 +21,7 @@
 //                          and is the independent cross-check of the other kernel (bit-identical slabs for NP = 2).
 //   conv_wgrad_v6_kernel   producer / consumer wave specialisation, two LDS stages (288-byte rows), one barrier per chunk.
 //                          Every 3x3 launch.
+#include "conv_launch.h"
 #include "conv_split.h"
 #include <type_traits>
 
@@ -556,16 +557,8 @@ __device__ __forceinline__ void wgrad_mma_v6_pipe(const W6Lane& w, f32x4v (&acc)
 // waves, 2 x 4 -> 4 (o) x 2 (c) waves).  Either way 96 accumulator registers; the resident dY fragments are NP * TOM * 4
 // registers, the X fragments are re-read per tap: 4 x 2 reads fewer fragments per MFMA (30 transposed reads per 144
 // MFMAs with three pieces), 2 x 4 keeps 24 instead of 48 registers resident (42 reads) and leaves room to prefetch.
-#if defined(SCAN_EXP_WGRAD_C256) && SCAN_EXP_WGRAD_C256 == 1
-// TIMING EXPERIMENT (make exp_wgrad_c256 M=1|2, WRONG results): the consumers alone on two LDS stages they fill once --
-// 1: eight waves with 256 registers, temporary accumulator + pipelined loop on either wave tile; 2: the shipped loops beside
-// four idle producer waves (168 registers)
-#define W6_BOUNDS __launch_bounds__(512, 2)
-#define W6_THREADS 512
-#else
 #define W6_BOUNDS __launch_bounds__(768, 3)
 #define W6_THREADS 768
-#endif
 //
 // WINO (three pieces, 3x3): F(2,3) applied ACROSS ROWS.  The K walk runs over row PAIRS (y0, y0 + 1), y0 even, of one image
 // of one level, and the workgroup owns one Winograd component j where the direct form owns one ky.  With e0, e1 = dY rows
@@ -733,11 +726,7 @@ __global__ W6_BOUNDS void conv_wgrad_v6_kernel(
           va.z = __builtin_fmaf(s_q, ra2[i].z, sa_p * ra[i].z);
           va.w = __builtin_fmaf(s_q, ra2[i].w, sa_p * ra[i].w);
         }
-#ifdef SCAN_EXP_WGRAD_NOSPLIT  // TIMING EXPERIMENT (make exp_wgrad_nosplit, never in libscan_hip.so): no conversion work
-        for (int p = 0; p < NP; ++p) pc[p] = __builtin_bit_cast(bf16x4, make_float2(va.x, va.y));
-#else
         split4_np<NP>(va, pc);
-#endif
 #pragma unroll
         for (int p = 0; p < NP; ++p) *reinterpret_cast<bf16x4*>(As + p * WKC * W6ROW + off) = pc[p];
         if (do_bias) {
@@ -769,11 +758,7 @@ __global__ W6_BOUNDS void conv_wgrad_v6_kernel(
             vb.z = __builtin_fmaf(s_q, rb2[i].z, rb[i].z);
             vb.w = __builtin_fmaf(s_q, rb2[i].w, rb[i].w);
           }
-#ifdef SCAN_EXP_WGRAD_NOSPLIT
-          for (int p = 0; p < NP; ++p) pc[p] = __builtin_bit_cast(bf16x4, make_float2(vb.x, vb.y));
-#else
           split4_np<NP>(vb, pc);
-#endif
 #pragma unroll
           for (int p = 0; p < NP; ++p) *reinterpret_cast<bf16x4*>(Bs + p * (WKC + KX - 1) * W6ROW + off) = pc[p];
         }
@@ -795,29 +780,6 @@ __global__ W6_BOUNDS void conv_wgrad_v6_kernel(
     load_b();
     __syncthreads();  // stage 0 is complete
     for (int k = 0; k < nch; ++k) {
-#if defined(SCAN_EXP_WGRAD_PROD)
-      // TIMING EXPERIMENT (make exp_wgrad_prod_<mask>, WRONG results): which part of the producers' work costs the consumers
-      // their issue slots -- bit 0: the loads, bit 1: the LDS writes (of unconverted bits unless the split is compiled in),
-      // bit 3: the chunk walk and descriptors
-      const int stage = (k + 1) & 1;
-      const bool more = k + 2 < nch;
-      auto keep_a = [&]() {
-#pragma unroll
-        for (int i = 0; i < NA; ++i) asm volatile("" ::"v"(ra[i].x), "v"(ra[i].y), "v"(ra[i].z), "v"(ra[i].w));
-      };
-      auto keep_b = [&]() {
-#pragma unroll
-        for (int i = 0; i < NB; ++i) asm volatile("" ::"v"(rb[i].x), "v"(rb[i].y), "v"(rb[i].z), "v"(rb[i].w));
-      };
-      if (SCAN_EXP_WGRAD_PROD & 8) {
-        if (more) advance();
-        prepare(more);
-      }
-      if (SCAN_EXP_WGRAD_PROD & 2) store_a(stage); else keep_a();
-      if (SCAN_EXP_WGRAD_PROD & 1) load_a();
-      if (SCAN_EXP_WGRAD_PROD & 2) store_b(stage); else keep_b();
-      if (SCAN_EXP_WGRAD_PROD & 1) load_b();
-#elif !defined(SCAN_EXP_WGRAD_NOPROD) && !defined(SCAN_EXP_WGRAD_C256)  // TIMING EXPERIMENT (make exp_wgrad_noprod): the producers only attend the barriers
       const int stage = (k + 1) & 1;  // chunk k + 1 is in the registers; chunk k + 2 follows it
       const bool more = k + 2 < nch;
       if (more) advance();
@@ -826,7 +788,6 @@ __global__ W6_BOUNDS void conv_wgrad_v6_kernel(
       load_a();
       store_b(stage);
       load_b();
-#endif
       __syncthreads();  // the consumers are done with stage k & 1; stage (k + 1) & 1 is complete
     }
     if (do_bias) {  // column sums of this split's dY rows: reduce the 8 pixel-row groups through LDS
@@ -861,18 +822,6 @@ __global__ W6_BOUNDS void conv_wgrad_v6_kernel(
 #pragma unroll
       for (int b = 0; b < TOMAX; ++b) acc[a][c][b] = f32x4v{0.f, 0.f, 0.f, 0.f};
 
-#ifdef SCAN_EXP_WGRAD_C256
-  {  // both stages filled once with bf16 values of the operands' magnitude
-    const long long nx = (long long)ct.chunk_off[d.n_levels] * 16 * Cs;
-    for (int i = tid; i < STAGE; i += 512) {
-      const float2 v = *reinterpret_cast<const float2*>(x + (((long long)i + (long long)blockIdx.x * STAGE) % (nx / 2)) * 2);
-      bf16x2 h;
-      h[0] = (__bf16)v.x;
-      h[1] = (__bf16)v.y;
-      *reinterpret_cast<bf16x2*>(sm + 2 * i) = h;
-    }
-  }
-#endif
   __syncthreads();  // stage 0 is complete
   // one K loop per live-tile count (wave-uniform; dead tiles: third c tile of Cin = 264 / 268, Cout = 8 / 5 / 1 heads):
   // inside one loop the compiler would keep the fragment addresses of all variants in registers across it, which at 168
@@ -886,11 +835,7 @@ __global__ W6_BOUNDS void conv_wgrad_v6_kernel(
     unsigned flip = 2u * STAGE;  // bytes; +-: unsigned wrap-around is the subtraction
     for (int k = 0; k < nch; ++k) {
       if constexpr (TO > 0) {
-#if defined(SCAN_EXP_WGRAD_C256) && SCAN_EXP_WGRAD_C256 == 1
-        if constexpr (NP == 3)
-#else
         if constexpr (SCAN_WG_PIPE && SCAN_WG_TCHAIN && NP == 3 && TOM == 2)
-#endif
           wgrad_mma_v6_pipe<NP, WKC, TO, TC, KX, TOMAX, TCMAX>(wl, acc);
         else
           wgrad_mma_v6<NP, WKC, TO, TC, KX, TOMAX, TCMAX, SCAN_WG_TCHAIN && NP == 3 && TOM == 2>(wl, acc);

@@ -45,7 +45,7 @@ typedef __bf16 db_bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 db_bf16x4 __attribute__((ext_vector_type(4)));
 #define DB_LDH 40  // bf16 row pitch of the split planes: 32 + 8, rows stay 16-byte aligned
 
-// hi = bf16(x), lo = bf16(x - hi): the split of the convolution kernels (conv_bf16x3_v2.hip)
+// hi = bf16(x), lo = bf16(x - hi): the split of the convolution kernels (conv_split.h)
 __device__ __forceinline__ void db_split4(const float4 v, db_bf16x4& hi, db_bf16x4& lo) {
   hi[0] = (__bf16)v.x; hi[1] = (__bf16)v.y; hi[2] = (__bf16)v.z; hi[3] = (__bf16)v.w;
   lo[0] = (__bf16)(v.x - (float)hi[0]); lo[1] = (__bf16)(v.y - (float)hi[1]);

@@ -551,3 +551,61 @@ def test_surface_adopt_and_flatten_order():
                 for x in range(w):
                     r = shape.row_off[l] + (i * h + y) * w + x
                     assert torch.equal(rows[r], levels[l][i, :, y, x])
+
+
+# the launch knobs the conv instance queries depend on, with the values swept (itertools.product order = order of "index" in the file)
+_INSTANCE_KNOBS = [("conv_bn256", (0, 1, 2)), ("conv_wg1024", (0, 1, 2)), ("conv_w8", (0, 1)), ("conv_glds", (0, 1)),
+                   ("conv_bn64_th16", (0, 1, 2)), ("conv1x1", (0, 1, 2, 3)), ("conv_wino", (0, 1))]
+_INSTANCE_NOUT = (32, 64, 96, 128, 256, 264, 512)
+_INSTANCE_CSW = (64, 72)
+# (images, level sizes): one small level, conv1_2-like, sizes that are no multiple of 32, a large level, two five-level pyramids
+_INSTANCE_PYRAMIDS = [(1, [(16, 16)]), (4, [(32, 64)]), (2, [(48, 80)]), (4, [(128, 256)]),
+                      (2, [(32, 64), (16, 32), (8, 16), (4, 8), (2, 4)]), (2, [(100, 168), (50, 84), (25, 42), (13, 21), (7, 11)])]
+
+
+def _sweep_conv_instance_queries():
+    """{query: {"rows": distinct result rows, "index": row of each knob setting}} over the grid above; a row lists the results for
+    every (Nout[, Csw], pyramid) in that nesting order.  Every knob is put back afterwards."""
+    import itertools
+    L = _lib.lib()
+    pyr = [ops.PyramidShape(n, sizes) for n, sizes in _INSTANCE_PYRAMIDS]
+    queries = {
+        "scan_conv3x3_bf16x3_instance": lambda: [L.scan_conv3x3_bf16x3_instance(p.ref(), n) for n in _INSTANCE_NOUT for p in pyr],
+        "scan_conv3x3_bf16x6_instance": lambda: [L.scan_conv3x3_bf16x6_instance(p.ref(), n) for n in _INSTANCE_NOUT for p in pyr],
+        "scan_conv1x1_bf16x6_instance": lambda: [L.scan_conv1x1_bf16x6_instance(p.ref(), n, c) for n in _INSTANCE_NOUT
+                                                 for c in _INSTANCE_CSW for p in pyr],
+        "scan_conv3x3_bf16x6_wino": lambda: [L.scan_conv3x3_bf16x6_wino(n, c) for n in _INSTANCE_NOUT for c in _INSTANCE_CSW],
+    }
+    out = {q: {"rows": [], "index": []} for q in queries}
+    saved = {k: L.scan_tune_get(k.encode()) for k, _ in _INSTANCE_KNOBS}
+    try:
+        for values in itertools.product(*(v for _, v in _INSTANCE_KNOBS)):
+            for (k, _), v in zip(_INSTANCE_KNOBS, values):
+                L.scan_tune(k.encode(), v)
+            for q, fn in queries.items():
+                row = fn()
+                if row not in out[q]["rows"]:
+                    out[q]["rows"].append(row)
+                out[q]["index"].append(out[q]["rows"].index(row))
+    finally:
+        for k, v in saved.items():
+            L.scan_tune(k.encode(), v)
+    assert {k: L.scan_tune_get(k.encode()) for k in saved} == saved
+    return out
+
+
+def test_conv_instance_queries_match_recorded(gold_dir):
+    """The instance ids the four conv query functions report (bench.py labels its roofline lines with them, ops.py chooses the
+    Winograd weight planes by one) over every setting of the launch knobs they read: equal to the values recorded from the build
+    before the launch code and the queries were put on one picker.  Host-only: no device is touched."""
+    gold = json.load(open(os.path.join(gold_dir, "conv_instances.json")))
+    grid = gold["grid"]
+    assert grid["knobs"] == [[k, list(v)] for k, v in _INSTANCE_KNOBS]
+    assert grid["nout"] == list(_INSTANCE_NOUT) and grid["csw"] == list(_INSTANCE_CSW)
+    assert grid["pyramids"] == [[n, [list(s) for s in sizes]] for n, sizes in _INSTANCE_PYRAMIDS]
+    got = _sweep_conv_instance_queries()
+    assert set(got) == set(gold["queries"])
+    for q, g in gold["queries"].items():
+        assert len(got[q]["index"]) == len(g["index"]) == 864
+        for i, (a, b) in enumerate(zip(got[q]["index"], g["index"])):
+            assert got[q]["rows"][a] == g["rows"][b], (q, "knob setting %d" % i)

@@ -384,7 +384,7 @@ CONV_CASES = [
 @pytest.fixture
 def conv_generation(request):
     """1 = the production kernels; 0 = the independent implementations kept as cross-checks: scan_tune("conv_v2", 0) sends
-    the two-piece forward / data gradient to the 32x32x16 kernel of csrc/conv_bf16x3.hip, scan_tune("wgrad_v6", 0) the 3x3
+    the two-piece forward / data gradient to the 32x32x16 kernel of csrc/conv_gen1.hip, scan_tune("wgrad_v6", 0) the 3x3
     weight gradient (two and three pieces) to conv_wgrad_v4_kernel."""
     from scan_amd import _lib
     old = _lib.query("scan_tune", b"conv_v2", int(request.param))

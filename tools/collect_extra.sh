@@ -47,12 +47,11 @@ timeout 300 python3 tools/layer_times.py 2>&1 | grep -v amdgpu.ids > $O/${TAG}_l
 } > $O/${TAG}_wgrad_error.txt
 {
   echo "# weight-gradient timing experiments (tools/conv_bench.py --op wgrad, bf16x6): shipped library, then the exp_* builds"
-  for L in "" scan_amd/libscan_hip_exp_notchain.so scan_amd/libscan_hip_exp_tg1.so scan_amd/libscan_hip_exp_nosplit.so; do
+  for L in "" scan_amd/libscan_hip_exp_notchain.so scan_amd/libscan_hip_exp_tg1.so; do
     [ -z "$L" ] || [ -f "$L" ] || continue
     echo "## library: ${L:-scan_amd/libscan_hip.so}"
     SCAN_HIP_LIB=$L timeout 250 python3 tools/conv_bench.py --op wgrad --shapes conv3,conv4,towers,dis --variants wgrad_tile=1,wgrad_tile=0 2>&1 | grep -v "amdgpu.ids"
   done
-  echo "# exp_wgrad_nosplit: the producers store raw bits instead of converting (WRONG results): what the fp32 -> 3 x bf16 split costs"
   echo "# exp_wgrad_notchain: no temporary accumulator;  exp_wgrad_tg1: temporary over one column tile per block (150 registers, no scratch)"
 } > $O/${TAG}_wgrad_exp.txt
 ls -la $O/${TAG}_*.txt
