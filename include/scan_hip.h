@@ -648,6 +648,28 @@ int64_t scan_cond_rnn_ws_floats(void);
 int scan_cond_rnn_backward(const float* x, int32_t K, int32_t T, const float* const* weights, const float* h0,
                            const float* h1, const float* dkernels, float* const* grads, float* ws, void* stream);
 
+/* ---- per-level NCHW tensors <-> the pyramid row matrix, all levels in one launch ----
+ * One level of a feature pyramid as a caller outside this library holds it: the logical [N, C, h, w] fp32 tensor at `data`
+ * with its four ELEMENT strides (NCHW-contiguous: sn = C h w, sc = h w, sy = w, sx = 1; channels_last: sn = h w C, sc = 1,
+ * sy = w C, sx = C; any other non-negative strides, e.g. a channel slice of either, work too). */
+#define SCAN_PACK_MAX_LEVELS 8
+typedef struct {
+  const float* data;
+  int32_t h, w;
+  int64_t sn, sc, sy, sx;
+} scan_level_t;
+/* replaces the flatten-and-concatenate in front of every loss (rpn/fcos/loss.py:191-202: permute(0, 2, 3, 1).reshape(-1, C)
+ * per level, then torch.cat over the levels): rows [M, Cs] (M = N * sum_l h_l w_l, Cs >= C, Cs % 4 == 0), row order level ->
+ * image -> y -> x, columns C..Cs-1 written as zeros; every element of rows is written exactly once, so it may be
+ * uninitialised.  levels: HOST array of n_levels <= SCAN_PACK_MAX_LEVELS descriptors (copied into the kernel arguments). */
+int scan_pyramid_pack(const scan_level_t* levels, int32_t n_levels, int32_t n_images, int32_t C, float* rows, int32_t Cs,
+                      void* stream);
+/* the exact inverse, and the adjoint (the gradient of the flatten-and-concatenate of rpn/fcos/loss.py:191-202 w.r.t. the
+ * level tensors): columns 0..C-1 of every row go to element (n, c, y, x) of its level tensor (levels[l].data is WRITTEN here;
+ * every element of the level tensors once), padding columns are ignored. */
+int scan_pyramid_unpack(const float* rows, int32_t Cs, const scan_level_t* levels, int32_t n_levels, int32_t n_images,
+                        int32_t C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,12 @@ class CkaBranch(ctypes.Structure):
     _fields_ = [("w0", c_vp), ("b0", c_vp), ("w2", c_vp), ("b2", c_vp)]
 
 
+class LevelDesc(ctypes.Structure):
+    """scan_level_t"""
+    _fields_ = [("data", c_vp), ("h", c_i32), ("w", c_i32), ("sn", c_i64), ("sc", c_i64), ("sy", c_i64), ("sx", c_i64)]
+
+
+PACK_MAX_LEVELS = 8  # SCAN_PACK_MAX_LEVELS
 SGD_MAX_SEGMENTS = 32
 CKA_MAX_CLASSES = 16
 SPLIT_JOB_WORDS = 11
@@ -187,6 +193,8 @@ SIGNATURES = {
                                                                c_vp, c_vp, c_i32, c_vp, c_vp]),
     "scan_normalize_image_u8": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_f32),
                                                ctypes.POINTER(c_f32), c_vp, c_i32, c_i32, c_i32, c_vp]),
+    "scan_pyramid_pack": (ctypes.c_int, [ctypes.POINTER(LevelDesc), c_i32, c_i32, c_i32, c_vp, c_i32, c_vp]),
+    "scan_pyramid_unpack": (ctypes.c_int, [c_vp, c_i32, ctypes.POINTER(LevelDesc), c_i32, c_i32, c_i32, c_vp]),
 }
 
 _lib = None

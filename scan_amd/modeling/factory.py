@@ -1,0 +1,229 @@
+"""The reference's module factories and call signatures on the pyramid path.
+
+A reference training script builds its sub-models with ``build_backbone(cfg)`` (modeling/backbone/backbone.py:21-44),
+``build_rpn(cfg, in_channels)`` / ``build_middle_head(cfg, in_channels)`` (modeling/rpn/rpn.py:201-218) and one
+``FCOSDiscriminator_con`` per level (tools/train_net_da.py:223-274), and drives them through ``foward_detector``
+(engine/trainer.py:20-72): NCHW level lists between the modules, ``list[BoxList]`` targets in, ``list[BoxList]`` detections
+out.  The builders here take the same yacs-shaped cfg (``config.load(...)``) and return modules with those signatures --
+
+    backbone(images_tensor)                                                      -> features
+    middle_head(images, features, targets, return_maps, mode, forward_target)    -> (features, loss_graph, act_loss, act_maps)
+    fcos(images, features, targets, return_maps, act_maps)                       -> (proposals, losses, score_maps)
+    dis(feature, target, act_maps, domain)                                       -> loss
+
+-- that are thin subclasses of the engine's modules: same parameters, same ``state_dict`` keys (checkpoints and
+``engine.load_state_dicts`` work on them), only ``forward`` differs.  Every level list they return is an ``ops.PyramidLevels``:
+channels_last NCHW views of ONE [M, C] row matrix.  A module that is handed such a list back takes the matrix itself
+(``ops.pack_levels``: no copy, no launch) and runs the engine's one-launch-per-layer implementation on it; a level list from
+anywhere else (a foreign backbone, any layout) is packed into a row matrix by one launch of csrc/pyramid_pack.hip, whose
+backward returns the gradient in the caller's layout.  Unlike ``scan_amd.surface`` nothing here runs once per level.
+"""
+import torch
+
+from .. import config, ops
+from ..structures import BoxList, to_image_list
+from . import fcos as fcos_mod
+from .backbone import VGG16FPN
+from .condgraph import GRAPHModule
+from .discriminator import FCOSDiscriminator_con
+from .fcos import FCOSModule
+from .resnet import ResNetFPNBackbone
+
+LEVELS = ("P3", "P4", "P5", "P6", "P7")
+DIS_ORDER = ("P7", "P6", "P5", "P4", "P3")  # order the reference builds them in (tools/train_net_da.py:223-274)
+CONV_BODIES = ("VGG-16-FPN-RETINANET", "R-50-FPN-RETINANET", "R-101-FPN-RETINANET")
+
+
+def _channels_last_(module):
+    """4-D parameters stored channels_last, as engine.build_model leaves them (the kernels read [Cout][k*k][Cin] in place)"""
+    for p in module.parameters():
+        if p.dim() == 4:
+            p.data = p.data.contiguous(memory_format=torch.channels_last)
+    return module
+
+
+_targets_seen = [None, None]
+
+
+def target_tuples(targets):
+    """list[BoxList] (boxes read in xyxy, labels from the "labels" field) -> the (boxes, labels) tuples the ground-truth plan
+    consumes; tuples pass through.  The same list object maps to the same result object, so the middle head and the FCOS head of
+    one iteration share one plan (modeling/fcos.py: target_plan is keyed by the list's identity)."""
+    if not targets or not isinstance(targets[0], BoxList):
+        return targets
+    if _targets_seen[0] is targets:
+        return _targets_seen[1]
+    out = [(t.convert("xyxy").bbox, t.get_field("labels")) for t in targets]
+    _targets_seen[:] = [targets, out]
+    return out
+
+
+def _rows_exact(levels, c=None):
+    """(rows [M, c] contiguous, PyramidShape) of a level list: its own matrix when it is an intact PyramidLevels, one pack launch
+    otherwise (padding columns, present when c is no multiple of 4, are dropped again)"""
+    rows, shape = ops.pack_levels(levels)
+    c = levels[0].shape[1] if c is None else c
+    if rows.shape[1] != c:
+        rows = rows[:, :c].contiguous()
+    return rows, shape
+
+
+class _BackboneForward:
+    def forward(self, images, rows=None, shape=None):
+        """images [N, 3, H, W] (or an ImageList) -> PyramidLevels of P3..P7"""
+        if hasattr(images, "tensors"):
+            images = images.tensors
+        return ops.PyramidLevels(*super().forward(images, rows, shape))
+
+
+class VGG16FPNBackbone(_BackboneForward, VGG16FPN):
+    pass
+
+
+class ResNetFPNRetinaBackbone(_BackboneForward, ResNetFPNBackbone):
+    pass
+
+
+def build_backbone(cfg):
+    """reference modeling/backbone/backbone.py:21-44,76-80: the registry entry MODEL.BACKBONE.CONV_BODY names."""
+    body = str(cfg.MODEL.BACKBONE.CONV_BODY)
+    if body == "VGG-16-FPN-RETINANET":
+        m = VGG16FPNBackbone()
+    elif body in ("R-50-FPN-RETINANET", "R-101-FPN-RETINANET"):
+        m = ResNetFPNRetinaBackbone(body[:-len("-FPN-RETINANET")], int(cfg.MODEL.BACKBONE.FREEZE_CONV_BODY_AT))
+    else:
+        raise ValueError("MODEL.BACKBONE.CONV_BODY %r is not built (one of %s)" % (body, ", ".join(CONV_BODIES)))
+    return _channels_last_(m)
+
+
+class GRAPHModuleNCHW(GRAPHModule):
+    """GRAPHModule.forward of the reference (rpn/fcos/condgraph.py:547-556)."""
+
+    def forward(self, images, features, targets=None, return_maps=False, mode="source", forward_target=False):
+        """-> (features, (node_loss, consistency_loss) | None, act_loss | None, act_maps); both lists are PyramidLevels.  The act
+        maps are returned whatever ``return_maps`` says, like the reference's three branches do (:445, :527, :545)."""
+        rows, shape = ops.pack_levels(features)
+        targets = target_tuples(targets)
+        if self.training and targets and mode == "source" and rows.is_cuda:
+            # the ground-truth plan on the side stream engine.forward_detector builds it on: its host round trip then waits for
+            # three small kernels, not for the backbone convolutions queued in front of this call
+            after = None
+            if any(b.is_cuda or l.is_cuda for b, l in targets):
+                after = torch.cuda.Event()
+                after.record(torch.cuda.current_stream())
+            fcos_mod.target_plan(shape, targets, rows.device, side_stream=ops.borrow_side_streams(3)[0], after=after)
+        out, loss_graph, act_loss, maps = super().forward(rows, shape, targets=targets, mode=mode, forward_target=forward_target)
+        return ops.PyramidLevels(out, shape), loss_graph, act_loss, ops.PyramidLevels(maps, shape)
+
+
+def build_middle_head(cfg, in_channels):
+    """reference modeling/rpn/rpn.py:215-218."""
+    if not cfg.MODEL.MIDDLE_HEAD.CONDGRAPH_ON:
+        raise ValueError("MODEL.MIDDLE_HEAD.CONDGRAPH_ON is False: no other middle head is built")
+    s = config.settings(cfg)
+    if s["num_convs_in"] != 2 or s["num_convs_out"] != 1:
+        raise ValueError("MODEL.MIDDLE_HEAD.NUM_CONVS_IN/OUT other than 2/1 are not built")
+    # the same construction as condgraph.build_condgraph(settings, in_channels) (rpn/fcos/condgraph.py:127-253)
+    m = GRAPHModuleNCHW(in_channels, s["num_classes"], proto_iter=s["proto_iter"], transfer_cfg=s["transfer_cfg"],
+                        dbscan_eps=s["dbscan_eps"], dbscan_thr=s["dbscan_thr"])
+    m.lamda1, m.lamda2 = s["gcn_loss_weight"], s["act_loss_weight"]
+    m.lamda3, m.lamda4 = s["con_loss_weight"], s["gcn_loss_weight_tg"]
+    return _channels_last_(m)
+
+
+class FCOSModuleNCHW(FCOSModule):
+    """FCOSModule.forward of the reference (rpn/fcos/fcos.py:144-232)."""
+
+    def forward(self, images, features, targets=None, return_maps=False, act_maps=None):
+        """training: (None, losses, score_maps | None) -- score_maps = {"box_cls", "box_regression", "centerness"} as
+        PyramidLevels when ``return_maps``; without targets the loss dict is the reference's {"zero": 0} (:215-220) and the head
+        only runs when its maps are asked for.  eval: (list[BoxList] with fields "scores" and "labels", clipped to
+        images.image_sizes, {}, None)."""
+        il = to_image_list(images)
+        rows, shape = ops.pack_levels(features)
+        targets = target_tuples(targets)
+        if not self.training:
+            maps = _rows_exact(act_maps)[0] if act_maps is not None else None
+            dets, _ = super().forward(il.image_sizes, rows, shape, act_maps=maps)
+            boxlists = []
+            for (boxes, scores, labels), (h, w) in zip(dets, il.image_sizes):
+                b = BoxList(boxes, (int(w), int(h)), mode="xyxy")
+                b.add_field("scores", scores)
+                b.add_field("labels", labels)
+                boxlists.append(b)
+            return boxlists, {}, None
+        if not return_maps:
+            return super().forward(il.image_sizes, rows, shape, targets=targets) + (None,)
+        logits, reg, ctr = self.head(rows, shape)
+        if targets is None:
+            losses = {"zero": rows.new_zeros(())}
+        else:
+            lc, lr, lctr = self.loss_evaluator(shape, logits, reg, ctr, targets)
+            losses = {"loss_cls": lc, "loss_reg": lr, "loss_centerness": lctr}
+        score_maps = {"box_cls": ops.PyramidLevels(logits, shape), "box_regression": ops.PyramidLevels(reg, shape),
+                      "centerness": ops.PyramidLevels(ctr[:, None], shape)}
+        return None, losses, score_maps
+
+
+def build_rpn(cfg, in_channels):
+    """reference modeling/rpn/rpn.py:201-212."""
+    if not cfg.MODEL.get("FCOS_ON", False):
+        raise ValueError("MODEL.FCOS_ON is False: only the FCOS head is built (no RPN / RetinaNet / ATSS)")
+    if in_channels != 256:
+        raise ValueError("the FCOS head is built for 256 input channels, got %d" % in_channels)
+    s = config.settings(cfg)
+    return _channels_last_(FCOSModuleNCHW(s["num_classes"], s["test_mode"], s))
+
+
+class FCOSDiscriminatorNCHW(FCOSDiscriminator_con):
+    """FCOSDiscriminator_con.forward of the reference (discriminator/fcos_head_discriminator_con.py:92-126) on ONE level."""
+
+    def forward(self, feature, target, act_maps=None, domain="source", shape=None):
+        """feature [N, 256, h, w], act_maps [N, K, h, w].  Level views of a PyramidLevels are taken as the rows they are (no
+        copy); anything else goes through the pack kernel."""
+        if shape is not None:  # the engine's own call: rows of one level
+            return super().forward(feature, target, act_maps, domain=domain, shape=shape)
+        frows, shape = _level_rows(feature)
+        arows, _ = _level_rows(act_maps)
+        return super().forward(frows, target, arows, domain=domain, shape=shape)
+
+
+# the name a reference script constructs its discriminators by (tools/train_net_da.py:223-274): same keyword arguments
+FCOSDiscriminator_con = FCOSDiscriminatorNCHW
+
+
+def _level_rows(t):
+    """one [N, C, h, w] level -> ([N*h*w, C] rows, its PyramidShape): a view when the level is dense channels_last"""
+    n, c, h, w = t.shape
+    nhwc = t.permute(0, 2, 3, 1)
+    if nhwc.is_contiguous():
+        return nhwc.view(n * h * w, c), ops.PyramidShape(n, [(h, w)])
+    return _rows_exact([t], c)
+
+
+def build_discriminators(cfg):
+    """{"dis_P7_CON": ..., ..., "dis_P3_CON": ...} for the levels MODEL.ADV.USE_DIS_<level>_CON switches on, with the level's
+    CON_NUM_SHARED_CONV_<level> tower convs and GRL_WEIGHT_<level> (reference tools/train_net_da.py:223-274)."""
+    A = cfg.MODEL.ADV
+    if not A.USE_DIS_CON:
+        return {}
+    s = config.settings(cfg)
+    out = {}
+    for lvl in DIS_ORDER:
+        if A["USE_DIS_%s_CON" % lvl]:
+            out["dis_%s_CON" % lvl] = _channels_last_(FCOSDiscriminatorNCHW(
+                with_GA=bool(A.CON_WITH_GA), fusion_cfg=str(A.CON_FUSUIN_CFG), num_convs=s["dis_num_convs"][lvl],
+                in_channels=256, num_classes=s["num_classes"], grad_reverse_lambda=s["grl_weight"][lvl],
+                grl_applied_domain=str(A.GRL_APPLIED_DOMAIN), patch_stride=A.PATCH_STRIDE))
+    return out
+
+
+def build_model(cfg, device="cuda"):
+    """the reference's MODEL dict (tools/train_net_da.py:43-48,223-274) out of the factories above, moved to ``device``"""
+    backbone = build_backbone(cfg)
+    model = {"backbone": backbone, "middle_head": build_middle_head(cfg, backbone.out_channels),
+             "fcos": build_rpn(cfg, backbone.out_channels)}
+    model.update(build_discriminators(cfg))
+    for m in model.values():
+        m.to(device)
+    return model

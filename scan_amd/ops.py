@@ -778,6 +778,130 @@ def take_images(rows, shape, i0, i1):
     return _TakeImages.apply(rows, shape, i0, i1), PyramidShape(i1 - i0, shape.sizes)
 
 
+# ----------------------------------------------------------------------------- per-level NCHW lists <-> pyramid rows
+def _level_descs(levels):
+    """the scan_level_t array of a list of [N, C, h, w] tensors (element strides as torch reports them)"""
+    arr = (_lib.LevelDesc * len(levels))()
+    for d, t in zip(arr, levels):
+        d.data, d.h, d.w = t.data_ptr(), t.shape[2], t.shape[3]
+        d.sn, d.sc, d.sy, d.sx = t.stride()
+    return arr
+
+
+def _chk_levels(levels):
+    if not levels:
+        raise ValueError("pack_levels: empty level list")
+    if len(levels) > _lib.MAX_LEVELS:
+        raise ValueError("pack_levels: %d levels, a PyramidShape holds at most %d" % (len(levels), _lib.MAX_LEVELS))
+    n, c = levels[0].shape[0], levels[0].shape[1]
+    for t in levels:
+        if not t.is_cuda:
+            raise RuntimeError("scan_amd ops run only on the GPU (HIP) -- got a %s tensor; no CPU fallback" % t.device)
+        if t.dtype != torch.float32 or t.dim() != 4 or t.shape[0] != n or t.shape[1] != c:
+            raise ValueError("pack_levels: every level must be a fp32 [N, C, h, w] tensor with the same N and C")
+    return n, c
+
+
+def _level_format(t):
+    """memory format a gradient / copy of level t is allocated in: channels_last when its channels are the fastest dimension"""
+    return torch.channels_last if t.stride(1) == 1 and t.shape[1] > 1 else torch.contiguous_format
+
+
+def _unpack_into(rows, shape, c, formats):
+    out = [torch.empty((shape.n_images, c, h, w), dtype=rows.dtype, device=rows.device, memory_format=f)
+           for (h, w), f in zip(shape.sizes, formats)]
+    call("scan_pyramid_unpack", _ptr(rows), rows.shape[1], _level_descs(out), len(out), shape.n_images, c, _stream())
+    return out
+
+
+class _PackLevels(torch.autograd.Function):
+    """per-level [N, C, h, w] tensors of any strides -> rows [M, Cs] in one launch (csrc/pyramid_pack.hip); the backward is the
+    unpack kernel on the row gradient."""
+
+    @staticmethod
+    def forward(ctx, shape, cs, *levels):
+        c = levels[0].shape[1]
+        rows = levels[0].new_empty((shape.rows, cs))  # every element, padding columns included, is written by the kernel
+        call("scan_pyramid_pack", _level_descs(levels), len(levels), shape.n_images, c, _ptr(rows), cs, _stream())
+        ctx.cfg = (shape, c, [_level_format(t) for t in levels])
+        return rows
+
+    @staticmethod
+    def backward(ctx, g):
+        shape, c, formats = ctx.cfg
+        grads = _unpack_into(g.contiguous(), shape, c, formats)
+        return (None, None) + tuple(gl if need else None for gl, need in zip(grads, ctx.needs_input_grad[2:]))
+
+
+class _UnpackLevels(torch.autograd.Function):
+    """rows [M, Cs] -> one fresh [N, c, h, w] tensor per level in one launch; the backward is the pack kernel on the level
+    gradients, whatever their strides (an absent one counts as zeros)."""
+
+    @staticmethod
+    def forward(ctx, rows, shape, c, memory_format):
+        ctx.cfg = (shape, c, rows.shape[1])
+        return tuple(_unpack_into(rows, shape, c, [memory_format] * shape.n_levels))
+
+    @staticmethod
+    def backward(ctx, *grads):
+        shape, c, cs = ctx.cfg
+        ref = next(g for g in grads if g is not None)
+        grads = [g if g is not None else ref.new_zeros((shape.n_images, c, h, w)) for g, (h, w) in zip(grads, shape.sizes)]
+        out = ref.new_empty((shape.rows, cs))
+        call("scan_pyramid_pack", _level_descs(grads), len(grads), shape.n_images, c, _ptr(out), cs, _stream())
+        return out, None, None, None
+
+
+class PyramidLevels(list):
+    """The per-level channels_last [N, C, h, w] views of ONE pyramid row matrix, as the reference-shaped modules
+    (scan_amd/modeling/factory.py) return them -- a plain list to a caller that indexes or iterates it -- together with the
+    ``rows`` [M, Cs] matrix and the ``shape`` they are views of.  pack_levels hands ``rows`` back without a copy as long as
+    every element still is the view it was made as."""
+
+    def __init__(self, rows, shape, c=None):
+        if rows.dim() != 2 or rows.shape[0] != shape.rows:
+            raise ValueError("PyramidLevels: rows %s do not fit %r" % (tuple(rows.shape), shape))
+        self.rows, self.shape = rows, shape
+        self.c = rows.shape[1] if c is None else int(c)
+        parts = split_levels(rows, shape) if rows.requires_grad and torch.is_grad_enabled() else \
+            [rows[shape.row_off[l]:shape.row_off[l + 1]] for l in range(shape.n_levels)]
+        super().__init__((p if self.c == p.shape[1] else p[:, :self.c]).view(shape.n_images, h, w, self.c).permute(0, 3, 1, 2)
+                         for p, (h, w) in zip(parts, shape.sizes))
+        self._made = [(t.data_ptr(), tuple(t.shape), t.stride()) for t in self]
+
+    def intact(self):
+        """every element still has the data_ptr, shape and strides of its slice of ``rows`` (nobody replaced or reordered one)"""
+        return len(self) == len(self._made) and all(
+            isinstance(t, torch.Tensor) and (t.data_ptr(), tuple(t.shape), t.stride()) == m for t, m in zip(self, self._made))
+
+
+def pack_levels(levels, cs=None):
+    """list of per-level [N, C, h, w] fp32 tensors (any strides) -> (rows [M, Cs], PyramidShape); Cs defaults to pad4(C).
+    A PyramidLevels whose elements are untouched gives its own ``rows`` back (no launch, same storage), unless another
+    ``cs`` than its row pitch is asked for."""
+    if isinstance(levels, PyramidLevels) and (cs is None or cs == levels.rows.shape[1]) and levels.rows.is_contiguous() \
+            and levels.c == levels.rows.shape[1] and levels.intact():
+        _chk(levels.rows)
+        return levels.rows, levels.shape
+    levels = list(levels)
+    n, c = _chk_levels(levels)
+    cs = pad4(c) if cs is None else int(cs)
+    if cs < c or cs % 4:
+        raise ValueError("pack_levels: cs=%d must be a multiple of 4 and >= C=%d" % (cs, c))
+    shape = PyramidShape(n, [tuple(t.shape[2:]) for t in levels])
+    return _PackLevels.apply(shape, cs, *levels), shape
+
+
+def unpack_levels(rows, shape, c=None, memory_format=torch.channels_last):
+    """rows [M, Cs] -> list of fresh per-level [N, c, h, w] tensors in ``memory_format`` (columns c..Cs-1 are dropped)."""
+    _chk(rows)
+    c = rows.shape[1] if c is None else int(c)
+    if rows.dim() != 2 or rows.shape[0] != shape.rows or not 1 <= c <= rows.shape[1] or rows.shape[1] % 4:
+        raise ValueError("unpack_levels: rows %s do not fit %r with c=%d (the row pitch must be a multiple of 4)"
+                         % (tuple(rows.shape), shape, c))
+    return list(_UnpackLevels.apply(rows, shape, c, memory_format))
+
+
 # ----------------------------------------------------------------------------- 2x2 max pooling
 class _MaxPool2x2(torch.autograd.Function):
     @staticmethod

@@ -1,4 +1,5 @@
-"""Batch container semantics the hot path relies on (reference fcos_core/structures/image_list.py:8-72).
+"""Batch and box containers of the reference's interface: ImageList (fcos_core/structures/image_list.py:8-72) and BoxList with
+its helpers (structures/bounding_box.py:9-266, structures/boxlist_ops.py), further down.
 
 The reference collator hands the detector an ImageList: images of different sizes zero-padded at the bottom /
 right to a common size that is a multiple of SIZE_DIVISIBILITY (32), plus the true (h, w) of every image, which
@@ -43,3 +44,153 @@ def to_image_list(tensors, size_divisible=0):
     for t, dst in zip(tensors, batch):
         dst[:, :t.shape[1], :t.shape[2]].copy_(t)
     return ImageList(batch, [t.shape[-2:] for t in tensors])
+
+
+# ----------------------------------------------------------------------------- BoxList
+FLIP_LEFT_RIGHT = 0
+FLIP_TOP_BOTTOM = 1
+_MODES = ("xyxy", "xywh")
+
+
+class BoxList:
+    """The boxes of ONE image with per-box extra fields (reference fcos_core/structures/bounding_box.py:9-266): what the
+    reference's data pipeline hands the detector as ``targets`` and what its post-processor returns as detections.
+
+    bbox [n, 4] fp32, size = (image width, image height), mode "xyxy" or "xywh".  Pixel-index convention of the reference
+    (its TO_REMOVE = 1): a box covering pixels x0..x1 has width x1 - x0 + 1, so xywh <-> xyxy, area, the left-right flip and
+    the clipping bound all carry that 1.  Plain torch ops on either device: nothing here is on the hot path."""
+
+    def __init__(self, bbox, image_size, mode="xyxy"):
+        dev = bbox.device if isinstance(bbox, torch.Tensor) else torch.device("cpu")
+        bbox = torch.as_tensor(bbox, dtype=torch.float32, device=dev)
+        if bbox.dim() != 2 or bbox.shape[-1] != 4:
+            raise ValueError("BoxList: bbox must be [n, 4], got %s" % (tuple(bbox.shape),))
+        if mode not in _MODES:
+            raise ValueError("BoxList: mode must be 'xyxy' or 'xywh', got %r" % (mode,))
+        self.bbox, self.size, self.mode = bbox, tuple(image_size), mode
+        self.extra_fields = {}
+
+    # ---- extra fields
+    def add_field(self, field, field_data):
+        self.extra_fields[field] = field_data
+
+    def get_field(self, field):
+        return self.extra_fields[field]
+
+    def has_field(self, field):
+        return field in self.extra_fields
+
+    def fields(self):
+        return list(self.extra_fields)
+
+    def copy_with_fields(self, fields, skip_missing=False):
+        out = BoxList(self.bbox, self.size, self.mode)
+        for f in fields if isinstance(fields, (list, tuple)) else [fields]:
+            if self.has_field(f):
+                out.add_field(f, self.get_field(f))
+            elif not skip_missing:
+                raise KeyError("Field '%s' not found in %r" % (f, self))
+        return out
+
+    def _derived(self, bbox, size, mode, field_op=None):
+        """a new BoxList carrying this one's fields; non-tensor fields (masks, keypoints) follow the geometry through field_op"""
+        out = BoxList(bbox, size, mode)
+        for k, v in self.extra_fields.items():
+            if field_op is not None and not isinstance(v, torch.Tensor):
+                v = field_op(v)
+            out.add_field(k, v)
+        return out
+
+    # ---- geometry
+    def _xyxy(self):
+        """the four corner columns, each [n, 1]"""
+        a, b, c, d = self.bbox.split(1, dim=-1)
+        if self.mode == "xyxy":
+            return a, b, c, d
+        return a, b, a + (c - 1).clamp(min=0), b + (d - 1).clamp(min=0)
+
+    def convert(self, mode):
+        if mode not in _MODES:
+            raise ValueError("BoxList: mode must be 'xyxy' or 'xywh', got %r" % (mode,))
+        if mode == self.mode:
+            return self
+        x0, y0, x1, y1 = self._xyxy()
+        cols = (x0, y0, x1, y1) if mode == "xyxy" else (x0, y0, x1 - x0 + 1, y1 - y0 + 1)
+        return self._derived(torch.cat(cols, -1), self.size, mode)
+
+    def resize(self, size, *args, **kwargs):
+        """the boxes of the image scaled to ``size`` = (width, height)"""
+        size = tuple(size)
+        rw, rh = (float(s) / float(o) for s, o in zip(size, self.size))
+        op = lambda v: v.resize(size, *args, **kwargs)
+        if rw == rh:  # one ratio: every column scales alike, in either mode
+            return self._derived(self.bbox * rw, size, self.mode, op)
+        x0, y0, x1, y1 = self._xyxy()
+        return self._derived(torch.cat((x0 * rw, y0 * rh, x1 * rw, y1 * rh), -1), size, "xyxy", op).convert(self.mode)
+
+    def transpose(self, method):
+        """FLIP_LEFT_RIGHT or FLIP_TOP_BOTTOM (the reference flips columns as pixel indices, rows as coordinates)"""
+        if method not in (FLIP_LEFT_RIGHT, FLIP_TOP_BOTTOM):
+            raise NotImplementedError("Only FLIP_LEFT_RIGHT and FLIP_TOP_BOTTOM implemented")
+        width, height = self.size
+        x0, y0, x1, y1 = self._xyxy()
+        if method == FLIP_LEFT_RIGHT:
+            cols = (width - x1 - 1, y0, width - x0 - 1, y1)
+        else:
+            cols = (x0, height - y1, x1, height - y0)
+        return self._derived(torch.cat(cols, -1), self.size, "xyxy", lambda v: v.transpose(method)).convert(self.mode)
+
+    def clip_to_image(self, remove_empty=True):
+        """clamps the four columns IN PLACE to [0, width - 1] / [0, height - 1]; remove_empty drops boxes with x1 <= x0 or y1 <= y0"""
+        w, h = self.size
+        for col, hi in ((0, w - 1), (1, h - 1), (2, w - 1), (3, h - 1)):
+            self.bbox[:, col].clamp_(min=0, max=hi)
+        if remove_empty:
+            b = self.bbox
+            return self[(b[:, 3] > b[:, 1]) & (b[:, 2] > b[:, 0])]
+        return self
+
+    def area(self):
+        b = self.bbox
+        if self.mode == "xyxy":
+            return (b[:, 2] - b[:, 0] + 1) * (b[:, 3] - b[:, 1] + 1)
+        return b[:, 2] * b[:, 3]
+
+    # ---- container
+    def to(self, device):
+        out = BoxList(self.bbox.to(device), self.size, self.mode)
+        for k, v in self.extra_fields.items():
+            out.add_field(k, v.to(device) if hasattr(v, "to") else v)
+        return out
+
+    def __getitem__(self, item):
+        out = BoxList(self.bbox[item], self.size, self.mode)
+        for k, v in self.extra_fields.items():
+            out.add_field(k, v[item])
+        return out
+
+    def __len__(self):
+        return self.bbox.shape[0]
+
+    def __repr__(self):
+        return "BoxList(num_boxes=%d, image_width=%s, image_height=%s, mode=%s)" % (len(self), self.size[0], self.size[1],
+                                                                                  self.mode)
+
+
+def cat_boxlist(bboxes):
+    """list of BoxList of one image size, mode and field set -> one BoxList (reference structures/boxlist_ops.py:127-153)"""
+    if not isinstance(bboxes, (list, tuple)) or not bboxes or not all(isinstance(b, BoxList) for b in bboxes):
+        raise TypeError("cat_boxlist: a non-empty list of BoxList is needed")
+    first = bboxes[0]
+    if any(b.size != first.size or b.mode != first.mode or set(b.fields()) != set(first.fields()) for b in bboxes):
+        raise ValueError("cat_boxlist: image size, mode and fields must agree")
+    out = BoxList(torch.cat([b.bbox for b in bboxes], 0), first.size, first.mode)
+    for f in first.fields():
+        out.add_field(f, torch.cat([b.get_field(f) for b in bboxes], 0))
+    return out
+
+
+def remove_small_boxes(boxlist, min_size):
+    """keeps the boxes whose width AND height (pixel counts, the + 1 included) are >= min_size (boxlist_ops.py:59-73)"""
+    wh = boxlist.convert("xywh").bbox
+    return boxlist[((wh[:, 2] >= min_size) & (wh[:, 3] >= min_size)).nonzero().squeeze(1)]
