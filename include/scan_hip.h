@@ -38,6 +38,7 @@ typedef struct {
 } scan_pyramid_t;
 
 const char* scan_last_error(void);
+/* changes when an existing declaration changes its meaning; declarations that are only added leave it as it is */
 int scan_abi_version(void);
 
 /* Tuning knob for A/B measurements and tests (no reference counterpart): scan_tune(key, value) sets an integer
@@ -398,6 +399,51 @@ int scan_conv3x3_wino_bf16x6(const float* x, const scan_pyramid_t* d, int32_t Cs
                              const void* wl, int32_t Csw, const float* bias, const float* mask, float* y, int32_t Nout,
                              int32_t Ns, int32_t relu, float* gn_ws, int32_t clear, void* stream);
 int scan_conv3x3_bf16x6_wino(int32_t Nout, int32_t Csw);
+/* ---- one dispatcher for the split-operand forward / data-gradient convolutions above (no reference counterpart) ----
+ * Which weight planes a conv needs, which kernel family and instance runs it and how the launch is cut are decided HERE,
+ * once, for every binding (scan_amd.ops over ctypes, the compiled scan_ops module, a C caller): plan the conv, split the
+ * weights as the plan says, run it.  The entry points above stay what they were: single launches of one family for callers
+ * that choose themselves.  A plan is host arithmetic under the scan_tune knobs of the moment ("conv_wino" and the instance
+ * knobs): plan again after changing one; planes split for a plan belong to that plan's split_mode / csw / pieces. */
+#define SCAN_CONV_SUMS 1 /* flags: the epilogue accumulates GroupNorm(32, 256) sums (3x3, nout == 256, no ReLU, no mask) */
+#define SCAN_CONV_POOL 2 /* flags: fused 2x2 / stride-2 max-pool (3x3 forward, single-level pyramid with even H, W) */
+#define SCAN_CONV_DIRECT3X3 0 /* family: scan_conv3x3_bf16x3 / _bf16x6 and their _gn_ / _pool2_ forms */
+#define SCAN_CONV_WINO3X3 1   /* family: scan_conv3x3_wino_bf16x6 */
+#define SCAN_CONV_1X1 2       /* family: scan_conv1x1_bf16x3 / _bf16x6 */
+typedef struct {
+  int32_t pieces;     /* bf16 pieces per fp32 operand: 2 ("bf16x3") or 3 ("bf16x6") */
+  int32_t taps;       /* taps of the packed fp32 weight [O][taps][Cs_w]: 9 (3x3 / stride 1) or 1 (1x1) */
+  int32_t dgrad;      /* 0: forward (nout = O); 1: data gradient (nout = Cs_w, x = dY) */
+  int32_t O, Cs_w;    /* the packed weight's rows and row length, as given to scan_conv_plan */
+  int32_t split_mode; /* scan_weight_split mode the planes are written in: 0 / 1 = forward / dgrad, 2 / 3 = their Winograd planes */
+  int32_t plane_rows; /* each plane is [plane_rows][plane_taps][csw] bf16 */
+  int32_t plane_taps; /* 9, 1, or 12 (Winograd) */
+  int32_t csw;        /* plane row length: 3x3 planes are padded to whole 32-channel K chunks, 1x1 planes to 8 */
+  int32_t nout;       /* output channels of the conv */
+  int32_t rem;        /* > 0: the last rem output channels run as a second launch of the direct kernel (a 3x3 conv with
+                         nout > 128, 0 < nout % 128 <= 64, Cs_src >= 512 and >= 100,000 output rows, without sums or pool:
+                         the 64-channel instance takes the remainder instead of an almost empty 128-wide tile) */
+  int32_t family;     /* SCAN_CONV_DIRECT3X3 / SCAN_CONV_WINO3X3 / SCAN_CONV_1X1 */
+  int32_t instance;   /* what the scan_conv*_instance queries report for the whole nout (3128 = the Winograd instance):
+                         the label bench.py's kernel timer prints */
+  int32_t flags;      /* SCAN_CONV_SUMS | SCAN_CONV_POOL as planned */
+} scan_conv_plan_t;
+/* Fills *plan for a conv with packed weights [O][taps][Cs_w] reading Cs_src channels per pixel (forward: the input's row
+ * length, normally Cs_w; dgrad: dY's row length, >= O) on output pyramid od (3x3: the pyramid of input and output, before
+ * the pool if any).  Touches no device. */
+int scan_conv_plan(int32_t pieces, int32_t taps, int32_t dgrad, int32_t O, int32_t Cs_w, int32_t Cs_src,
+                   const scan_pyramid_t* od, int32_t flags, scan_conv_plan_t* plan);
+/* scan_weight_split / scan_weight_split3 of w [O][taps][Cs_w] in the plan's pieces, split_mode and csw; p2 only with three pieces */
+int scan_conv_weight_split(const scan_conv_plan_t* plan, const float* w, void* p0, void* p1, void* p2, void* stream);
+/* Runs the planned conv on planes from scan_conv_weight_split: y [M][Ns] (first nout columns written).  3x3: xd is the one
+ * pyramid, yd and map are not read; 1x1: xd / yd / map as scan_conv1x1_bf16x3.  relu != 0: ReLU; mask as scan_conv3x3_bf16x3
+ * (none with sums or pool).  gn_ws: the GroupNorm workspace of a plan with SCAN_CONV_SUMS (NULL otherwise); clear != 0 zeroes
+ * it first (scan_conv3x3_gn_bf16x3), 0 adds to it (scan_conv3x3_gn_acc_bf16x3).  Everything is validated before the first
+ * launch. */
+int scan_conv_run(const scan_conv_plan_t* plan, const float* x, const scan_pyramid_t* xd, int32_t Cs, const void* p0,
+                  const void* p1, const void* p2, const float* bias, const float* mask, float* y,
+                  const scan_pyramid_t* yd, int32_t Ns, int32_t relu, int32_t map, float* gn_ws, int32_t clear,
+                  void* stream);
 /* w [Cout][T][Cin_s] -> wt [Cin_s][T][Cout_s] (zero padded) */
 int scan_weight_transpose(const float* w, int32_t Cout, int32_t T, int32_t Cin_s, float* wt, int32_t Cout_s,
                           void* stream);

@@ -46,6 +46,15 @@ class LevelDesc(ctypes.Structure):
     _fields_ = [("data", c_vp), ("h", c_i32), ("w", c_i32), ("sn", c_i64), ("sc", c_i64), ("sy", c_i64), ("sx", c_i64)]
 
 
+class ConvPlan(ctypes.Structure):
+    """scan_conv_plan_t"""
+    _fields_ = [(n, c_i32) for n in ("pieces", "taps", "dgrad", "O", "Cs_w", "split_mode", "plane_rows", "plane_taps", "csw",
+                                     "nout", "rem", "family", "instance", "flags")]
+
+
+CONV_SUMS, CONV_POOL = 1, 2  # SCAN_CONV_SUMS, SCAN_CONV_POOL
+_CP = ctypes.POINTER(ConvPlan)
+
 PACK_MAX_LEVELS = 8  # SCAN_PACK_MAX_LEVELS
 SGD_MAX_SEGMENTS = 32
 CKA_MAX_CLASSES = 16
@@ -72,6 +81,10 @@ SIGNATURES = {
     "scan_conv3x3_bf16x6_wino": (ctypes.c_int, [c_i32, c_i32]),
     "scan_conv3x3_wino_bf16x6": (ctypes.c_int, [c_vp, _PD, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
                                                 c_vp, c_i32, c_vp]),
+    "scan_conv_plan": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, _PD, c_i32, _CP]),
+    "scan_conv_weight_split": (ctypes.c_int, [_CP, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "scan_conv_run": (ctypes.c_int, [_CP, c_vp, _PD, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _PD, c_i32, c_i32, c_i32, c_vp,
+                                     c_i32, c_vp]),
     "scan_sigmoid_focal_loss_forward": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i32, c_f32, c_f32, c_vp, c_vp, c_vp]),
     "scan_sigmoid_focal_loss_backward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f32, c_i64, c_i32, c_f32, c_f32, c_vp, c_vp]),
     "scan_iou_loss_forward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),

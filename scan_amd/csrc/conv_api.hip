@@ -1,9 +1,12 @@
 // Public entry points of the split-operand convolutions, forward and data gradient ("bf16x3" = two bf16 pieces per fp32
-// operand, "bf16x6" = three: conv_split.h), of their instance queries and of the weight split.
+// operand, "bf16x6" = three: conv_split.h), of their instance queries, of the weight split, and of the dispatcher that
+// chooses among them (scan_conv_plan / scan_conv_weight_split / scan_conv_run, at the end of the file).
 //
-// Every conv entry point does the same four things: validate the arguments (check3x3 / check1x1), fill a ConvArgs, pick the
-// kernel instance (conv_launch.h: pick3x3 / pick1x1 in conv_fwd.hip; the Winograd entry has its own instance; two-piece
-// launches go to conv_gen1.hip under scan_tune("conv_v2", 0)), launch and check.  No kernel of the convolutions lives here.
+// Every single-launch entry point does the same four things: validate the arguments (check3x3 / check1x1), fill a ConvArgs,
+// pick the kernel instance (conv_launch.h: pick3x3 / pick1x1 in conv_fwd.hip; the Winograd entry has its own instance;
+// two-piece launches go to conv_gen1.hip under scan_tune("conv_v2", 0)), launch and check.  The dispatcher is the one place
+// that says which of them a conv takes, on which weight planes: scan_amd/ops.py and scan_ops_ext.cpp hold no such rule.
+// No kernel of the convolutions lives here.
 //
 // dgrad reuses the forward kernels: dX = conv3x3(dY, W') with W'[c][t][o] = W[o][8-t][c]
 // (scan_weight_split mode 1 writes the flipped + transposed copy).
@@ -207,10 +210,9 @@ extern "C" int scan_conv3x3_gn_bf16x6(const float* x, const scan_pyramid_t* d, i
 // the Winograd F(2,3) instance (conv_fwd.hip): wh / wm / wl = scan_weight_split3 planes of mode 2 (forward) or 3 (data
 // gradient); gn_ws != nullptr: the GroupNorm sums of scan_conv3x3_gn_bf16x6 (Nout == 256, clear as there); relu: bit 0 =
 // ReLU, bit 1 = fused 2x2 / stride-2 max-pool as scan_conv3x3_pool2_bf16x6 (single level, even H and W)
-extern "C" int scan_conv3x3_wino_bf16x6(const float* x, const scan_pyramid_t* d, int32_t Cs, const void* wh, const void* wm,
-                                        const void* wl, int32_t Csw, const float* bias, const float* mask, float* y,
-                                        int32_t Nout, int32_t Ns, int32_t relu, float* gn_ws, int32_t clear, void* stream) {
-  const char* name = "conv3x3_wino_bf16x6";
+static int conv3x3_wino(const char* name, const float* x, const scan_pyramid_t* d, int32_t Cs, const void* wh, const void* wm,
+                        const void* wl, int32_t Csw, const float* bias, const float* mask, float* y, int32_t Nout, int32_t Ns,
+                        int32_t relu, float* gn_ws, int32_t clear, void* stream) {
   if (check3x3(name, 3, x, d, Cs, wh, wm, wl, Csw, mask, y, Nout, Ns)) return -1;
   SCAN_CHECK_ARG(Nout > 64 && Csw % 32 == 0, "%s: needs Nout > 64 and Csw %% 32 == 0 (Nout=%d Csw=%d)", name, Nout, Csw);
   if (gn_ws != nullptr)
@@ -223,6 +225,11 @@ extern "C" int scan_conv3x3_wino_bf16x6(const float* x, const scan_pyramid_t* d,
   conv3x3_wino_launch(conv_args(x, d, d, Cs, wh, wm, wl, Csw, bias, mask, y, Nout, Ns, relu & 3, 0, stream, gn_ws));
   SCAN_LAUNCH_CHECK(name);
   return 0;
+}
+extern "C" int scan_conv3x3_wino_bf16x6(const float* x, const scan_pyramid_t* d, int32_t Cs, const void* wh, const void* wm,
+                                        const void* wl, int32_t Csw, const float* bias, const float* mask, float* y,
+                                        int32_t Nout, int32_t Ns, int32_t relu, float* gn_ws, int32_t clear, void* stream) {
+  return conv3x3_wino("conv3x3_wino_bf16x6", x, d, Cs, wh, wm, wl, Csw, bias, mask, y, Nout, Ns, relu, gn_ws, clear, stream);
 }
 
 // conv3x3 + bias (+ ReLU) + 2x2 / stride-2 max-pool in one launch: y [N, H/2, W/2, Ns] (forward only; single-level
@@ -278,3 +285,89 @@ extern "C" int scan_conv1x1_bf16x6_instance(const scan_pyramid_t* yd, int32_t No
 }
 // 1: ops.py splits this layer's weights into Winograd planes and calls scan_conv3x3_wino_bf16x6 (scan_tune "conv_wino")
 extern "C" int scan_conv3x3_bf16x6_wino(int32_t Nout, int32_t Csw) { return g_scan_conv_wino && Nout > 64 && Csw % 32 == 0 ? 1 : 0; }
+
+// ---- the dispatcher: plan (host arithmetic), split the weights as planned, run.  The rules below were scan_amd/ops.py's
+// _conv_split and, a second time, scan_ops_ext.cpp's; they read the knobs through the picker and the Winograd query above.
+extern "C" int scan_conv_plan(int32_t pieces, int32_t taps, int32_t dgrad, int32_t O, int32_t Cs_w, int32_t Cs_src,
+                              const scan_pyramid_t* od, int32_t flags, scan_conv_plan_t* plan) {
+  const char* name = "conv_plan";
+  SCAN_CHECK_ARG(plan != nullptr, "%s: null plan", name);
+  SCAN_CHECK_ARG((pieces == 2 || pieces == 3) && (taps == 9 || taps == 1) && (dgrad == 0 || dgrad == 1), "%s: pieces=%d taps=%d dgrad=%d",
+                 name, pieces, taps, dgrad);
+  SCAN_CHECK_ARG(O > 0 && Cs_w > 0 && Cs_src > 0, "%s: O=%d Cs_w=%d Cs_src=%d", name, O, Cs_w, Cs_src);
+  const bool sums = flags & SCAN_CONV_SUMS, pool = flags & SCAN_CONV_POOL;
+  SCAN_CHECK_ARG((flags & ~(SCAN_CONV_SUMS | SCAN_CONV_POOL)) == 0 && !(sums && pool), "%s: flags=%d (sums or the pool)", name, flags);
+  if (check_pyramid(name, od)) return -1;
+  // plane rows are zero-padded to whole 32-channel K chunks for the 3x3 kernels: the LDS-DMA weight path needs whole chunks
+  // (a 264-channel input then takes it too); 1x1 planes keep the 8-element granule
+  const int32_t rnd = taps == 9 ? 32 : 8;
+  scan_conv_plan_t p{};
+  p.pieces = pieces, p.taps = taps, p.dgrad = dgrad, p.O = O, p.Cs_w = Cs_w, p.flags = flags;
+  p.plane_rows = p.nout = dgrad ? Cs_w : O;
+  p.csw = ((dgrad ? (O > Cs_src ? O : Cs_src) : Cs_w) + rnd - 1) / rnd * rnd;
+  // 128-wide output tiles plus a small remainder (data gradient of the 264-channel discriminator input at P3, K = 1024): the
+  // remainder columns go through the 64-channel instance instead of a third, almost empty 128-wide tile (2022 -> 1794 us).
+  // With a short K loop or few rows the extra launch costs more than the empty tile (265-channel head_out input: 614 ->
+  // 721 us), hence the size test.
+  const int32_t rem = p.nout % 128;
+  if (taps == 9 && !sums && !pool && p.nout > 128 && rem > 0 && rem <= 64 && Cs_src >= 512 && od->row_off[od->n_levels] >= 100000)
+    p.rem = rem;
+  // the Winograd F(2,3) kernel reads planes of its own: split modes 2 / 3, 12 taps per row
+  const bool wino = pieces == 3 && taps == 9 && p.rem == 0 && scan_conv3x3_bf16x6_wino(p.nout, p.csw) == 1;
+  p.family = wino ? SCAN_CONV_WINO3X3 : taps == 9 ? SCAN_CONV_DIRECT3X3 : SCAN_CONV_1X1;
+  p.split_mode = dgrad + (wino ? 2 : 0);
+  p.plane_taps = wino ? 12 : taps;
+  // 3128: the Winograd instance (128-channel tile); the others as the scan_conv*_instance queries (whole K chunks)
+  p.instance = wino ? 3128 : taps == 9 ? pick3x3(pieces, od, p.nout, true).id : pick1x1(pieces, od, p.nout, p.csw).id;
+  *plan = p;
+  return 0;
+}
+
+static int check_plan(const char* name, const scan_conv_plan_t* p) {
+  SCAN_CHECK_ARG(p != nullptr, "%s: null plan", name);
+  SCAN_CHECK_ARG((p->pieces == 2 || p->pieces == 3) && (p->taps == 9 || p->taps == 1) && p->nout > 0 && p->rem >= 0 && p->rem < p->nout &&
+                     p->csw > 0 && p->family >= SCAN_CONV_DIRECT3X3 && p->family <= SCAN_CONV_1X1 &&
+                     (p->family == SCAN_CONV_1X1) == (p->taps == 1) && (p->family != SCAN_CONV_WINO3X3 || (p->pieces == 3 && p->rem == 0)),
+                 "%s: not a plan scan_conv_plan filled", name);
+  return 0;
+}
+
+extern "C" int scan_conv_weight_split(const scan_conv_plan_t* plan, const float* w, void* p0, void* p1, void* p2, void* stream) {
+  if (check_plan("conv_weight_split", plan)) return -1;
+  return weight_split_launch(plan->pieces, w, plan->O, plan->taps, plan->Cs_w, plan->split_mode, p0, p1, p2, plan->csw, stream);
+}
+
+extern "C" int scan_conv_run(const scan_conv_plan_t* plan, const float* x, const scan_pyramid_t* xd, int32_t Cs, const void* p0,
+                             const void* p1, const void* p2, const float* bias, const float* mask, float* y,
+                             const scan_pyramid_t* yd, int32_t Ns, int32_t relu, int32_t map, float* gn_ws, int32_t clear,
+                             void* stream) {
+  const char* name = "conv_run";
+  if (check_plan(name, plan)) return -1;
+  const int np = plan->pieces, nout = plan->nout, csw = plan->csw;
+  const bool sums = plan->flags & SCAN_CONV_SUMS, pool = plan->flags & SCAN_CONV_POOL;
+  relu = relu ? 1 : 0;
+  SCAN_CHECK_ARG(plan->taps == 9 || plan->flags == 0, "%s: sums and the fused pool are epilogues of the 3x3 kernels", name);
+  SCAN_CHECK_ARG(!(pool && plan->dgrad), "%s: the fused pool is forward only", name);
+  SCAN_CHECK_ARG(sums == (gn_ws != nullptr), "%s: a GroupNorm workspace goes with a plan for sums, and only with one", name);
+  SCAN_CHECK_ARG(!(sums || pool) || mask == nullptr, "%s: no mask with sums or the fused pool", name);
+  SCAN_CHECK_ARG(!sums || !relu, "%s: no ReLU with GroupNorm sums", name);
+  switch (plan->family) {
+    case SCAN_CONV_1X1:
+      return conv1x1(name, np, x, xd, Cs, p0, p1, p2, csw, bias, mask, y, yd, nout, Ns, relu, map, stream);
+    case SCAN_CONV_WINO3X3:
+      return conv3x3_wino(name, x, xd, Cs, p0, p1, p2, csw, bias, mask, y, nout, Ns, relu | (pool ? 2 : 0), gn_ws, clear, stream);
+    default:
+      break;
+  }
+  if (sums) return conv3x3_gn(name, np, clear, x, xd, Cs, p0, p1, p2, csw, bias, y, nout, Ns, gn_ws, stream);
+  if (pool && check_pool2(name, xd)) return -1;
+  if (plan->rem == 0) return conv3x3(name, np, x, xd, Cs, p0, p1, p2, csw, bias, mask, y, nout, Ns, relu | (pool ? 2 : 0), stream);
+  // main part on 128-wide tiles, then the remainder columns: planes, bias, mask and y move on by the main channels
+  if (check3x3(name, np, x, xd, Cs, p0, p1, p2, csw, mask, y, nout, Ns)) return -1;
+  const int32_t main = nout - plan->rem;
+  const size_t wo = (size_t)main * plan->plane_taps * csw * sizeof(__bf16);
+  auto at = [wo](const void* q) -> const void* { return q ? static_cast<const char*>(q) + wo : nullptr; };
+  if (int rc = conv3x3(name, np, x, xd, Cs, p0, p1, p2, csw, bias, mask, y, main, Ns, relu, stream)) return rc;
+  return conv3x3(name, np, x, xd, Cs, at(p0), at(p1), at(p2), csw, bias ? bias + main : nullptr, mask ? mask + main : nullptr,
+                 y + main, plan->rem, Ns, relu, stream);
+}

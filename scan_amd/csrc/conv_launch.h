@@ -1,5 +1,7 @@
 // Host-side launch layer of the split-operand forward / data-gradient convolutions (internal to libscan_hip.so).
-//   conv_api.hip    the public entry points: validate the arguments, fill a ConvArgs, pick an instance, launch, check
+//   conv_api.hip    the public entry points: validate the arguments, fill a ConvArgs, pick an instance, launch, check; and the
+//                   dispatcher above them (scan_conv_plan / _weight_split / _run): planes, kernel family and launch cut of a conv,
+//                   decided once for the Python and the C++ bindings
 //   conv_fwd.hip    the production kernel, its instantiations and the picker that chooses among them
 //   conv_gen1.hip   the first-generation kernel behind scan_tune("conv_v2", 0)
 // and the scan_tune knobs of the whole library: each is DEFINED, with the measurements behind its default, next to the launch

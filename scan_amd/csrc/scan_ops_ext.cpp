@@ -17,7 +17,8 @@
 //        rpn/fcos/condgraph.py:619-629,344-346
 //
 // Arithmetic: the reference's fp32 multiply / fp32 accumulate on the bf16 matrix cores ("bf16x6", scan_hip.h); 3x3 / stride 2
-// (P6 / P7) on the exact fp32-MFMA kernels.  Same kernels as scan_amd.ops -> bit-identical results (tests/test_gpu_kernels.py).
+// (P6 / P7) on the exact fp32-MFMA kernels.  Which planes and which kernel a conv takes is the library's decision
+// (scan_conv_plan), the one scan_amd.ops follows too -> bit-identical results (tests/test_gpu_kernels.py).
 #include <ATen/ATen.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
@@ -37,7 +38,6 @@ using torch::autograd::variable_list;
 void* cur_stream(const at::Tensor& t) { return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(t.device().index()).stream(); }
 void check(int rc, const char* what) { TORCH_CHECK(rc == 0, what, " failed (", rc, "): ", scan_last_error()); }
 int64_t pad4(int64_t c) { return (c + 3) / 4 * 4; }
-int64_t round_up(int64_t c, int64_t m) { return (c + m - 1) / m * m; }
 
 void require_gpu_f32(const at::Tensor& t, const char* who, const char* what) {
   TORCH_CHECK(t.is_cuda(), who, ": ", what, " must be a GPU tensor (the HIP kernels have no CPU fallback)");
@@ -80,8 +80,15 @@ at::Tensor unpack_wgrad(const at::Tensor& dwp, int64_t i, int64_t k) {
 
 struct Planes {
   at::Tensor p[3];
-  int64_t csw;
 };
+
+// which planes, which kernel family, how the launch is cut: the library's one dispatcher (scan_conv_plan, scan_hip.h) -- the
+// function scan_amd.ops asks, so the two bindings cannot disagree
+scan_conv_plan_t conv_plan(int64_t taps, bool dgrad, int64_t o, int64_t cs_w, int64_t cs_src, const scan_pyramid_t& od, int flags) {
+  scan_conv_plan_t plan;
+  check(scan_conv_plan(3, (int32_t)taps, dgrad ? 1 : 0, (int32_t)o, (int32_t)cs_w, (int32_t)cs_src, &od, flags, &plan), "scan_conv_plan");
+  return plan;
+}
 
 // ---- weight planes across calls.  A reference-shaped module graph calls the SAME conv once per pyramid level (rpn/fcos/fcos.py:
 // 66-114 shares its towers over five levels), and every call would split the same fp32 weight into the same three bf16 planes
@@ -106,39 +113,43 @@ void invalidate_weight_cache() {
   ++g_plane_epoch;
   plane_cache().clear();
 }
-// three bf16 planes of packed weights wp [O][T][Cs]; mode 0: forward [O][T][csw]; mode 1: data gradient [Cs][T][csw];
-// modes 2 / 3: their Winograd F(2,3) planes (T = 9 -> 12 taps per row) for scan_conv3x3_wino_bf16x6
-Planes split3_uncached(const at::Tensor& wp, int mode, int64_t cs_src);
-Planes split3(const at::Tensor& wp, int mode, int64_t cs_src, const at::Tensor& owner = at::Tensor()) {
+// the three bf16 planes of packed weights wp [O][T][Cs] that `plan` reads (scan_conv_weight_split)
+Planes split3_uncached(const at::Tensor& wp, const scan_conv_plan_t& plan) {
+  Planes pl;
+  for (auto& q : pl.p) q = at::empty({plan.plane_rows, plan.plane_taps, plan.csw}, wp.options().dtype(at::kBFloat16));
+  check(scan_conv_weight_split(&plan, wp.data_ptr<float>(), pl.p[0].data_ptr(), pl.p[1].data_ptr(), pl.p[2].data_ptr(), cur_stream(wp)),
+        "scan_conv_weight_split");
+  return pl;
+}
+Planes split3(const at::Tensor& wp, const scan_conv_plan_t& plan, const at::Tensor& owner = at::Tensor()) {
   // owner: defined when wp is a VIEW of the weight tensor (pack_weight of a channels_last weight with C % 4 == 0: shares its storage
   // and its version counter) -- only then does the cache apply; a packed COPY is a fresh temporary every call
-  if (!owner.defined() || owner.data_ptr() != wp.data_ptr()) return split3_uncached(wp, mode, cs_src);
-  const auto key = std::make_pair((const void*)wp.data_ptr(), mode);
+  if (!owner.defined() || owner.data_ptr() != wp.data_ptr()) return split3_uncached(wp, plan);
+  const auto key = std::make_pair((const void*)wp.data_ptr(), (int)plan.split_mode);
   void* st = cur_stream(wp);
   auto& cache = plane_cache();
   auto it = cache.find(key);
   if (it != cache.end()) {
     const PlaneEntry& e = it->second;
     if (e.version == owner._version() && e.epoch == g_plane_epoch && e.stream == st && e.o == wp.size(0) && e.t == wp.size(1) &&
-        e.cs == wp.size(2))
+        e.cs == wp.size(2) && e.pl.p[0].size(2) == plan.csw)
       return e.pl;
   }
   if (cache.size() > 512) cache.clear();
-  PlaneEntry e{wp, owner._version(), g_plane_epoch, st, wp.size(0), wp.size(1), wp.size(2), split3_uncached(wp, mode, cs_src)};
+  PlaneEntry e{wp, owner._version(), g_plane_epoch, st, wp.size(0), wp.size(1), wp.size(2), split3_uncached(wp, plan)};
   cache[key] = e;
   return e.pl;
 }
-Planes split3_uncached(const at::Tensor& wp, int mode, int64_t cs_src) {
-  const int64_t o = wp.size(0), t = wp.size(1), cs = wp.size(2);
-  const int64_t rnd = t == 9 ? 32 : 8;  // 3x3: whole 32-channel K chunks (LDS-DMA weight tiles); 1x1: 8-element granule
-  Planes pl;
-  const int64_t rows = (mode & 1) == 0 ? o : cs;
-  pl.csw = round_up((mode & 1) == 0 ? cs : std::max(o, cs_src), rnd);
-  for (auto& q : pl.p) q = at::empty({rows, mode >= 2 ? 12 : t, pl.csw}, wp.options().dtype(at::kBFloat16));
-  check(scan_weight_split3(wp.data_ptr<float>(), (int32_t)o, (int32_t)t, (int32_t)cs, mode, pl.p[0].data_ptr(), pl.p[1].data_ptr(),
-                           pl.p[2].data_ptr(), (int32_t)pl.csw, cur_stream(wp)),
-        "scan_weight_split3");
-  return pl;
+
+// plan -> planes (cached) -> one scan_conv_run: y rows [.., Ns] of a conv reading x rows [.., Cs]
+void conv_run(const scan_conv_plan_t& plan, const at::Tensor& wp, const at::Tensor& owner, const at::Tensor& x, const scan_pyramid_t& xd,
+              int64_t cs, const at::Tensor& bias, at::Tensor& y, const scan_pyramid_t& yd, int64_t ns, bool relu, int map,
+              const at::Tensor& gn_sums) {
+  const Planes pl = split3(wp, plan, owner);
+  check(scan_conv_run(&plan, x.data_ptr<float>(), &xd, (int32_t)cs, pl.p[0].data_ptr(), pl.p[1].data_ptr(), pl.p[2].data_ptr(),
+                      bias.defined() ? bias.data_ptr<float>() : nullptr, nullptr, y.data_ptr<float>(), &yd, (int32_t)ns, relu ? 1 : 0, map,
+                      gn_sums.defined() ? reinterpret_cast<float*>(gn_sums.data_ptr()) : nullptr, 1, cur_stream(x)),
+        "scan_conv_run");
 }
 
 const float* opt_ptr(const at::Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; }
@@ -182,33 +193,9 @@ at::Tensor conv_rows_forward(const at::Tensor& xr, const at::Tensor& wp, const a
           "scan_conv_smallcin_bf16x6");
     return y;
   }
-  // the Winograd instance takes the launches scan_amd.ops gives it (same planes, same kernel: bit-identical to the Python path)
-  if (g.k == 3 && scan_conv3x3_bf16x6_wino((int32_t)g.cout, (int32_t)round_up(g.cs, 32))) {
-    const Planes pl = split3(wp, 2, g.cs, owner);
-    check(scan_conv3x3_wino_bf16x6(xr.data_ptr<float>(), &xd, (int32_t)g.cs, pl.p[0].data_ptr(), pl.p[1].data_ptr(), pl.p[2].data_ptr(),
-                                   (int32_t)pl.csw, opt_ptr(bias), nullptr, y.data_ptr<float>(), (int32_t)g.cout, (int32_t)g.ns,
-                                   relu ? 1 : 0, gn_sums.defined() ? reinterpret_cast<float*>(gn_sums.data_ptr()) : nullptr, 1, st),
-          "scan_conv3x3_wino_bf16x6");
-    return y;
-  }
-  const Planes pl = split3(wp, 0, g.cs, owner);
-  if (g.k == 3) {
-    if (gn_sums.defined())
-      check(scan_conv3x3_gn_bf16x6(xr.data_ptr<float>(), &xd, (int32_t)g.cs, pl.p[0].data_ptr(), pl.p[1].data_ptr(), pl.p[2].data_ptr(),
-                                   (int32_t)pl.csw, opt_ptr(bias), y.data_ptr<float>(), (int32_t)g.cout, (int32_t)g.ns,
-                                   reinterpret_cast<float*>(gn_sums.data_ptr()), 1, st),
-            "scan_conv3x3_gn_bf16x6");
-    else
-      check(scan_conv3x3_bf16x6(xr.data_ptr<float>(), &xd, (int32_t)g.cs, pl.p[0].data_ptr(), pl.p[1].data_ptr(), pl.p[2].data_ptr(),
-                                (int32_t)pl.csw, opt_ptr(bias), nullptr, y.data_ptr<float>(), (int32_t)g.cout, (int32_t)g.ns,
-                                relu ? 1 : 0, st),
-            "scan_conv3x3_bf16x6");
-  } else {
-    check(scan_conv1x1_bf16x6(xr.data_ptr<float>(), &xd, (int32_t)g.cs, pl.p[0].data_ptr(), pl.p[1].data_ptr(), pl.p[2].data_ptr(),
-                              (int32_t)pl.csw, opt_ptr(bias), nullptr, y.data_ptr<float>(), &yd, (int32_t)g.cout, (int32_t)g.ns,
-                              relu ? 1 : 0, g.stride == 2 ? 1 : 0, st),
-          "scan_conv1x1_bf16x6");
-  }
+  // 3x3 / stride 1 and 1x1: Winograd, direct or 1x1 kernel as the library plans it (the launches scan_amd.ops makes: bit-identical)
+  conv_run(conv_plan(g.k * g.k, false, g.cout, g.cs, g.cs, yd, gn_sums.defined() ? SCAN_CONV_SUMS : 0), wp, owner, xr, xd, g.cs, bias, y, yd,
+           g.ns, relu, g.stride == 2 ? 1 : 0, gn_sums);
   return y;
 }
 
@@ -229,23 +216,9 @@ std::vector<at::Tensor> conv_rows_backward(const at::Tensor& xr, const at::Tenso
                               (int32_t)g.cs, 3, 2, nullptr, st),
             "scan_conv2d_dgrad");
     } else {
-      const bool wino = g.k == 3 && scan_conv3x3_bf16x6_wino((int32_t)g.cs, (int32_t)round_up(std::max(g.cout, g.ns), 32));
       // flipped + transposed planes: the data gradient is the forward kernel on dY
-      const Planes pl = split3(wp, wino ? 3 : 1, g.ns, owner);
-      if (wino)
-        check(scan_conv3x3_wino_bf16x6(dyr.data_ptr<float>(), &yd, (int32_t)g.ns, pl.p[0].data_ptr(), pl.p[1].data_ptr(), pl.p[2].data_ptr(),
-                                       (int32_t)pl.csw, nullptr, nullptr, dx.data_ptr<float>(), (int32_t)g.cs, (int32_t)g.cs, 0, nullptr, 0,
-                                       st),
-              "scan_conv3x3_wino_bf16x6 (data gradient)");
-      else if (g.k == 3)
-        check(scan_conv3x3_bf16x6(dyr.data_ptr<float>(), &yd, (int32_t)g.ns, pl.p[0].data_ptr(), pl.p[1].data_ptr(), pl.p[2].data_ptr(),
-                                  (int32_t)pl.csw, nullptr, nullptr, dx.data_ptr<float>(), (int32_t)g.cs, (int32_t)g.cs, 0, st),
-              "scan_conv3x3_bf16x6 (data gradient)");
-      else
-        check(scan_conv1x1_bf16x6(dyr.data_ptr<float>(), &yd, (int32_t)g.ns, pl.p[0].data_ptr(), pl.p[1].data_ptr(), pl.p[2].data_ptr(),
-                                  (int32_t)pl.csw, nullptr, nullptr, dx.data_ptr<float>(), &xd, (int32_t)g.cs, (int32_t)g.cs, 0,
-                                  g.stride == 2 ? 2 : 0, st),
-              "scan_conv1x1_bf16x6 (data gradient)");
+      conv_run(conv_plan(T, true, g.cout, g.cs, g.ns, xd, 0), wp, owner, dyr, yd, g.ns, at::Tensor(), dx, xd, g.cs, false,
+               g.stride == 2 ? 2 : 0, at::Tensor());
     }
   }
   if (need_dw || need_db) {

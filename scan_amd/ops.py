@@ -399,24 +399,16 @@ def _conv_split(x, shape, wp, cout, rows_out, cs_src, mode, bias, relu, ns, name
     scan_conv1x1_*'s map).  mode 0: forward (Nout = O); mode 1: dgrad (Nout = Cs_w)."""
     st = _stream()
     npc = pieces or split_pieces()
-    sfx = "bf16x6" if npc == 3 else "bf16x3"
     O, T, cs_w = wp.shape
-    # plane rows are zero-padded to whole 32-channel K chunks for the 3x3 kernels: the LDS-DMA weight path needs whole
-    # chunks (a 264-channel input then takes it too); 1x1 planes keep the 8-element granule
-    rnd = _round32 if T == 9 else _round8
-    if mode == 0:
-        rows, csw, nout = O, rnd(cs_w), O
-    else:
-        rows, csw, nout = cs_w, rnd(max(O, cs_src)), cs_w
-    # a 3x3 launch whose Nout is 128-wide tiles plus a <= 64-channel remainder splits in two (below)
-    rem = nout % 128
-    split_rem = T == 9 and not gn_sums and not pool and nout > 128 and 0 < rem <= 64 and cs_src >= 512 and rows_out >= 100000
-    # the Winograd F(2,3) kernel (scan_tune conv_wino) reads planes of its own: split modes 2 / 3, 12 taps per row
-    wino = npc == 3 and T == 9 and not split_rem and query("scan_conv3x3_bf16x6_wino", nout, csw) == 1
-    smode, TP = (mode + 2, 12) if wino else (mode, T)
+    # planes, kernel family and launch cut come from the library (scan_conv_plan, include/scan_hip.h): the compiled operators
+    # (csrc/scan_ops_ext.cpp) ask the same function
+    plan = _lib.ConvPlan()
+    call("scan_conv_plan", npc, T, mode, O, cs_w, cs_src, (dst_shape or shape).ref(),
+         (_lib.CONV_SUMS if gn_sums else 0) | (_lib.CONV_POOL if pool else 0), ctypes.byref(plan))
+    smode, csw, rows, TP, nout = plan.split_mode, plan.csw, plan.plane_rows, plan.plane_taps, plan.nout
+    key = (cache_key, smode, csw, npc)
     hit = None
     if cache_key is not None and SPLIT_EPOCH is not None:
-        key = (cache_key, smode, csw, npc)
         hit = _split_cache.get(key)
         if hit is not None and (hit[0] != SPLIT_EPOCH or tuple(hit[1][0].shape) != (rows, TP, csw)):
             hit = None
@@ -426,72 +418,25 @@ def _conv_split(x, shape, wp, cout, rows_out, cs_src, mode, bias, relu, ns, name
         torch.cuda.current_stream().wait_event(hit[2])
     else:
         planes = tuple(torch.empty((rows, TP, csw), dtype=torch.bfloat16, device=x.device) for _ in range(npc))
-        if npc == 3:
-            call("scan_weight_split3", _ptr(wp), O, T, cs_w, smode, _ptr(planes[0]), _ptr(planes[1]), _ptr(planes[2]), csw, st)
-        else:
-            call("scan_weight_split", _ptr(wp), O, T, cs_w, mode, _ptr(planes[0]), _ptr(planes[1]), csw, st)
+        call("scan_conv_weight_split", ctypes.byref(plan), _ptr(wp), *[_ptr(t) for t in planes], *[None] * (3 - npc), st)
         if cache_key is not None and SPLIT_EPOCH is not None:
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream())
-            _split_cache[(cache_key, smode, csw, npc)] = (SPLIT_EPOCH, planes, ev)
+            _split_cache[key] = (SPLIT_EPOCH, planes, ev)
             if _active_plan is not None and param is not None and wp.data_ptr() == cache_key == param.data_ptr():
-                _active_plan.add((cache_key, smode, csw, npc), param, O, T, cs_w, smode, rows, csw, planes)
-    wptrs = [_ptr(t) for t in planes]
+                _active_plan.add(key, param, O, T, cs_w, smode, rows, csw, planes)
     y = out if out is not None else (x.new_zeros if ns != nout else x.new_empty)((rows_out, ns))
-    if kernel_timer.enabled:  # label the record with the template instance the launch takes (64 / 128 / 256 channels)
-        if wino:  # 3128: the Winograd instance (128-channel tile); its roofline counts direct-conv FLOPs
-            inst = 3128
-        elif T == 9:
-            inst = query("scan_conv3x3_%s_instance" % sfx, (dst_shape or shape).ref(), nout)
-        elif npc == 3:
-            inst = query("scan_conv1x1_bf16x6_instance", (dst_shape or shape).ref(), nout, csw)
-        else:
-            inst = 128 if nout > 64 else 64
-        ev = kernel_timer.begin("%s_bn%d" % (name, inst), flops)
-    else:
-        ev = None
-    if wino:
-        if gn_sums:
-            sums, cleared = _ws_f64(shape.n_levels * shape.n_images * 32 * 2, x.device)
-            _gn_sums.clear()
-            _gn_sums[y.data_ptr()] = sums
-        call("scan_conv3x3_wino_bf16x6", _ptr(x), shape.ref(), cs_src, *wptrs, csw, _ptr(bias), _ptr(mask), _ptr(y), nout, ns,
-             int(bool(relu)) | (2 if pool else 0), _ptr(sums) if gn_sums else None, 0 if not gn_sums or cleared else 1, st)
-    elif gn_sums:
+    # the record carries the template instance the launch takes (64 / 128 / 256 channels; 3128: the Winograd instance, whose
+    # roofline counts direct-conv FLOPs)
+    ev = kernel_timer.begin("%s_bn%d" % (name, plan.instance), flops) if kernel_timer.enabled else None
+    sums, cleared = (None, True)
+    if gn_sums:
         sums, cleared = _ws_f64(shape.n_levels * shape.n_images * 32 * 2, x.device)
-        if npc == 3:
-            call("scan_conv3x3_gn_bf16x6", _ptr(x), shape.ref(), cs_src, *wptrs, csw, _ptr(bias), _ptr(y), nout, ns,
-                 _ptr(sums), 0 if cleared else 1, st)
-        else:
-            call("scan_conv3x3_gn_acc_bf16x3" if cleared else "scan_conv3x3_gn_bf16x3", _ptr(x), shape.ref(), cs_src, *wptrs, csw,
-                 _ptr(bias), _ptr(y), nout, ns, _ptr(sums), st)
         _gn_sums.clear()  # at most one pending hand-over: conv and its GroupNorm are adjacent calls of one thread
         _gn_sums[y.data_ptr()] = sums
-    elif pool:
-        call("scan_conv3x3_pool2_" + sfx, _ptr(x), shape.ref(), cs_src, *wptrs, csw, _ptr(bias), _ptr(y),
-             nout, ns, int(bool(relu)), st)
-    elif T == 1:
-        call("scan_conv1x1_" + sfx, _ptr(x), shape.ref(), cs_src, *wptrs, csw, _ptr(bias), _ptr(mask),
-             _ptr(y), (dst_shape or shape).ref(), nout, ns, int(bool(relu)), cmap, st)
-    else:
-        fn = "scan_conv3x3_" + sfx
-        if split_rem:
-            # 128-wide output tiles plus a small remainder (data gradient of the 264-channel discriminator input at
-            # P3, K = 1024): the remainder columns go through the 64-channel instance instead of a third, almost empty
-            # 128-wide tile (2022 -> 1794 us).  With a short K loop or few rows the extra launch costs more than the
-            # empty tile (265-channel head_out input: 614 -> 721 us), hence the size test.
-            main = nout - rem
-
-            def off(t, nbytes):
-                return ctypes.c_void_p(t.data_ptr() + nbytes) if t is not None else ctypes.c_void_p(0)
-
-            call(fn, _ptr(x), shape.ref(), cs_src, *wptrs, csw, _ptr(bias), _ptr(mask), _ptr(y), main, ns,
-                 int(bool(relu)), st)
-            call(fn, _ptr(x), shape.ref(), cs_src, *[off(t, main * T * csw * 2) for t in planes], csw, off(bias, main * 4),
-                 off(mask, main * 4), off(y, main * 4), rem, ns, int(bool(relu)), st)
-        else:
-            call(fn, _ptr(x), shape.ref(), cs_src, *wptrs, csw, _ptr(bias), _ptr(mask), _ptr(y), nout, ns,
-                 int(bool(relu)), st)
+    call("scan_conv_run", ctypes.byref(plan), _ptr(x), shape.ref(), cs_src, *[_ptr(t) for t in planes], *[None] * (3 - npc),
+         _ptr(bias), _ptr(mask), _ptr(y), (dst_shape or shape).ref(), ns, int(bool(relu)), cmap, _ptr(sums),
+         0 if cleared else 1, st)
     kernel_timer.end(ev)
     return y
 
@@ -607,54 +552,44 @@ class _Conv2d(torch.autograd.Function):
             kernel_timer.end(ev)
         direct_w = ctx.wgrad_buf is not None
         direct_b = direct_w and ctx.bgrad_buf is not None
+        want_db = has_bias and ctx.needs_input_grad[2]
         db_done = False
+
+        def wgrad(sym, label, ws_floats, geom, fused_db):
+            """one weight-gradient launch on the current stream: dw (and db, where the kernel fuses the column sums of dy)
+            straight into the flat gradient buffers or into fresh tensors -> dw for autograd (None when accumulated in place)"""
+            nonlocal db, db_done
+            ws = x.new_empty((ws_floats,))
+            dwp = ctx.wgrad_buf if direct_w else x.new_empty((cout, T, cs))
+            ev = kernel_timer.begin(label, 2.0 * oshape.rows * cout * T * cin)
+            if fused_db and want_db:
+                db = ctx.bgrad_buf if direct_b else x.new_empty((cout,))
+                db_done = True
+            call(sym, _ptr(x), shape.ref(), cs, _ptr(dy), *geom, _ptr(dwp), *([_ptr(db) if want_db else None] if fused_db else []),
+                 int(direct_w), _ptr(ws), _stream())
+            kernel_timer.end(ev)
+            if fused_db and want_db and direct_w and not direct_b:
+                raise RuntimeError("conv2d: flat weight gradient without a flat bias gradient")
+            if direct_b:
+                db = None
+            return None if direct_w else unpack_weight_grad(dwp, weight)
+
         if ctx.needs_input_grad[1] and fast and ksize == 3:
-            want_db = has_bias and ctx.needs_input_grad[2]
             side = WGRAD_STREAM if (direct_w and (direct_b or not want_db) and not kernel_timer.enabled) else None
             if side is not None:  # in place into the flat gradient buffers, nothing returned to autograd: off the chain
                 side.wait_stream(torch.cuda.current_stream())
                 x.record_stream(side)
                 dy.record_stream(side)
             with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
-                ws = x.new_empty((query("scan_conv3x3_wgrad_%s_ws_floats" % sfx, shape.ref(), cs, cout),))
-                dwp = ctx.wgrad_buf if direct_w else x.new_empty((cout, T, cs))
-                ev = kernel_timer.begin("conv3x3_%s_wgrad" % sfx, 2.0 * oshape.rows * cout * T * cin)
-                if want_db:
-                    db = ctx.bgrad_buf if direct_b else x.new_empty((cout,))
-                    db_done = True
-                call("scan_conv3x3_wgrad_" + sfx, _ptr(x), shape.ref(), cs, _ptr(dy), cout, cout_s, _ptr(dwp),
-                     _ptr(db) if want_db else None, int(direct_w), _ptr(ws), _stream())
-                kernel_timer.end(ev)
-            if want_db and direct_w and not direct_b:
-                raise RuntimeError("conv2d: flat weight gradient without a flat bias gradient")
-            dw = None if direct_w else unpack_weight_grad(dwp, weight)
-            if direct_b:
-                db = None
+                dw = wgrad("scan_conv3x3_wgrad_" + sfx, "conv3x3_%s_wgrad" % sfx,
+                           query("scan_conv3x3_wgrad_%s_ws_floats" % sfx, shape.ref(), cs, cout), (cout, cout_s), True)
         elif ctx.needs_input_grad[1] and fast:  # 1x1, stride 1 or 2
-            ws = x.new_empty((query("scan_conv1x1_wgrad_%s_ws_floats" % sfx, oshape.ref(), cs, cout),))
-            dwp = ctx.wgrad_buf if direct_w else x.new_empty((cout, T, cs))
-            ev = kernel_timer.begin("conv1x1_%s_wgrad" % sfx, 2.0 * oshape.rows * cout * T * cin)
-            want_db = has_bias and ctx.needs_input_grad[2]
-            if want_db:
-                db = ctx.bgrad_buf if direct_b else x.new_empty((cout,))
-                db_done = True
-            call("scan_conv1x1_wgrad_" + sfx, _ptr(x), shape.ref(), cs, _ptr(dy), oshape.ref(), cout, cout_s, stride,
-                 _ptr(dwp), _ptr(db) if want_db else None, int(direct_w), _ptr(ws), st)
-            kernel_timer.end(ev)
-            if want_db and direct_w and not direct_b:
-                raise RuntimeError("conv2d: flat weight gradient without a flat bias gradient")
-            dw = None if direct_w else unpack_weight_grad(dwp, weight)
-            if direct_b:
-                db = None
+            dw = wgrad("scan_conv1x1_wgrad_" + sfx, "conv1x1_%s_wgrad" % sfx,
+                       query("scan_conv1x1_wgrad_%s_ws_floats" % sfx, oshape.ref(), cs, cout),
+                       (oshape.ref(), cout, cout_s, stride), True)
         elif ctx.needs_input_grad[1]:
-            n = query("scan_conv2d_wgrad_ws_floats", oshape.ref(), cs, cout, ksize)
-            ws = x.new_empty((n,))
-            dwp = ctx.wgrad_buf if direct_w else x.new_empty((cout, T, cs))
-            ev = kernel_timer.begin("conv_wgrad", 2.0 * oshape.rows * cout * T * cin)
-            call("scan_conv2d_wgrad", _ptr(x), shape.ref(), cs, _ptr(dy), oshape.ref(), cout, cout_s, ksize, stride,
-                 _ptr(dwp), int(direct_w), _ptr(ws), st)
-            kernel_timer.end(ev)
-            dw = None if direct_w else unpack_weight_grad(dwp, weight)
+            dw = wgrad("scan_conv2d_wgrad", "conv_wgrad", query("scan_conv2d_wgrad_ws_floats", oshape.ref(), cs, cout, ksize),
+                       (oshape.ref(), cout, cout_s, ksize, stride), False)
         if has_bias and ctx.needs_input_grad[2] and not db_done:
             M = dy.shape[0]
             ws = x.new_empty((query("scan_colsum_ws_floats", M, cout),))

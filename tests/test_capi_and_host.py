@@ -38,6 +38,41 @@ def test_argument_validation_without_device():
         _lib.call("scan_nms", None, None, None, _lib.NMS_MAX + 1, 0.5, 1, None, ctypes.c_void_p(8), None, None)
     with pytest.raises(RuntimeError, match="K in"):
         _lib.call("scan_dynconv_softmax_forward", None, None, 10, 256, 5, None, None, None)
+    # the conv dispatcher: everything is refused before a device is touched (the pointers below are never dereferenced)
+    L, fake = _lib.lib(), ctypes.c_void_p(4096)
+    two = ops.PyramidShape(2, [(12, 20), (6, 10)])
+
+    def plan(O, cs, flags=0, pieces=3, pyr=two):
+        p = _lib.ConvPlan()
+        _lib.call("scan_conv_plan", pieces, 9, 0, O, cs, cs, pyr.ref(), flags, ctypes.byref(p))
+        return p
+
+    def run(p, p2=fake, gn_ws=None, pyr=two):
+        return L.scan_conv_run(ctypes.byref(p) if p is not None else None, fake, pyr.ref(), 36, fake, fake, p2, None, None, fake,
+                               pyr.ref(), 256, 0, 0, gn_ws, 1, None)
+
+    def refused(rc, text):
+        assert rc == -1 and re.search(text, L.scan_last_error().decode()), (rc, L.scan_last_error())
+
+    refused(run(None), "null plan")
+    refused(L.scan_conv_weight_split(None, fake, fake, fake, fake, None), "null plan")
+    refused(run(plan(72, 36), p2=None), "null pointer")
+    refused(L.scan_conv_weight_split(ctypes.byref(plan(72, 36)), fake, fake, fake, None, None), "weight_split: bad arguments")
+    assert L.scan_conv_plan(3, 9, 0, 72, 36, 36, two.ref(), 3, ctypes.byref(_lib.ConvPlan())) == -1  # sums AND pool
+    assert L.scan_conv_plan(3, 9, 0, 72, 36, 36, two.ref(), 0, None) == -1
+    old = L.scan_tune(b"conv_wino", 1)
+    try:
+        for wino in (1, 0):  # sums need the 256 channels of GroupNorm(32, 256), on the Winograd and on the direct kernel
+            L.scan_tune(b"conv_wino", wino)
+            p = plan(128, 36, _lib.CONV_SUMS)
+            assert p.family == wino
+            refused(run(p, gn_ws=fake), "Nout == 256")
+            refused(run(plan(256, 36, _lib.CONV_SUMS)), "workspace")  # planned with sums, run without a workspace
+            refused(run(plan(256, 36), gn_ws=fake), "workspace")
+            refused(run(plan(72, 36, _lib.CONV_POOL)), "single-level pyramid")  # the fused pool on a two-level pyramid
+            refused(run(plan(72, 36, _lib.CONV_POOL, pieces=2), p2=None), "single-level pyramid")
+    finally:
+        L.scan_tune(b"conv_wino", old)
     assert _lib.query("scan_nms_ws_bytes", _lib.NMS_MAX + 1) == -1
     assert _lib.query("scan_nms_ws_bytes", 100) > 0
     # beyond one panel the mask is n x ceil(n / 64) words (the reference's own size, csrc/cuda/nms.cu:95-100) + sort keys
@@ -609,3 +644,63 @@ def test_conv_instance_queries_match_recorded(gold_dir):
         assert len(got[q]["index"]) == len(g["index"]) == 864
         for i, (a, b) in enumerate(zip(got[q]["index"], g["index"])):
             assert got[q]["rows"][a] == g["rows"][b], (q, "knob setting %d" % i)
+
+
+def _frozen_conv_plan_rules(L, npc, T, mode, O, cs_w, cs_src, od, gn_sums, pool):
+    """FROZEN -- do not edit with the library: the rules of ops._conv_split as they stood (commit a0f27ea, scan_amd/ops.py lines
+    401-416 and 441-450) before they moved into scan_conv_plan, restated on the pinned queries alone.  od: output pyramid."""
+    def rnd(c):
+        return (c + 31) // 32 * 32 if T == 9 else (c + 7) // 8 * 8
+    sfx = "bf16x6" if npc == 3 else "bf16x3"
+    rows_out = od.rows
+    if mode == 0:
+        rows, csw, nout = O, rnd(cs_w), O
+    else:
+        rows, csw, nout = cs_w, rnd(max(O, cs_src)), cs_w
+    rem = nout % 128
+    split_rem = T == 9 and not gn_sums and not pool and nout > 128 and 0 < rem <= 64 and cs_src >= 512 and rows_out >= 100000
+    wino = npc == 3 and T == 9 and not split_rem and L.scan_conv3x3_bf16x6_wino(nout, csw) == 1
+    smode, TP = (mode + 2, 12) if wino else (mode, T)
+    if wino:
+        inst = 3128
+    elif T == 9:
+        inst = getattr(L, "scan_conv3x3_%s_instance" % sfx)(od.ref(), nout)
+    elif npc == 3:
+        inst = L.scan_conv1x1_bf16x6_instance(od.ref(), nout, csw)
+    else:
+        inst = 128 if nout > 64 else 64
+    return {"pieces": npc, "taps": T, "dgrad": mode, "O": O, "Cs_w": cs_w, "split_mode": smode, "plane_rows": rows, "plane_taps": TP,
+            "csw": csw, "nout": nout, "rem": rem if split_rem else 0, "family": 1 if wino else 0 if T == 9 else 2, "instance": inst,
+            "flags": (1 if gn_sums else 0) | (2 if pool else 0)}
+
+
+def test_conv_plan_equals_frozen_rules():
+    """scan_conv_plan (csrc/conv_api.hip), field by field, against the frozen restatement above: pieces, taps, direction, flags,
+    conv_wino, pyramids on both sides of the 100,000-row threshold of the remainder rule, channel counts on both sides of its
+    Cs_src >= 512 threshold.  Host-only: no device is touched."""
+    import itertools
+    L = _lib.lib()
+    # the query grid's pyramids (the five-level ones have 40,960 and 44,800 rows, (4, [(128, 256)]) 131,072) plus the
+    # discriminator-P3 size of 100,352 rows and one just below the threshold (99,904)
+    pyr = [ops.PyramidShape(n, sizes) for n, sizes in _INSTANCE_PYRAMIDS + [(1, [(224, 448)]), (1, [(223, 448)])]]
+    assert sorted(p.rows for p in pyr)[-3:] == [99904, 100352, 131072]
+    nouts, css = (1, 8, 64, 65, 72, 128, 256, 264, 320, 321, 1024), (4, 36, 264, 512)
+    fields = [n for n, _ in _lib.ConvPlan._fields_]
+    seen = set()  # (rem > 0, rows >= 100000, Cs_src >= 512) among the 3x3 launches without flags whose Nout leaves a remainder
+    old = L.scan_tune_get(b"conv_wino")
+    try:
+        for wino, npc, T, mode, flags, od, nout, cs in itertools.product((0, 1), (2, 3), (9, 1), (0, 1), (0, 1, 2), pyr, nouts, css):
+            L.scan_tune(b"conv_wino", wino)
+            # forward: Cs channels in, Nout out; data gradient of a conv with Nout input and Cs output channels (dY padded to 4)
+            O, cs_w, cs_src = (nout, cs, cs) if mode == 0 else (cs, nout, (cs + 3) // 4 * 4)
+            plan = _lib.ConvPlan()
+            assert L.scan_conv_plan(npc, T, mode, O, cs_w, cs_src, od.ref(), flags, ctypes.byref(plan)) == 0, L.scan_last_error()
+            want = _frozen_conv_plan_rules(L, npc, T, mode, O, cs_w, cs_src, od, flags == 1, flags == 2)
+            got = {f: getattr(plan, f) for f in fields}
+            assert got == want, (wino, npc, T, mode, flags, od.sizes, nout, cs, got, want)
+            if T == 9 and flags == 0 and nout in (264, 320):
+                seen.add((plan.rem > 0, od.rows >= 100000, cs_src >= 512))
+                assert plan.rem in (0, nout % 128) and (plan.rem == 0 or plan.family == 0)
+    finally:
+        L.scan_tune(b"conv_wino", old)
+    assert seen == {(True, True, True), (False, False, True), (False, True, False), (False, False, False)}

@@ -1127,29 +1127,32 @@ def test_conv_relu_pool_fused(device, cin, cout, hw):
 
 
 def test_dgrad_remainder_split_full_size(device):
-    """data gradient of a 264-channel input at discriminator-P3 size (K = 512, M = 100,352): the 8 remainder output
-    channels run as a second launch of the 64-channel instance (ops._conv_split); result must equal the
-    independent fp32-MFMA kernel."""
+    """data gradient of a 264-channel input at discriminator-P3 size (K = 512, M = 100,352): the library plans the 8 remainder
+    output channels as a second launch of the 64-channel instance (scan_conv_plan: rem = 8 after a 256-channel main part) and
+    scan_conv_run makes exactly those two launches -- the result equals, bit for bit, two hand-made scan_conv3x3_bf16x6 calls
+    on hand-split mode-1 planes, and agrees with the independent fp32-MFMA kernel."""
+    import ctypes
     from scan_amd import _lib, ops
     g = torch.Generator().manual_seed(77)
     shape = ops.PyramidShape(1, [(224, 448)])
     x = torch.randn(shape.rows, 264, generator=g).to(device).requires_grad_(True)
     w = (torch.randn(512, 264, 3, 3, generator=g) / (264 * 9) ** 0.5).to(device).contiguous(memory_format=torch.channels_last)
     gy = torch.randn(shape.rows, 512, generator=g).to(device)
-    calls = []
-    orig = ops.call
-
-    def spy(name, *a):
-        if name == "scan_conv3x3_bf16x6":
-            calls.append(a[10])  # Nout
-        return orig(name, *a)
-
-    ops.call = spy
-    try:
-        ops.conv2d(x, w, None, shape, 3, 1).backward(gy)
-    finally:
-        ops.call = orig
-    assert 256 in calls and 8 in calls, calls  # main (2 x 128) + remainder launch
+    assert ops.split_pieces() == 3
+    plan = _lib.ConvPlan()
+    _lib.call("scan_conv_plan", 3, 9, 1, 512, 264, 512, shape.ref(), 0, ctypes.byref(plan))
+    assert (plan.rem, plan.nout - plan.rem, plan.family, plan.split_mode, plan.plane_taps, plan.csw) == (8, 256, 0, 1, 9, 512)
+    ops.conv2d(x, w, None, shape, 3, 1).backward(gy)
+    # by hand: flipped + transposed planes [264][9][512], Nout 256 from their start, Nout 8 from row 256 on into column 256 on
+    wp = ops.pack_weight(w, 264)
+    planes = [torch.empty((264, 9, 512), dtype=torch.bfloat16, device=device) for _ in range(3)]
+    vp = ctypes.c_void_p
+    _lib.call("scan_weight_split3", vp(wp.data_ptr()), 512, 9, 264, 1, *[vp(t.data_ptr()) for t in planes], 512, None)
+    hand = torch.empty((shape.rows, 264), device=device)
+    for nout, first in ((256, 0), (8, 256)):
+        _lib.call("scan_conv3x3_bf16x6", vp(gy.data_ptr()), shape.ref(), 512, *[vp(t.data_ptr() + first * 9 * 512 * 2) for t in planes],
+                  512, None, None, vp(hand.data_ptr() + first * 4), nout, 264, 0, None)
+    assert torch.equal(x.grad, hand)
     dx = x.grad.clone()
     x.grad = None
     keep = ops.CONV_MODE
