@@ -227,7 +227,10 @@ int scan_paradigm_update(float* P, const float* pb, int32_t K, int32_t C, int32_
 
 /* ---- semantic-conditioned dynamic 1x1 conv + channel softmax
  *      (replaces GRAPHModule.dynamic_conv + softmax, rpn/fcos/condgraph.py:619-629, 344-346) ----
- * feat [M,C] (C % 4 == 0), kernels [K,C] (K <= 16) -> logits [M,K], probs [M,K]. */
+ * feat [M,C] (C == 256), kernels [K,C] (2 <= K <= scan_dynconv_max_classes() = 32) -> logits [M,K], probs [M,K].
+ * K = 2 and K = 9 run kernels compiled for that K; every other K runs the generic ones (scan_tune "dynconv_generic" = 1:
+ * every K does).  A K outside the range is an argument error naming it; nothing is launched. */
+int32_t scan_dynconv_max_classes(void);
 int scan_dynconv_softmax_forward(const float* feat, const float* kernels, int64_t M, int32_t C, int32_t K,
                                  float* logits, float* probs, void* stream);
 /* d_logits_in [M,K] or NULL (grad arriving at the logits, e.g. from the act loss), d_probs [M,K] or NULL.
@@ -633,7 +636,9 @@ int scan_cka_unstack_grads(const scan_cka_branch_t* grads, int32_t Cf, int32_t C
  * arithmetic, HBM-bound (one read of x).  ws: scan_gconv3x3_to1_ws_floats floats.
  *   dgrad: dx[q][c] = sum_t dy[q - off(t)][g(c)] * w[g][t][c], multiplied by (mask[q][c] > 0) when mask != NULL (the
  *          deferred ReLU of the producer); wgrad: dw[g][t][g*128 + i] (diagonal blocks only; added to dw when
- *          accumulate != 0), deterministic. */
+ *          accumulate != 0), deterministic.
+ * These entry points take G = 1, 2, 4, 8 (kernels whose lane map is built on G * 32 dividing 256); the _any_ entry points
+ * below take every 1 <= G <= scan_gconv3x3_to1_max_groups() = 31. */
 int64_t scan_gconv3x3_to1_ws_floats(const scan_pyramid_t* d, int32_t G, int32_t Cg);
 int scan_gconv3x3_to1_forward(const float* x, const scan_pyramid_t* d, int32_t G, int32_t Cg, const float* w,
                               const float* bias, float* y, int32_t Ns, float* ws, void* stream);
@@ -645,6 +650,19 @@ int scan_gconv3x3_to1_wgrad(const float* x, const float* dy, int32_t Ns, const s
 int scan_gconv3x3_to1_backward(const float* x, const float* dy, int32_t Ns, const scan_pyramid_t* d, int32_t G, int32_t Cg,
                                const float* w, int32_t relu_mask, float* dx, float* dw, int32_t accumulate, float* ws,
                                void* stream);
+/* Any group count 1 <= G <= scan_gconv3x3_to1_max_groups() = 31, same arguments and results: G = 1, 2, 4, 8 run the kernels
+ * of the entry points above, every other G generic ones (one 32-lane half-wave per (pixel, group), plain fp32 FMA,
+ * deterministic weight gradient).  Workspace: scan_gconv3x3_to1_ws_floats. */
+int32_t scan_gconv3x3_to1_max_groups(void);
+int scan_gconv3x3_to1_any_forward(const float* x, const scan_pyramid_t* d, int32_t G, int32_t Cg, const float* w,
+                                  const float* bias, float* y, int32_t Ns, float* ws, void* stream);
+int scan_gconv3x3_to1_any_dgrad(const float* dy, int32_t Ns, const scan_pyramid_t* d, int32_t G, int32_t Cg, const float* w,
+                                const float* mask, float* dx, void* stream);
+int scan_gconv3x3_to1_any_wgrad(const float* x, const float* dy, int32_t Ns, const scan_pyramid_t* d, int32_t G, int32_t Cg,
+                                float* dw, int32_t accumulate, float* ws, void* stream);
+int scan_gconv3x3_to1_any_backward(const float* x, const float* dy, int32_t Ns, const scan_pyramid_t* d, int32_t G, int32_t Cg,
+                                   const float* w, int32_t relu_mask, float* dx, float* dw, int32_t accumulate, float* ws,
+                                   void* stream);
 /* forward that also leaves the ReLU mask of x as bits (relu_bits: M * G * 4 uint32; bit 4 j + e of word
  * [(row * G + g) * 4 + q] = x[row][g * 128 + 16 j + 4 q + e] > 0), and the backward that masks dx with them instead of
  * re-reading x for the mask. */

@@ -100,6 +100,7 @@ SIGNATURES = {
     "scan_paradigm_update": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "scan_dynconv_softmax_forward": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "scan_dynconv_ws_floats": (c_i64, [c_i64, c_i32, c_i32]),
+    "scan_dynconv_max_classes": (c_i32, []),
     "scan_dynconv_softmax_backward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "scan_softmax_focal_forward": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i32, c_f32, c_vp, c_vp]),
     "scan_softmax_focal_backward": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i32, c_f32, c_f32, c_vp, c_vp]),
@@ -176,6 +177,12 @@ SIGNATURES = {
     "scan_cka_unstack_grads": (ctypes.c_int, [ctypes.POINTER(CkaBranch), c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_i64,
                                               c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
     "scan_gconv3x3_to1_ws_floats": (c_i64, [_PD, c_i32, c_i32]),
+    "scan_gconv3x3_to1_max_groups": (c_i32, []),
+    "scan_gconv3x3_to1_any_forward": (ctypes.c_int, [c_vp, _PD, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "scan_gconv3x3_to1_any_dgrad": (ctypes.c_int, [c_vp, c_i32, _PD, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "scan_gconv3x3_to1_any_wgrad": (ctypes.c_int, [c_vp, c_vp, c_i32, _PD, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp]),
+    "scan_gconv3x3_to1_any_backward": (ctypes.c_int, [c_vp, c_vp, c_i32, _PD, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32,
+                                                      c_vp, c_vp]),
     "scan_gconv3x3_to1_forward": (ctypes.c_int, [c_vp, _PD, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "scan_gconv3x3_to1_dgrad": (ctypes.c_int, [c_vp, c_i32, _PD, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "scan_gconv3x3_to1_wgrad": (ctypes.c_int, [c_vp, c_vp, c_i32, _PD, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp]),

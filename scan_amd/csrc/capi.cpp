@@ -36,7 +36,7 @@ static Knob* knob_table(int* count) {
       {"wgrad_tile", &g_scan_wgrad_tile, 0},   {"wgrad_wgs", &g_scan_wgrad_wgs, 0},     {"gconv_mfma", &g_scan_gconv_mfma, 0},
       {"dbscan_bf16x3", &g_scan_dbscan_bf16x3, 0}, {"reduce_blocks", &g_scan_reduce_blocks, 0}, {"conv1x1", &g_scan_conv1x1, 0},
       {"conv_wino", &g_scan_conv_wino, 0},     {"wgrad_wino", &g_scan_wgrad_wino, 0},   {"wino_tpb", &g_scan_wino_tpb, 0},
-      {"deterministic", &g_scan_deterministic, 0},
+      {"deterministic", &g_scan_deterministic, 0}, {"dynconv_generic", &g_scan_dynconv_generic, 0},
   };
   static bool init = false;
   if (!init) {  // the values the library was built with: knobs are only ever written through scan_tune below

@@ -18,6 +18,7 @@ extern int g_scan_conv_glds, g_scan_conv_bn64_th16, g_scan_conv1x1;             
 extern int g_scan_conv_wino, g_scan_wino_tpb;                                           // conv_fwd.hip
 extern int g_scan_wgrad_v6, g_scan_wgrad_prio, g_scan_wgrad_tile, g_scan_wgrad_wgs, g_scan_wgrad_wino;  // conv_wgrad.hip
 extern int g_scan_gconv_mfma;                                                           // gconv.hip
+extern int g_scan_dynconv_generic;                                                      // dynconv.hip
 extern int g_scan_dbscan_bf16x3;                                                        // dbscan.hip
 extern int g_scan_reduce_blocks;                                                        // pointwise.hip
 

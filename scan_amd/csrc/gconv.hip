@@ -17,6 +17,15 @@
 // Weight layout: the stacked conv weight [G][9][G*128] (scan_cka_stack_weights' w2): only the diagonal blocks
 // w[g][t][g*128 + i] are read / written.  Lane map: thread t of 256 handles the channel quad t % (GC/4) of pixel slot
 // t / (GC/4), so 32 consecutive lanes = one group of 128 channels.
+//
+// Group counts.  That lane map needs G * 32 channel quads to divide 256 threads: G = 1, 2, 4, 8 (8 = the Cityscapes
+// foreground classes).  Every other 1 <= G <= 31 (GC_GMAX) runs the generic family (gconv_*_generic_kernel): half-wave
+// hw of the grid keeps group hw % G for its whole life (nine weight quads in registers, as above) and walks the pixels
+// hw / G, hw / G + J, ... -- the half-waves of one step read one contiguous stretch of x.  Same T layout (the gather
+// kernel serves both), same arithmetic per (pixel, group); the weight-gradient partials are one [9][128] block per
+// half-wave, summed in a fixed order.  The matrix-core / bit-mask variants exist for G = 1, 2, 4, 8 only.  The generic
+// family is reached through the scan_gconv3x3_to1_any_* entry points; the entry points without "any" keep refusing every
+// G outside {1, 2, 4, 8}, as their callers and tests expect.
 #include "common.h"
 
 #define GC_G 128  // channels per group
@@ -376,14 +385,157 @@ __global__ __launch_bounds__(256) void gconv_wgrad_reduce_kernel(const float* __
   *dst = accumulate ? *dst + s : s;
 }
 
+// ---- generic group count (any 1 <= G <= GC_GMAX): one 32-lane half-wave per (pixel, group) -------------------------------
+// The grid has J * G half-waves (J a multiple of 8, so J * G / 8 workgroups): half-wave hw serves group hw % G at the
+// pixels hw / G + i J.
+__global__ __launch_bounds__(256) void gconv_taps_generic_kernel(const float* __restrict__ x, int64_t M, int G, int GC,
+                                                                 const float* __restrict__ w, float* __restrict__ T) {
+  const int hw = blockIdx.x * 8 + (threadIdx.x >> 5), l32 = threadIdx.x & 31;
+  const int g = hw % G;
+  const int64_t J = (int64_t)gridDim.x * 8 / G;
+  const int64_t coff = (int64_t)g * GC_G + 4 * l32;
+  float4 wv[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t) wv[t] = *reinterpret_cast<const float4*>(w + ((int64_t)g * 9 + t) * GC + coff);
+  for (int64_t q0 = hw / G; q0 < M; q0 += GC_UNROLL_F * J) {
+    float4 h[GC_UNROLL_F];
+#pragma unroll
+    for (int u = 0; u < GC_UNROLL_F; ++u) {
+      const int64_t q = q0 + u * J;
+      h[u] = q < M ? *reinterpret_cast<const float4*>(x + q * GC + coff) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int u = 0; u < GC_UNROLL_F; ++u) {
+      const int64_t q = q0 + u * J;
+      float mine = 0.f;
+#pragma unroll
+      for (int t = 0; t < 9; ++t) {
+        float s = __fmaf_rn(h[u].x, wv[t].x, __fmaf_rn(h[u].y, wv[t].y, __fmaf_rn(h[u].z, wv[t].z, h[u].w * wv[t].w)));
+        s = half_wave_sum_hi(s);
+        if (l32 == 16 + t) mine = s;
+      }
+      if (q < M && l32 >= 16 && l32 < 25) T[(q * G + g) * 9 + (l32 - 16)] = mine;
+    }
+  }
+}
+
+// slab[hw][t][128]: half-wave hw's partial of dw[hw % G][t][..] = slab[j][(g * 9 + t) * 128 + i] with hw = j G + g, i.e.
+// J "blocks" of n = 9 * GC columns for gconv_slab_partial_kernel
+template <bool DO_DX, bool DO_DW>
+__global__ __launch_bounds__(256, 4) void gconv_bwd_generic_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+                                                                   int Ns, scan_pyramid_t d, int G, int GC,
+                                                                   const float* __restrict__ w, int relu_mask,
+                                                                   float* __restrict__ dx, float* __restrict__ slab) {
+  const int64_t M = d.row_off[d.n_levels];
+  const int hw = blockIdx.x * 8 + (threadIdx.x >> 5), l32 = threadIdx.x & 31;
+  const int g = hw % G;
+  const int64_t J = (int64_t)gridDim.x * 8 / G;
+  const int64_t coff = (int64_t)g * GC_G + 4 * l32;
+  float4 wv[9], acc[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t) {
+    wv[t] = DO_DX ? *reinterpret_cast<const float4*>(w + ((int64_t)g * 9 + t) * GC + coff) : make_float4(0.f, 0.f, 0.f, 0.f);
+    acc[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  const bool need_x = DO_DW || relu_mask;
+  // both gradients at once: wv + acc are 72 registers, one pixel in flight keeps the kernel inside 128 without scratch
+  constexpr int UN = (DO_DX && DO_DW) ? 1 : GC_UNROLL;
+  for (int64_t q0 = hw / G; q0 < M; q0 += UN * J) {
+    float4 h[UN];
+    float gy[UN][9];
+#pragma unroll
+    for (int u = 0; u < UN; ++u) {
+      const int64_t q = q0 + u * J;
+      h[u] = (q < M && need_x) ? *reinterpret_cast<const float4*>(x + q * GC + coff) : make_float4(0.f, 0.f, 0.f, 0.f);
+      if (q < M) {
+        const RowCoord rc = decode_row(d, q);
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+          // y[p] took x[p + off(t)] * w[t], so x[q] feeds y[q - off(t)]
+          const int64_t p = neighbour_row(d, q, rc, 1 - t / 3, 1 - t % 3);
+          gy[u][t] = p >= 0 ? dy[p * Ns + g] : 0.f;
+        }
+      } else {
+#pragma unroll
+        for (int t = 0; t < 9; ++t) gy[u][t] = 0.f;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < UN; ++u) {
+      const int64_t q = q0 + u * J;
+      if (DO_DW) {
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+          acc[t].x = __fmaf_rn(gy[u][t], h[u].x, acc[t].x);
+          acc[t].y = __fmaf_rn(gy[u][t], h[u].y, acc[t].y);
+          acc[t].z = __fmaf_rn(gy[u][t], h[u].z, acc[t].z);
+          acc[t].w = __fmaf_rn(gy[u][t], h[u].w, acc[t].w);
+        }
+      }
+      if (DO_DX && q < M) {
+        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+          o.x = __fmaf_rn(gy[u][t], wv[t].x, o.x);
+          o.y = __fmaf_rn(gy[u][t], wv[t].y, o.y);
+          o.z = __fmaf_rn(gy[u][t], wv[t].z, o.z);
+          o.w = __fmaf_rn(gy[u][t], wv[t].w, o.w);
+        }
+        if (relu_mask) {
+          o.x = h[u].x > 0.f ? o.x : 0.f;
+          o.y = h[u].y > 0.f ? o.y : 0.f;
+          o.z = h[u].z > 0.f ? o.z : 0.f;
+          o.w = h[u].w > 0.f ? o.w : 0.f;
+        }
+        *reinterpret_cast<float4*>(dx + q * GC + coff) = o;
+      }
+    }
+  }
+  if (!DO_DW) return;
+  float* out = slab + (int64_t)hw * 9 * GC_G + 4 * l32;
+#pragma unroll
+  for (int t = 0; t < 9; ++t) *reinterpret_cast<float4*>(out + t * GC_G) = acc[t];
+}
+
+// partial [parts][(g * 9 + t) * 128 + i] of the generic slab -> dw[g][t][g * 128 + i]
+__global__ __launch_bounds__(256) void gconv_wgrad_reduce_generic_kernel(const float* __restrict__ partial, int parts, int G,
+                                                                         int GC, float* __restrict__ dw, int accumulate) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;  // over 9 * GC
+  if (i >= 9 * GC) return;
+  const int gt = i / GC_G, c = i - gt * GC_G;  // gt = g * 9 + t
+  float s = 0.f;
+  for (int b = 0; b < parts; ++b) s += partial[(int64_t)b * 9 * GC + i];
+  float* dst = dw + (int64_t)gt * GC + (gt / 9) * GC_G + c;
+  *dst = accumulate ? *dst + s : s;
+}
+
 #define GC_MAX_BLOCKS 1024
 #define GC_PARTS 32
+#define GC_GMAX 31
 
-static int gconv_check(const scan_pyramid_t* d, int G, int Cg, const char* who) {
+// any_g: the scan_gconv3x3_to1_any_* entry points (1 <= G <= GC_GMAX); the others keep to the four lane-mapped counts
+static int gconv_check(const scan_pyramid_t* d, int G, int Cg, const char* who, bool any_g = false) {
   SCAN_CHECK_ARG(d && d->n_levels >= 1 && d->n_levels <= SCAN_MAX_LEVELS, "%s: bad pyramid", who);
   SCAN_CHECK_ARG(Cg == GC_G, "%s: only 128 channels per group are built (got %d)", who, Cg);
+  if (any_g) {
+    SCAN_CHECK_ARG(G >= 1 && G <= GC_GMAX, "%s: G=%d out of 1..%d", who, G, GC_GMAX);
+    return 0;
+  }
   SCAN_CHECK_ARG(G == 1 || G == 2 || G == 4 || G == 8, "%s: G=%d must be 1, 2, 4 or 8", who, G);
   return 0;
+}
+
+static bool gconv_generic(int G) { return !(G == 1 || G == 2 || G == 4 || G == 8); }
+
+extern "C" int32_t scan_gconv3x3_to1_max_groups(void) { return GC_GMAX; }
+
+// pixel strides J of the generic kernels: a multiple of 8 (J * G / 8 whole workgroups), about `per` pixels per half-wave,
+// at most max_j (the weight-gradient slab holds GC_MAX_BLOCKS strides)
+static int gconv_generic_strides(int64_t M, int per, int max_j) {
+  int64_t j = ((M + per - 1) / per + 7) / 8 * 8;
+  if (j < 8) j = 8;
+  if (j > max_j) j = max_j;
+  return (int)j;
 }
 
 extern "C" int64_t scan_gconv3x3_to1_ws_floats(const scan_pyramid_t* d, int32_t G, int32_t Cg) {
@@ -411,12 +563,21 @@ static int gconv_wave_grid(int64_t M, int G) {
 }
 
 static int gconv_forward(const float* x, const scan_pyramid_t* d, int G, int Cg, const float* w, const float* bias, float* y,
-                         int Ns, float* ws, uint32_t* relu_bits, hipStream_t st) {
-  if (gconv_check(d, G, Cg, "gconv3x3_to1_forward")) return -1;
+                         int Ns, float* ws, uint32_t* relu_bits, hipStream_t st, bool any_g = false) {
+  if (gconv_check(d, G, Cg, "gconv3x3_to1_forward", any_g)) return -1;
   SCAN_CHECK_ARG(x && w && y && ws && Ns >= G, "gconv3x3_to1_forward: bad arguments (Ns=%d)", Ns);
   const int64_t M = d->row_off[d->n_levels];
   if (M == 0) return 0;
   const int GC = G * Cg, slots = 256 / (GC / 4);
+  if (gconv_generic(G)) {
+    SCAN_CHECK_ARG(relu_bits == nullptr, "gconv3x3_to1_forward_bits: G=%d must be 1, 2, 4 or 8", G);
+    const int J = gconv_generic_strides(M, GC_UNROLL_F, 2048);
+    hipLaunchKernelGGL(gconv_taps_generic_kernel, dim3(J / 8 * G), dim3(256), 0, st, x, M, G, GC, w, ws);
+    SCAN_LAUNCH_CHECK("gconv_taps_generic");
+    hipLaunchKernelGGL(gconv_gather_kernel, dim3(grid_for(M * Ns, 256)), dim3(256), 0, st, ws, *d, G, bias, y, Ns);
+    SCAN_LAUNCH_CHECK("gconv_gather");
+    return 0;
+  }
   if (g_scan_gconv_mfma || relu_bits != nullptr) {
     hipLaunchKernelGGL(gconv_taps_mfma_kernel, dim3(gconv_wave_grid(M, G)), dim3(256), 0, st, x, M, G, GC, w, ws, relu_bits);
   } else {
@@ -443,8 +604,8 @@ extern "C" int scan_gconv3x3_to1_forward_bits(const float* x, const scan_pyramid
 
 static int gconv_backward(const float* x, const float* dy, int Ns, const scan_pyramid_t* d, int G, int Cg, const float* w,
                           int relu_mask, const uint32_t* relu_bits, float* dx, float* dw, int accumulate, float* ws,
-                          hipStream_t st, const char* who) {
-  if (gconv_check(d, G, Cg, who)) return -1;
+                          hipStream_t st, const char* who, bool any_g = false) {
+  if (gconv_check(d, G, Cg, who, any_g)) return -1;
   SCAN_CHECK_ARG(dy && Ns >= G && (dx || dw), "%s: bad arguments (Ns=%d)", who, Ns);
   SCAN_CHECK_ARG(!dx || w, "%s: the data gradient needs the weights", who);
   SCAN_CHECK_ARG(!dw || (x && ws), "%s: the weight gradient needs x and a workspace", who);
@@ -452,6 +613,30 @@ static int gconv_backward(const float* x, const float* dy, int Ns, const scan_py
   const int64_t M = d->row_off[d->n_levels];
   if (M == 0) return 0;
   const int GC = G * Cg;
+  if (gconv_generic(G)) {
+    SCAN_CHECK_ARG(relu_bits == nullptr, "%s: G=%d must be 1, 2, 4 or 8", who, G);
+    const int J = gconv_generic_strides(M, 16, GC_MAX_BLOCKS);
+    const dim3 grid(J / 8 * G);
+    if (dx && dw)
+      hipLaunchKernelGGL((gconv_bwd_generic_kernel<true, true>), grid, dim3(256), 0, st, x, dy, Ns, *d, G, GC, w, relu_mask, dx, ws);
+    else if (dx)
+      hipLaunchKernelGGL((gconv_bwd_generic_kernel<true, false>), grid, dim3(256), 0, st, x, dy, Ns, *d, G, GC, w, relu_mask, dx,
+                         ws);
+    else
+      hipLaunchKernelGGL((gconv_bwd_generic_kernel<false, true>), grid, dim3(256), 0, st, x, dy, Ns, *d, G, GC, w, 0, dx, ws);
+    SCAN_LAUNCH_CHECK(who);
+    if (dw) {
+      // the same fixed-order two-level sum: 32 runs of consecutive strides j, then the 32 run sums
+      const int n = 9 * GC, per = (J + GC_PARTS - 1) / GC_PARTS, parts = (J + per - 1) / per;
+      float* partial = ws + (int64_t)GC_MAX_BLOCKS * n;
+      hipLaunchKernelGGL(gconv_slab_partial_kernel, dim3((n + 255) / 256, parts), dim3(256), 0, st, ws, J, n, per, partial);
+      SCAN_LAUNCH_CHECK("gconv_slab_partial");
+      hipLaunchKernelGGL(gconv_wgrad_reduce_generic_kernel, dim3((n + 255) / 256), dim3(256), 0, st, partial, parts, G, GC, dw,
+                         accumulate);
+      SCAN_LAUNCH_CHECK("gconv_wgrad_reduce");
+    }
+    return 0;
+  }
   int blocks = GC_MAX_BLOCKS;
   int64_t rpb = (M + blocks - 1) / blocks;
   if (rpb < 16) rpb = 16;  // small levels: fewer, fuller workgroups
@@ -518,4 +703,33 @@ extern "C" int scan_gconv3x3_to1_backward_bits(const float* x, const float* dy, 
   SCAN_CHECK_ARG(x && dx && dw && relu_bits, "gconv3x3_to1_backward_bits: null pointer");
   return gconv_backward(x, dy, Ns, d, G, Cg, w, 1, relu_bits, dx, dw, accumulate, ws, as_stream(stream),
                         "gconv3x3_to1_backward_bits");
+}
+
+// ---- any group count 1 <= G <= scan_gconv3x3_to1_max_groups(): G = 1, 2, 4, 8 run the kernels above, every other G the
+// generic family.  Same arguments and results as the entry points without "any".
+extern "C" int scan_gconv3x3_to1_any_forward(const float* x, const scan_pyramid_t* d, int32_t G, int32_t Cg, const float* w,
+                                             const float* bias, float* y, int32_t Ns, float* ws, void* stream) {
+  return gconv_forward(x, d, G, Cg, w, bias, y, Ns, ws, nullptr, as_stream(stream), true);
+}
+
+extern "C" int scan_gconv3x3_to1_any_dgrad(const float* dy, int32_t Ns, const scan_pyramid_t* d, int32_t G, int32_t Cg,
+                                           const float* w, const float* mask, float* dx, void* stream) {
+  SCAN_CHECK_ARG(dx, "gconv3x3_to1_any_dgrad: null output");
+  return gconv_backward(mask, dy, Ns, d, G, Cg, w, mask != nullptr, nullptr, dx, nullptr, 0, nullptr, as_stream(stream),
+                        "gconv3x3_to1_any_dgrad", true);
+}
+
+extern "C" int scan_gconv3x3_to1_any_wgrad(const float* x, const float* dy, int32_t Ns, const scan_pyramid_t* d, int32_t G,
+                                           int32_t Cg, float* dw, int32_t accumulate, float* ws, void* stream) {
+  SCAN_CHECK_ARG(dw, "gconv3x3_to1_any_wgrad: null output");
+  return gconv_backward(x, dy, Ns, d, G, Cg, nullptr, 0, nullptr, nullptr, dw, accumulate, ws, as_stream(stream),
+                        "gconv3x3_to1_any_wgrad", true);
+}
+
+extern "C" int scan_gconv3x3_to1_any_backward(const float* x, const float* dy, int32_t Ns, const scan_pyramid_t* d, int32_t G,
+                                              int32_t Cg, const float* w, int32_t relu_mask, float* dx, float* dw,
+                                              int32_t accumulate, float* ws, void* stream) {
+  SCAN_CHECK_ARG(x && dx && dw, "gconv3x3_to1_any_backward: null pointer");
+  return gconv_backward(x, dy, Ns, d, G, Cg, w, relu_mask, nullptr, dx, dw, accumulate, ws, as_stream(stream),
+                        "gconv3x3_to1_any_backward", true);
 }

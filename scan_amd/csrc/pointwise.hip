@@ -426,7 +426,7 @@ extern "C" int scan_bce_logits_backward(const float* logits, const float* target
 }
 
 // ------------------------------------------------------------------ CKA class-conditional BCE
-#define CKA_MAXC 16
+#define CKA_MAXC 32  // foreground classes: scan_dynconv_max_classes() - 1 fit
 // fin != nullptr: the block that finishes last (ticket fin[0], zeroed by the caller) turns the completed sums into the
 // loss  fin[1] = sum_c (num_c / den_c) / Cf  -- the reference's per-class weighted means averaged over the classes
 // (discriminator/fcos_head_discriminator_con.py:119-121) -- so the layer needs no select / div / sum / div kernels of
@@ -616,6 +616,7 @@ extern "C" int scan_scale(const float* x, float alpha, float* y, int64_t n, void
 // ------------------------------------------------------------------ softmax focal loss (alpha = 1)
 // layers/sigmoid_focal_loss_wbg.py:38-64:  p = softmax(z)[label] clamped at 1e-15; -(1-p)^g log p
 #define SFL_MAXK 16
+#define SFL_MAXK_WIDE 32  // = scan_dynconv_max_classes()
 // Rows are K floats (36 B at K = 9): a lane reading its own row touches a new cache line every 3-4 lanes.  A block
 // therefore moves its 256 rows as ONE contiguous 256*K-float segment with coalesced dword accesses through LDS and each
 // lane then walks its row in LDS (stride K floats: conflict-free for odd K).
@@ -624,22 +625,24 @@ extern "C" int scan_scale(const float* x, float alpha, float* y, int64_t n, void
 // conflict-free for odd K); LDS operations of one wave execute in order, so a wave-level fence is all that is needed.
 // Two 64-row batches are in flight per wave and iteration (the first cut -- 256 rows per workgroup between two
 // __syncthreads -- spent 72 % of its wave cycles parked: profiles/r03_pointwise_counters.txt).
-template <bool BWD, bool ORD = false>
+// MAXK: the unrolled class bound and the LDS row pitch.  16 (SFL_MAXK) serves K <= 16 -- the shipped class counts; K = 17..32
+// run the MAXK = 32 instances, one 64-row batch per wave and iteration so that the LDS region stays at 32 KB.
+template <bool BWD, bool ORD = false, int MAXK = SFL_MAXK>
 __global__ __launch_bounds__(256) void sfl_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
                                                   int64_t M, int K, float gamma, float d_scale,
                                                   float* __restrict__ loss_sum, float* __restrict__ d_logits) {
-  constexpr int NB = 2;  // batches of 64 rows per wave and iteration
-  __shared__ float rows_all[4 * NB * 64 * SFL_MAXK];
+  constexpr int NB = MAXK > SFL_MAXK ? 1 : 2;  // batches of 64 rows per wave and iteration
+  __shared__ float rows_all[4 * NB * 64 * MAXK];
   __shared__ float red[4];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  float* wrows = rows_all + wid * (NB * 64 * SFL_MAXK);
+  float* wrows = rows_all + wid * (NB * 64 * MAXK);
   const bool g2 = gamma == 2.0f;
   const bool vec_ok = (reinterpret_cast<uintptr_t>(logits) & 15) == 0;
   float acc = 0.f;
   const int64_t nbatch = (M + 63) / 64;
   const int64_t stride = (int64_t)gridDim.x * 4 * NB;
   for (int64_t b0 = ((int64_t)blockIdx.x * 4 + wid) * NB; b0 < nbatch; b0 += stride) {
-    constexpr int NV = SFL_MAXK / 4;  // float4 per lane and batch: 64 rows x K floats = 16 K float4, lane + 64 j
+    constexpr int NV = MAXK / 4;  // float4 per lane and batch: 64 rows x K floats = 16 K float4, lane + 64 j
     float4 v[NB][NV];
     int nrow[NB];
 #pragma unroll
@@ -666,30 +669,30 @@ __global__ __launch_bounds__(256) void sfl_kernel(const float* __restrict__ logi
     for (int u = 0; u < NB; ++u)
 #pragma unroll
       for (int j = 0; j < NV; ++j)
-        if (4 * 64 * j < 64 * K) *reinterpret_cast<float4*>(wrows + u * 64 * SFL_MAXK + 4 * (lane + 64 * j)) = v[u][j];
+        if (4 * 64 * j < 64 * K) *reinterpret_cast<float4*>(wrows + u * 64 * MAXK + 4 * (lane + 64 * j)) = v[u][j];
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
     for (int u = 0; u < NB; ++u) {
       const int64_t r0 = (b0 + u) * 64;
-      float* z = wrows + u * 64 * SFL_MAXK + lane * K;
+      float* z = wrows + u * 64 * MAXK + lane * K;
       if (lane < nrow[u]) {
-        float e[SFL_MAXK];
+        float e[MAXK];
         float mx = z[0];
 #pragma unroll
-        for (int k = 1; k < SFL_MAXK; ++k)
+        for (int k = 1; k < MAXK; ++k)
           if (k < K) mx = fmaxf(mx, z[k]);
         float den = 0.f;
 #pragma unroll
-        for (int k = 0; k < SFL_MAXK; ++k) {
+        for (int k = 0; k < MAXK; ++k) {
           e[k] = (k < K) ? __expf(z[k] - mx) : 0.f;
           den += e[k];
         }
         const int lab = (int)labels[r0 + lane];
         float el = 0.f;
 #pragma unroll
-        for (int k = 0; k < SFL_MAXK; ++k) el = (k == lab) ? e[k] : el;
+        for (int k = 0; k < MAXK; ++k) el = (k == lab) ? e[k] : el;
         const float inv = __builtin_amdgcn_rcpf(den);
         const float pr = el * inv;
         if (!BWD) {
@@ -708,7 +711,7 @@ __global__ __launch_bounds__(256) void sfl_kernel(const float* __restrict__ logi
           }
           const float c = dLdp * pr * d_scale;
 #pragma unroll
-          for (int k = 0; k < SFL_MAXK; ++k)
+          for (int k = 0; k < MAXK; ++k)
             if (k < K) z[k] = c * ((k == lab ? 1.f : 0.f) - e[k] * inv);
         }
       }
@@ -724,9 +727,9 @@ __global__ __launch_bounds__(256) void sfl_kernel(const float* __restrict__ logi
         const int nf = nrow[u] * K;
         const bool st_ok = (reinterpret_cast<uintptr_t>(d_logits) & 15) == 0;
 #pragma unroll
-        for (int j = 0; j < SFL_MAXK / 4; ++j) {
+        for (int j = 0; j < MAXK / 4; ++j) {
           const int i4 = 4 * (lane + 64 * j);
-          const float4 o = *reinterpret_cast<const float4*>(wrows + u * 64 * SFL_MAXK + i4);
+          const float4 o = *reinterpret_cast<const float4*>(wrows + u * 64 * MAXK + i4);
           if (i4 + 3 < nf && st_ok) {
             *reinterpret_cast<float4*>(dst + i4) = o;
           } else if (i4 < nf) {
@@ -750,11 +753,17 @@ __global__ __launch_bounds__(256) void sfl_kernel(const float* __restrict__ logi
 
 extern "C" int scan_softmax_focal_forward(const float* logits, const int64_t* labels, int64_t M, int32_t K,
                                           float gamma, float* loss_sum, void* stream) {
-  SCAN_CHECK_ARG(M >= 0 && K > 0 && K <= SFL_MAXK && loss_sum, "softmax_focal_forward: bad arguments (K=%d)", K);
+  SCAN_CHECK_ARG(M >= 0 && K > 0 && K <= SFL_MAXK_WIDE && loss_sum, "softmax_focal_forward: bad arguments (K=%d)", K);
   if (M == 0) return 0;
   SCAN_CHECK_ARG(logits && labels, "softmax_focal_forward: null input");
   int64_t g = (M + 511) / 512;  // a workgroup iteration covers 4 waves x 2 batches x 64 rows
   if (g > 2048) g = 2048;
+  if (K > SFL_MAXK) {
+    hipLaunchKernelGGL((sfl_kernel<false, false, SFL_MAXK_WIDE>), dim3((int)g), dim3(256), 0, as_stream(stream), logits, labels, M,
+                       K, gamma, 0.f, loss_sum, (float*)nullptr);
+    SCAN_LAUNCH_CHECK("sfl_fwd");
+    return 0;
+  }
   hipLaunchKernelGGL(sfl_kernel<false>, dim3((int)g), dim3(256), 0, as_stream(stream), logits, labels, M, K, gamma, 0.f,
                      loss_sum, (float*)nullptr);
   SCAN_LAUNCH_CHECK("sfl_fwd");
@@ -763,11 +772,17 @@ extern "C" int scan_softmax_focal_forward(const float* logits, const int64_t* la
 
 extern "C" int scan_softmax_focal_backward(const float* logits, const int64_t* labels, int64_t M, int32_t K,
                                            float gamma, float d_scale, float* d_logits, void* stream) {
-  SCAN_CHECK_ARG(M >= 0 && K > 0 && K <= SFL_MAXK, "softmax_focal_backward: bad arguments (K=%d)", K);
+  SCAN_CHECK_ARG(M >= 0 && K > 0 && K <= SFL_MAXK_WIDE, "softmax_focal_backward: bad arguments (K=%d)", K);
   if (M == 0) return 0;
   SCAN_CHECK_ARG(logits && labels && d_logits, "softmax_focal_backward: null pointer");
   int64_t g = (M + 511) / 512;
   if (g > 4096) g = 4096;
+  if (K > SFL_MAXK) {
+    hipLaunchKernelGGL((sfl_kernel<true, false, SFL_MAXK_WIDE>), dim3((int)g), dim3(256), 0, as_stream(stream), logits, labels, M, K,
+                       gamma, d_scale, (float*)nullptr, d_logits);
+    SCAN_LAUNCH_CHECK("sfl_bwd");
+    return 0;
+  }
   hipLaunchKernelGGL(sfl_kernel<true>, dim3((int)g), dim3(256), 0, as_stream(stream), logits, labels, M, K, gamma,
                      d_scale, (float*)nullptr, d_logits);
   SCAN_LAUNCH_CHECK("sfl_bwd");
@@ -908,10 +923,16 @@ extern "C" int scan_cka_bce_forward_loss_ordered(const float* logits, const floa
 
 extern "C" int scan_softmax_focal_forward_ordered(const float* logits, const int64_t* labels, int64_t M, int32_t K,
                                                   float gamma, float* loss_sum, float* ws, void* stream) {
-  SCAN_CHECK_ARG(M >= 0 && K > 0 && K <= SFL_MAXK && loss_sum && ws, "softmax_focal_forward_ordered: bad arguments (K=%d)", K);
+  SCAN_CHECK_ARG(M >= 0 && K > 0 && K <= SFL_MAXK_WIDE && loss_sum && ws, "softmax_focal_forward_ordered: bad arguments (K=%d)", K);
   if (M == 0) return 0;
   SCAN_CHECK_ARG(logits && labels, "softmax_focal_forward_ordered: null input");
   const int grid = sfl_fwd_grid(M);
+  if (K > SFL_MAXK) {
+    hipLaunchKernelGGL((sfl_kernel<false, true, SFL_MAXK_WIDE>), dim3(grid), dim3(256), 0, as_stream(stream), logits, labels, M, K,
+                       gamma, 0.f, ws, (float*)nullptr);
+    SCAN_LAUNCH_CHECK("sfl_fwd_ordered");
+    return ordered_sum_launch(ws, grid, 1, loss_sum, 0, nullptr, stream, "sfl_fwd_ordered_sum");
+  }
   hipLaunchKernelGGL((sfl_kernel<false, true>), dim3(grid), dim3(256), 0, as_stream(stream), logits, labels, M, K, gamma, 0.f, ws,
                      (float*)nullptr);
   SCAN_LAUNCH_CHECK("sfl_fwd_ordered");

@@ -50,6 +50,9 @@ def build_model(num_classes=9, test_mode="precision", device="cuda", attn_dropou
     s.update(num_classes=num_classes, test_mode=test_mode, transfer_cfg=tuple(transfer_cfg), conv_body=conv_body)
     if settings is not None:
         s.update(settings)
+    if not 2 <= s["num_classes"] <= ops.dynconv_max_classes():
+        raise ValueError("num_classes=%d (background included): the kernels are built for 2..%d classes"
+                         % (s["num_classes"], ops.dynconv_max_classes()))
     conv_body = s["conv_body"]
     if conv_body == "VGG-16-FPN-RETINANET":
         backbone = build_backbone()

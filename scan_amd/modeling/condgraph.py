@@ -219,6 +219,9 @@ class GRAPHModule(nn.Module):
     def __init__(self, in_channels=256, num_classes=9, proto_iter=3, attn_dropout=0.1, transfer_cfg=("NODES", "ADJ"),
                  dbscan_eps=3, dbscan_thr=0.05):
         super().__init__()
+        if not 2 <= num_classes <= ops.dynconv_max_classes():
+            raise ValueError("num_classes=%d (background included): the dynamic-conv kernels are built for 2..%d"
+                             % (num_classes, ops.dynconv_max_classes()))
         self.transfer_cfg = tuple(transfer_cfg)
         self.dbscan_eps, self.dbscan_thr = dbscan_eps, dbscan_thr
         self.lamda3 = self.lamda4 = 1.0

@@ -76,15 +76,17 @@ class FCOSDiscriminator_con(nn.Module):
             if cs1 != xcat.shape[1]:
                 xcat = torch.nn.functional.pad(xcat, (0, cs1 - xcat.shape[1]))
         blocks = [getattr(self, "classifier_cls_%d" % c) for c in range(Cf)]
-        if ops.BATCHED:
+        if ops.BATCHED and Cf <= ops.CKA_STACK_MAX:  # the one-launch stacking takes 16 branches; more: the torch spelling
             w1, b1, w2, b2 = ops.cka_stacked_weights([(b[0], b[2]) for b in blocks], self.in_channels, 128,
                                                      xcat.shape[1])
         else:
             w1, b1, w2, b2 = self._stacked_weights_torch()
         h = ops.conv2d(xcat, w1, b1, shape, 3, 1, relu="deferred")  # its only consumer masks dx by (h > 0)
-        if ops.GROUPED_CLS and Cf in (1, 2, 4, 8):
+        if ops.GROUPED_CLS and 1 <= Cf <= ops.gconv_max_groups():
             # one output channel per class from that class's 128 hidden channels: an HBM-bound grouped kernel instead of
             # a dense conv over the block-diagonal weight (64x the useful multiply-adds)
+            if not w2.permute(0, 2, 3, 1).is_contiguous():  # the torch-stacked weight (more than 16 branches)
+                w2 = w2.contiguous(memory_format=torch.channels_last)
             return ops.gconv3x3_to1(h, w2, b2, shape, Cf, mask_dx=True)[:, :Cf], act_maps
         return ops.conv2d(h, w2, b2, shape, 3, 1, mask_dx=True)[:, :Cf], act_maps
 

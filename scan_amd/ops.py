@@ -1137,8 +1137,26 @@ class _DynConvSoftmax(torch.autograd.Function):
         return d_feat, d_k
 
 
+_limits = {}  # constants of the loaded library, asked once
+
+
+def _limit(name):
+    if name not in _limits:
+        _limits[name] = int(query(name))
+    return _limits[name]
+
+
+def dynconv_max_classes():
+    """largest class count (background included) the dynamic conv is built for"""
+    return _limit("scan_dynconv_max_classes")
+
+
 def dynconv_softmax(feat, kernels):
-    """feat [M,256], kernels [K,256] -> (logits [M,K], probs [M,K])."""
+    """feat [M,256], kernels [K,256] -> (logits [M,K], probs [M,K]); 2 <= K <= dynconv_max_classes().  K = 2 and 9 run
+    kernels compiled for them, every other K the generic ones."""
+    K = int(kernels.shape[0])
+    if not 2 <= K <= dynconv_max_classes():
+        raise ValueError("dynconv_softmax: %d classes, the kernels are built for 2..%d" % (K, dynconv_max_classes()))
     return _DynConvSoftmax.apply(feat, kernels)
 
 
@@ -1581,6 +1599,9 @@ class _CkaStackedWeights(torch.autograd.Function):
         return (None, None, None) + (tuple(None for _ in params) if direct else tuple(tgt))
 
 
+CKA_STACK_MAX = _lib.CKA_MAX_CLASSES  # branches scan_cka_stack_weights / scan_cka_unstack_grads take in one launch
+
+
 def cka_stacked_weights(branches, C, H, cs1):
     """branches: the Cf (conv0, conv2) module pairs.  Returns (w1 [Cf*H, cs1, 3, 3], b1, w2 [Cf, Cf*H, 3, 3], b2) with
     cs1 = the (padded) channel count of cat(x, act[1:])."""
@@ -1606,12 +1627,14 @@ class _GroupedConvTo1(torch.autograd.Function):
         ws = x.new_empty((query("scan_gconv3x3_to1_ws_floats", shape.ref(), G, 128),))
         bits = None
         mfma = query("scan_tune_get", b"gconv_mfma")  # read-only: no write to the launch-selection state
-        if mfma == 1 and mask_dx and torch.is_grad_enabled() and x.requires_grad:
+        # the matrix-core / bit-mask kernels exist for G = 1, 2, 4, 8 only
+        any_ = "" if G in (1, 2, 4, 8) else "any_"  # the scan_gconv3x3_to1_any_* entry points take every G up to gconv_max_groups()
+        if mfma == 1 and not any_ and mask_dx and torch.is_grad_enabled() and x.requires_grad:
             bits = torch.empty((shape.rows * G * 4,), dtype=torch.int32, device=x.device)
             call("scan_gconv3x3_to1_forward_bits", _ptr(x), shape.ref(), G, 128, _ptr(w), _ptr(bias), _ptr(y), ns,
                  _ptr(ws), _ptr(bits), _stream())
         else:
-            call("scan_gconv3x3_to1_forward", _ptr(x), shape.ref(), G, 128, _ptr(w), _ptr(bias), _ptr(y), ns, _ptr(ws),
+            call("scan_gconv3x3_to1_%sforward" % any_, _ptr(x), shape.ref(), G, 128, _ptr(w), _ptr(bias), _ptr(y), ns, _ptr(ws),
                  _stream())
         ctx.save_for_backward(x, w, bits)
         ctx.cfg = (shape, G, ns, mask_dx, bias is not None)
@@ -1621,6 +1644,7 @@ class _GroupedConvTo1(torch.autograd.Function):
     def backward(ctx, dy):
         x, w, bits = ctx.saved_tensors
         shape, G, ns, mask_dx, has_bias = ctx.cfg
+        any_ = "" if G in (1, 2, 4, 8) else "any_"
         dy = dy.contiguous()
         st = _stream()
         dx = dw = db = dwp = None
@@ -1634,13 +1658,13 @@ class _GroupedConvTo1(torch.autograd.Function):
             call("scan_gconv3x3_to1_backward_bits", _ptr(x), _ptr(dy), ns, shape.ref(), G, 128, _ptr(w), _ptr(bits),
                  _ptr(dx), _ptr(dwp), 0, _ptr(ws), st)
         elif dx is not None and dwp is not None:
-            call("scan_gconv3x3_to1_backward", _ptr(x), _ptr(dy), ns, shape.ref(), G, 128, _ptr(w), int(mask_dx), _ptr(dx),
+            call("scan_gconv3x3_to1_%sbackward" % any_, _ptr(x), _ptr(dy), ns, shape.ref(), G, 128, _ptr(w), int(mask_dx), _ptr(dx),
                  _ptr(dwp), 0, _ptr(ws), st)
         elif dx is not None:
-            call("scan_gconv3x3_to1_dgrad", _ptr(dy), ns, shape.ref(), G, 128, _ptr(w), _ptr(x if mask_dx else None),
+            call("scan_gconv3x3_to1_%sdgrad" % any_, _ptr(dy), ns, shape.ref(), G, 128, _ptr(w), _ptr(x if mask_dx else None),
                  _ptr(dx), st)
         elif dwp is not None:
-            call("scan_gconv3x3_to1_wgrad", _ptr(x), _ptr(dy), ns, shape.ref(), G, 128, _ptr(dwp), 0, _ptr(ws), st)
+            call("scan_gconv3x3_to1_%swgrad" % any_, _ptr(x), _ptr(dy), ns, shape.ref(), G, 128, _ptr(dwp), 0, _ptr(ws), st)
         if has_bias and ctx.needs_input_grad[2]:
             M = dy.shape[0]
             cws = x.new_empty((query("scan_colsum_ws_floats", M, G),))
@@ -1651,6 +1675,11 @@ class _GroupedConvTo1(torch.autograd.Function):
 
 # SCAN_GROUPED_CLS=0: the class branches' second conv on the dense MFMA kernel (block-diagonal weight), for A/B
 GROUPED_CLS = os.environ.get("SCAN_GROUPED_CLS", "1") != "0"
+
+
+def gconv_max_groups():
+    """largest group count of gconv3x3_to1 (G = 1, 2, 4, 8 have kernels of their own, every other G the generic ones)"""
+    return _limit("scan_gconv3x3_to1_max_groups")
 
 
 def gconv3x3_to1(x, w, bias, shape, G, mask_dx=False):
