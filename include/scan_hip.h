@@ -80,9 +80,10 @@ int scan_abi_version(void);
  *   "wgrad_wino"  1 (default): the bf16x6 3x3 weight gradient on that kernel's 32 x 64 tile runs Winograd F(2,3) across rows:
  *                 the K walk goes over row pairs, a workgroup owns one of four components instead of one of three ky, a third
  *                 fewer MFMAs; transforms in fp32 on the loaded rows (one rounding per value), G^T on the fp64 slab sums.
- *                 Slabs then hold 12 taps: scan_conv3x3_wgrad_bf16x6_ws_floats follows the knob, so size the workspace
- *                 AFTER setting it.  0: the direct kernel and split-K plan, bit for bit.  bf16x3, wgrad_v6 = 0 and
- *                 wgrad_tile = 0 are always direct.
+ *                 Slabs then hold 12 taps.  scan_conv_wgrad_plan reads the knob once and scan_conv_wgrad_run runs what was
+ *                 planned, whatever the knob says by then; only the older pair -- scan_conv3x3_wgrad_bf16x6_ws_floats, then
+ *                 scan_conv3x3_wgrad_bf16x6 -- reads it twice: there, size the workspace AFTER setting it.  0: the direct
+ *                 kernel and split-K plan, bit for bit.  bf16x3, wgrad_v6 = 0 and wgrad_tile = 0 are always direct.
  *   "wino_tpb"    (bf16x6, next to "conv_wino": the Winograd F(2,3) forward / data-gradient instance, scan_conv3x3_wino_bf16x6)
  *                 weight taps per barrier interval: 2 (default) = the patch is staged in component pairs and the LDS that frees
  *                 holds two taps per weight buffer -- 8 barriers per 32-channel chunk, 96 MFMAs per wave between them; 1 (and
@@ -447,6 +448,56 @@ int scan_conv_run(const scan_conv_plan_t* plan, const float* x, const scan_pyram
                   const void* p1, const void* p2, const float* bias, const float* mask, float* y,
                   const scan_pyramid_t* yd, int32_t Ns, int32_t relu, int32_t map, float* gn_ws, int32_t clear,
                   void* stream);
+/* ---- one dispatcher for the weight gradients above (no reference counterpart) ----
+ * Kernel family, kernel variant, split-K cut and workspace layout of a weight gradient are decided ONCE, by scan_conv_wgrad_plan,
+ * for every binding; scan_conv_wgrad_run launches what the plan says and reads none of the scan_tune knobs the plan decided
+ * ("wgrad_v6", "wgrad_tile", "wgrad_wino", "wgrad_wgs"): a workspace of plan.ws_floats fits the launch whatever the knobs say
+ * by then.  ("wgrad_prio", a scheduling hint without effect on layout or bits, is still read at launch.)  The entry points
+ * above stay what they were; each plans under the knobs of the moment and runs. */
+#define SCAN_WGRAD_SPLIT3X3 1 /* family: scan_conv3x3_wgrad_bf16x3 / _bf16x6 (pieces 2 / 3, 3x3, stride 1) */
+#define SCAN_WGRAD_SPLIT1X1 2 /* family: scan_conv1x1_wgrad_bf16x3 / _bf16x6 (pieces 2 / 3, 1x1, stride 1 or 2) */
+#define SCAN_WGRAD_GENERIC 3  /* family: scan_conv2d_wgrad, then scan_colsum for the bias gradient (everything else) */
+#define SCAN_WGRAD_FP32 0          /* variant: conv_wgrad_kernel, fp32 MFMAs (the generic family) */
+#define SCAN_WGRAD_V4 1            /* variant: conv_wgrad_v4_kernel (every 1x1; 3x3 under wgrad_v6 = 0) */
+#define SCAN_WGRAD_V6_64X32 2      /* variant: conv_wgrad_v6_kernel, consumer wave tile 64 (o) x 32 (c) */
+#define SCAN_WGRAD_V6_32X64 3      /* variant: conv_wgrad_v6_kernel, wave tile 32 x 64 */
+#define SCAN_WGRAD_V6_32X64_WINO 4 /* variant: the same in the Winograd F(2,3) form across rows (pieces 3 only) */
+typedef struct {
+  int32_t family;      /* SCAN_WGRAD_SPLIT3X3 / _SPLIT1X1 / _GENERIC */
+  int32_t pieces;      /* as given: 0 (fp32, always generic), 2 ("bf16x3") or 3 ("bf16x6") */
+  int32_t ksize;       /* 1, 3, 5 or 7 */
+  int32_t stride;      /* 1 or 2 */
+  int32_t Cs, Cout;    /* row length of x and output channels: dw is [Cout][ksize * ksize][Cs] */
+  int32_t variant;     /* SCAN_WGRAD_FP32 / _V4 / _V6_64X32 / _V6_32X64 / _V6_32X64_WINO */
+  int32_t wk;          /* pixels per K chunk of that kernel: 64, or 32 (three pieces on the v6 kernel; generic) */
+  int32_t n_tiles;     /* output tiles per split: 128-channel Cout tiles x tap groups (3 row taps, 4 Winograd components, 1;
+                          generic: ksize * ksize) x c_tiles */
+  int32_t c_tiles;     /* 128-channel tiles of Cs */
+  int32_t splits;      /* split-K slabs; the launch has n_tiles * splits workgroups */
+  int32_t cps;         /* K chunks per split */
+  int32_t slab_taps;   /* taps a slab holds per output channel: 12 (Winograd), 9, 1; generic: ksize * ksize */
+  int32_t fused_db;    /* 1: the kernel also sums dy's columns (split families); 0: scan_colsum's kernels follow (generic) */
+  int64_t chunks;      /* K chunks in all: wk-pixel pieces of the rows (Winograd: row pairs) of x's pyramid (3x3) or dy's (1x1);
+                          generic: wk-row pieces of dy */
+  int64_t slab_floats; /* the workspace starts with [splits][Cout][slab_taps][Cs] weight slabs: this many floats */
+  int64_t bias_off;    /* fused_db: offset of the [splits][Cout] bias slabs; otherwise -1 */
+  int64_t colsum_off;  /* not fused_db: offset of scan_colsum's workspace for dy; otherwise -1 */
+  int64_t ws_floats;   /* floats the workspace must hold */
+} scan_conv_wgrad_plan_t;
+/* Fills *plan for the weight gradient of a conv (pad ksize / 2) with x [.., Cs] on pyramid xd and dy on pyramid yd.  pieces 2 /
+ * 3 with ksize 3 and stride 1 take the split 3x3 family, with ksize 1 the split 1x1 family; everything else (pieces 0 too) that
+ * scan_conv2d_wgrad accepts is generic.  Host arithmetic under the scan_tune knobs of the moment; touches no device. */
+int scan_conv_wgrad_plan(int32_t pieces, int32_t ksize, int32_t stride, int32_t Cs, int32_t Cout, const scan_pyramid_t* xd,
+                         const scan_pyramid_t* yd, scan_conv_wgrad_plan_t* plan);
+/* Runs the planned weight gradient: dw [Cout][ksize * ksize][Cs], db [Cout] or NULL, dy rows of length Cout_s, ws of
+ * plan->ws_floats floats, everything on stream.  accumulate: bit 0 adds to dw, bit 1 adds to db instead of overwriting.  The
+ * split families reduce both in one launch under one flag: with db != NULL, differing bits are refused.  The generic family
+ * runs scan_colsum's kernels for db after the weight gradient.  Refused before any launch: a plan the planner did not fill (its
+ * layout is re-derived from its shape, variant and splits and compared), Cs / Cout other than planned, pyramids whose chunk
+ * count is not the plan's. */
+int scan_conv_wgrad_run(const scan_conv_wgrad_plan_t* plan, const float* x, const scan_pyramid_t* xd, int32_t Cs,
+                        const float* dy, const scan_pyramid_t* yd, int32_t Cout, int32_t Cout_s, float* dw, float* db,
+                        int32_t accumulate, float* ws, void* stream);
 /* w [Cout][T][Cin_s] -> wt [Cin_s][T][Cout_s] (zero padded) */
 int scan_weight_transpose(const float* w, int32_t Cout, int32_t T, int32_t Cin_s, float* wt, int32_t Cout_s,
                           void* stream);

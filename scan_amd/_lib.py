@@ -55,6 +55,18 @@ class ConvPlan(ctypes.Structure):
 CONV_SUMS, CONV_POOL = 1, 2  # SCAN_CONV_SUMS, SCAN_CONV_POOL
 _CP = ctypes.POINTER(ConvPlan)
 
+
+class WgradPlan(ctypes.Structure):
+    """scan_conv_wgrad_plan_t"""
+    _fields_ = [(n, c_i32) for n in ("family", "pieces", "ksize", "stride", "Cs", "Cout", "variant", "wk", "n_tiles", "c_tiles",
+                                     "splits", "cps", "slab_taps", "fused_db")] + \
+               [(n, c_i64) for n in ("chunks", "slab_floats", "bias_off", "colsum_off", "ws_floats")]
+
+
+WGRAD_SPLIT3X3, WGRAD_SPLIT1X1, WGRAD_GENERIC = 1, 2, 3  # SCAN_WGRAD_* families
+WGRAD_FP32, WGRAD_V4, WGRAD_V6_64X32, WGRAD_V6_32X64, WGRAD_V6_32X64_WINO = range(5)  # SCAN_WGRAD_* variants
+_WP = ctypes.POINTER(WgradPlan)
+
 PACK_MAX_LEVELS = 8  # SCAN_PACK_MAX_LEVELS
 SGD_MAX_SEGMENTS = 32
 CKA_MAX_CLASSES = 16
@@ -85,6 +97,8 @@ SIGNATURES = {
     "scan_conv_weight_split": (ctypes.c_int, [_CP, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "scan_conv_run": (ctypes.c_int, [_CP, c_vp, _PD, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _PD, c_i32, c_i32, c_i32, c_vp,
                                      c_i32, c_vp]),
+    "scan_conv_wgrad_plan": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, _PD, _PD, _WP]),
+    "scan_conv_wgrad_run": (ctypes.c_int, [_WP, c_vp, _PD, c_i32, c_vp, _PD, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "scan_sigmoid_focal_loss_forward": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i32, c_f32, c_f32, c_vp, c_vp, c_vp]),
     "scan_sigmoid_focal_loss_backward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f32, c_i64, c_i32, c_f32, c_f32, c_vp, c_vp]),
     "scan_iou_loss_forward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),

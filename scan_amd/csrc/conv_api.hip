@@ -8,6 +8,9 @@
 // that says which of them a conv takes, on which weight planes: scan_amd/ops.py and scan_ops_ext.cpp hold no such rule.
 // No kernel of the convolutions lives here.
 //
+// The weight gradients have their dispatcher here too (scan_conv_wgrad_plan / scan_conv_wgrad_run and, on top of the same two
+// steps, the split families' older entry points); their plan and launch code is conv_wgrad.hip's and conv_mfma.hip's.
+//
 // dgrad reuses the forward kernels: dX = conv3x3(dY, W') with W'[c][t][o] = W[o][8-t][c]
 // (scan_weight_split mode 1 writes the flipped + transposed copy).
 #include "conv_launch.h"
@@ -370,4 +373,73 @@ extern "C" int scan_conv_run(const scan_conv_plan_t* plan, const float* x, const
   if (int rc = conv3x3(name, np, x, xd, Cs, p0, p1, p2, csw, bias, mask, y, main, Ns, relu, stream)) return rc;
   return conv3x3(name, np, x, xd, Cs, at(p0), at(p1), at(p2), csw, bias ? bias + main : nullptr, mask ? mask + main : nullptr,
                  y + main, plan->rem, Ns, relu, stream);
+}
+
+// ---- the weight-gradient dispatcher: plan (host arithmetic, the knobs are read here and only here), run what was planned.
+// The routing was scan_amd/ops.py's _Conv2d.backward and, a second time, scan_ops_ext.cpp's conv_rows_backward.
+extern "C" int scan_conv_wgrad_plan(int32_t pieces, int32_t ksize, int32_t stride, int32_t Cs, int32_t Cout, const scan_pyramid_t* xd,
+                                    const scan_pyramid_t* yd, scan_conv_wgrad_plan_t* plan) {
+  const char* name = "conv_wgrad_plan";
+  SCAN_CHECK_ARG(plan != nullptr, "%s: null plan", name);
+  SCAN_CHECK_ARG(pieces == 0 || pieces == 2 || pieces == 3, "%s: pieces=%d (0, 2 or 3)", name, pieces);
+  if (check_pyramid(name, xd) || check_pyramid(name, yd)) return -1;
+  if (pieces && ksize == 3 && stride == 1) return wgrad_split_plan(name, pieces, 3, 1, Cs, Cout, xd, plan);
+  if (pieces && ksize == 1 && (stride == 1 || stride == 2)) return wgrad_split_plan(name, pieces, 1, stride, Cs, Cout, yd, plan);
+  return wgrad_generic_plan(name, pieces, ksize, stride, Cs, Cout, yd, plan);
+}
+
+extern "C" int scan_conv_wgrad_run(const scan_conv_wgrad_plan_t* plan, const float* x, const scan_pyramid_t* xd, int32_t Cs,
+                                   const float* dy, const scan_pyramid_t* yd, int32_t Cout, int32_t Cout_s, float* dw, float* db,
+                                   int32_t accumulate, float* ws, void* stream) {
+  const char* name = "conv_wgrad_run";
+  SCAN_CHECK_ARG(plan != nullptr, "%s: null plan", name);
+  SCAN_CHECK_ARG((accumulate & ~3) == 0, "%s: accumulate=%d (bit 0: dw, bit 1: db)", name, accumulate);
+  auto run = plan->family == SCAN_WGRAD_GENERIC ? wgrad_generic_run : wgrad_split_run;  // each refuses a plan that is not its own
+  return run(name, *plan, x, xd, Cs, dy, yd, Cout, Cout_s, dw, db, accumulate, ws, stream);
+}
+
+// the split families' entry points of before the plan: plan under the knobs of the moment (the *_ws_floats query, and again the
+// launch), run; one accumulate flag for dw and db
+static int64_t split_ws_floats(int np, int ksize, const scan_pyramid_t* d, int32_t Cs, int32_t Cout) {
+  WgradPlan p;
+  return wgrad_split_plan("wgrad_ws_floats", np, ksize, 1, Cs, Cout, d, &p) ? -1 : p.ws_floats;
+}
+static int split_wgrad(const char* name, int np, int ksize, int32_t stride, const float* x, const scan_pyramid_t* xd, int32_t Cs,
+                       const float* dy, const scan_pyramid_t* yd, int32_t Cout, int32_t Cout_s, float* dw, float* db,
+                       int32_t accumulate, float* ws, void* stream) {
+  WgradPlan p;
+  if (int rc = wgrad_split_plan(name, np, ksize, stride, Cs, Cout, ksize == 3 ? xd : yd, &p)) return rc;
+  return wgrad_split_run(name, p, x, xd, Cs, dy, yd, Cout, Cout_s, dw, db, accumulate ? 3 : 0, ws, stream);
+}
+extern "C" int64_t scan_conv3x3_wgrad_bf16x3_ws_floats(const scan_pyramid_t* d, int32_t Cs, int32_t Cout) {
+  return split_ws_floats(2, 3, d, Cs, Cout);
+}
+extern "C" int64_t scan_conv3x3_wgrad_bf16x6_ws_floats(const scan_pyramid_t* d, int32_t Cs, int32_t Cout) {
+  return split_ws_floats(3, 3, d, Cs, Cout);
+}
+extern "C" int64_t scan_conv1x1_wgrad_bf16x3_ws_floats(const scan_pyramid_t* yd, int32_t Cs, int32_t Cout) {
+  return split_ws_floats(2, 1, yd, Cs, Cout);
+}
+extern "C" int64_t scan_conv1x1_wgrad_bf16x6_ws_floats(const scan_pyramid_t* yd, int32_t Cs, int32_t Cout) {
+  return split_ws_floats(3, 1, yd, Cs, Cout);
+}
+extern "C" int scan_conv3x3_wgrad_bf16x3(const float* x, const scan_pyramid_t* d, int32_t Cs, const float* dy,
+                                         int32_t Cout, int32_t Cout_s, float* dw, float* db, int32_t accumulate,
+                                         float* ws, void* stream) {
+  return split_wgrad("conv3x3_wgrad_bf16x3", 2, 3, 1, x, d, Cs, dy, d, Cout, Cout_s, dw, db, accumulate, ws, stream);
+}
+extern "C" int scan_conv3x3_wgrad_bf16x6(const float* x, const scan_pyramid_t* d, int32_t Cs, const float* dy,
+                                         int32_t Cout, int32_t Cout_s, float* dw, float* db, int32_t accumulate,
+                                         float* ws, void* stream) {
+  return split_wgrad("conv3x3_wgrad_bf16x6", 3, 3, 1, x, d, Cs, dy, d, Cout, Cout_s, dw, db, accumulate, ws, stream);
+}
+extern "C" int scan_conv1x1_wgrad_bf16x3(const float* x, const scan_pyramid_t* xd, int32_t Cs, const float* dy,
+                                         const scan_pyramid_t* yd, int32_t Cout, int32_t Cout_s, int32_t stride,
+                                         float* dw, float* db, int32_t accumulate, float* ws, void* stream) {
+  return split_wgrad("conv1x1_wgrad_bf16x3", 2, 1, stride, x, xd, Cs, dy, yd, Cout, Cout_s, dw, db, accumulate, ws, stream);
+}
+extern "C" int scan_conv1x1_wgrad_bf16x6(const float* x, const scan_pyramid_t* xd, int32_t Cs, const float* dy,
+                                         const scan_pyramid_t* yd, int32_t Cout, int32_t Cout_s, int32_t stride,
+                                         float* dw, float* db, int32_t accumulate, float* ws, void* stream) {
+  return split_wgrad("conv1x1_wgrad_bf16x6", 3, 1, stride, x, xd, Cs, dy, yd, Cout, Cout_s, dw, db, accumulate, ws, stream);
 }

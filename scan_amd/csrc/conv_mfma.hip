@@ -14,7 +14,10 @@
 // fp32 MFMA on gfx950 runs at the fp32 vector rate (64 cycles per 32x32x2 per SIMD),
 // so one MFMA hides many LDS reads; the kernels below therefore favour simple,
 // conflict-light LDS layouts over elaborate swizzles.
+#include <string.h>
+
 #include "common.h"
+#include "conv_launch.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -487,38 +490,83 @@ extern "C" int scan_conv2d_dgrad(const float* dy, const scan_pyramid_t* yd, int3
   return launch_igemm<1>(dy, yd, Cout_s, wt, nullptr, mask, dx, xd, Cin, Cin_s, ksize, stride, 0, as_stream(stream));
 }
 
-static void wgrad_plan(const scan_pyramid_t* yd, int Cin_s, int Cout, int ksize, int* o_tiles, int* c_tiles, int* splits,
-                       int* cps) {
+// ---- column sums (the bias gradient of the generic weight gradient, and scan_colsum)
+static int colsum_blocks(int64_t M) {
+  int64_t b = (M + 255) / 256;
+  if (b > 1024) b = 1024;
+  if (b < 1) b = 1;
+  return (int)b;
+}
+static int colsum_launch(const float* dy, int64_t M, int32_t C, int32_t ld, float* db, int32_t accumulate, float* ws, hipStream_t st) {
+  const int nb = colsum_blocks(M);
+  const int64_t rpb = (M + nb - 1) / nb;
+  hipLaunchKernelGGL(colsum_partial_kernel, dim3(nb), dim3(256), 0, st, dy, M, C, ld, rpb > 0 ? rpb : 1, ws);
+  SCAN_LAUNCH_CHECK("colsum_partial");
+  hipLaunchKernelGGL(colsum_final_kernel, dim3((C + 255) / 256), dim3(256), 0, st, ws, nb, C, db, accumulate);
+  SCAN_LAUNCH_CHECK("colsum_final");
+  return 0;
+}
+extern "C" int64_t scan_colsum_ws_floats(int64_t M, int32_t C) { return (int64_t)colsum_blocks(M) * C; }
+extern "C" int scan_colsum(const float* dy, int64_t M, int32_t C, int32_t ld, float* db, int32_t accumulate, float* ws,
+                           void* stream) {
+  SCAN_CHECK_ARG(dy && db && ws && M >= 0 && C > 0 && ld >= C, "colsum: bad arguments");
+  return colsum_launch(dy, M, C, ld, db, accumulate, ws, as_stream(stream));
+}
+
+// ---- the generic weight gradient: its plan (WgradPlan, conv_launch.h) and launch.  Split-K cut and workspace layout: everything
+// that follows from the plan's shape fields and -- unless choose -- its splits
+static void wgrad_generic_layout(WgradPlan* p, const scan_pyramid_t* yd, bool choose) {
   const int64_t M = yd->row_off[yd->n_levels];
-  const int64_t chunks = (M + BK - 1) / BK;
-  *o_tiles = (Cout + 127) / 128;
-  *c_tiles = (Cin_s + 127) / 128;
-  const int tiles = *o_tiles * *c_tiles * ksize * ksize;
-  int64_t s = 2048 / tiles;
-  if (s < 1) s = 1;
-  const int64_t smax = (chunks + 7) / 8;
-  if (s > smax) s = smax;
-  if (s < 1) s = 1;
-  *cps = (int)((chunks + s - 1) / s);
-  *splits = (int)((chunks + *cps - 1) / *cps);
+  const int64_t chunks = p->chunks = (M + BK - 1) / BK;
+  p->wk = BK;
+  p->slab_taps = p->ksize * p->ksize;
+  p->c_tiles = (p->Cs + 127) / 128;
+  p->n_tiles = ((p->Cout + 127) / 128) * p->c_tiles * p->slab_taps;
+  if (choose) {
+    int64_t s = 2048 / p->n_tiles;
+    if (s < 1) s = 1;
+    const int64_t smax = (chunks + 7) / 8;
+    if (s > smax) s = smax;
+    if (s < 1) s = 1;
+    p->splits = (int)s;
+  }
+  p->cps = (int)((chunks + p->splits - 1) / p->splits);
+  if (choose) p->splits = (int)((chunks + p->cps - 1) / p->cps);
+  // the workspace: [splits][Cout][k * k][Cs] weight slabs, then the column sums' partial rows
+  p->fused_db = 0, p->bias_off = -1;
+  p->colsum_off = p->slab_floats = (int64_t)p->splits * p->Cout * p->slab_taps * p->Cs;
+  p->ws_floats = p->slab_floats + scan_colsum_ws_floats(M, p->Cout);
 }
 
-extern "C" int64_t scan_conv2d_wgrad_ws_floats(const scan_pyramid_t* yd, int32_t Cin_s, int32_t Cout, int32_t ksize) {
-  int ot, ct, sp, cps;
-  wgrad_plan(yd, Cin_s, Cout, ksize, &ot, &ct, &sp, &cps);
-  return (int64_t)sp * Cout * ksize * ksize * Cin_s;
+int wgrad_generic_plan(const char* name, int np, int ksize, int stride, int32_t Cs, int32_t Cout, const scan_pyramid_t* yd, WgradPlan* p) {
+  if (check_pyr(yd, name)) return -1;
+  SCAN_CHECK_ARG(ksize == 1 || ksize == 3 || ksize == 5 || ksize == 7, "%s: ksize must be 1, 3, 5 or 7, got %d", name, ksize);
+  SCAN_CHECK_ARG(stride == 1 || stride == 2, "%s: stride must be 1 or 2, got %d", name, stride);
+  SCAN_CHECK_ARG(Cs > 0 && Cs % 4 == 0, "%s: Cin_s=%d must be a positive multiple of 4", name, Cs);
+  SCAN_CHECK_ARG(Cout > 0, "%s: Cout=%d", name, Cout);
+  *p = WgradPlan{};
+  p->family = SCAN_WGRAD_GENERIC, p->variant = SCAN_WGRAD_FP32;
+  p->pieces = np, p->ksize = ksize, p->stride = stride, p->Cs = Cs, p->Cout = Cout;
+  wgrad_generic_layout(p, yd, true);
+  return 0;
 }
 
-extern "C" int scan_conv2d_wgrad(const float* x, const scan_pyramid_t* xd, int32_t Cin_s, const float* dy,
-                                 const scan_pyramid_t* yd, int32_t Cout, int32_t Cout_s, int32_t ksize, int32_t stride,
-                                 float* dw, int32_t accumulate, float* ws, void* stream) {
-  if (check_pyr(xd, "conv2d_wgrad(x)") || check_pyr(yd, "conv2d_wgrad(dy)")) return -1;
-  if (check_geometry(xd, yd, ksize, stride, "conv2d_wgrad")) return -1;
-  SCAN_CHECK_ARG(Cin_s > 0 && Cin_s % 4 == 0, "conv2d_wgrad: Cin_s=%d must be a positive multiple of 4", Cin_s);
-  SCAN_CHECK_ARG(Cout > 0 && Cout_s >= Cout, "conv2d_wgrad: Cout=%d Cout_s=%d", Cout, Cout_s);
-  SCAN_CHECK_ARG(x && dy && dw && ws, "conv2d_wgrad: null pointer");
-  int ot, ct, sp, cps;
-  wgrad_plan(yd, Cin_s, Cout, ksize, &ot, &ct, &sp, &cps);
+int wgrad_generic_run(const char* name, const WgradPlan& p, const float* x, const scan_pyramid_t* xd, int32_t Cs, const float* dy,
+                      const scan_pyramid_t* yd, int32_t Cout, int32_t Cout_s, float* dw, float* db, int32_t accumulate, float* ws,
+                      void* stream) {
+  if (check_pyr(xd, name) || check_pyr(yd, name)) return -1;
+  // the plan: this family's, and equal to its own layout re-derived on the pyramid passed in
+  SCAN_CHECK_ARG(p.family == SCAN_WGRAD_GENERIC && p.variant == SCAN_WGRAD_FP32 && p.ksize >= 1 && p.ksize <= 7 && p.ksize % 2 == 1 &&
+                     (p.stride == 1 || p.stride == 2) && p.Cs > 0 && p.Cs % 4 == 0 && p.Cout > 0 && p.splits >= 1,
+                 "%s: not a plan scan_conv_wgrad_plan filled", name);
+  WgradPlan q = p;
+  wgrad_generic_layout(&q, yd, false);
+  SCAN_CHECK_ARG(memcmp(&q, &p, sizeof p) == 0, "%s: not a plan scan_conv_wgrad_plan filled for these pyramids (K chunks: planned %lld, here %lld)",
+                 name, (long long)p.chunks, (long long)q.chunks);
+  SCAN_CHECK_ARG(Cs == p.Cs && Cout == p.Cout, "%s: Cs=%d Cout=%d, planned for %d and %d", name, Cs, Cout, p.Cs, p.Cout);
+  if (check_geometry(xd, yd, p.ksize, p.stride, name)) return -1;
+  SCAN_CHECK_ARG(Cout_s >= Cout, "%s: Cout=%d Cout_s=%d", name, Cout, Cout_s);
+  SCAN_CHECK_ARG(x && dy && dw && ws, "%s: null pointer", name);
   hipStream_t st = as_stream(stream);
   const size_t sh = (size_t)4 * BK * LDW * sizeof(float);
   static bool attr_done = false;
@@ -527,13 +575,27 @@ extern "C" int scan_conv2d_wgrad(const float* x, const scan_pyramid_t* xd, int32
                         (int)sh);
     attr_done = true;
   }
-  hipLaunchKernelGGL(conv_wgrad_kernel, dim3(ot * ct * ksize * ksize, sp), dim3(256), sh, st, x, *xd, Cin_s, dy, *yd,
-                     Cout, Cout_s, ksize, stride, ws, ot, ct, cps);
+  hipLaunchKernelGGL(conv_wgrad_kernel, dim3(p.n_tiles, p.splits), dim3(256), sh, st, x, *xd, Cs, dy, *yd, Cout, Cout_s, p.ksize,
+                     p.stride, ws, (Cout + 127) / 128, p.c_tiles, p.cps);
   SCAN_LAUNCH_CHECK("conv_wgrad");
-  const int64_t n = (int64_t)Cout * ksize * ksize * Cin_s;  // multiple of 4 because Cin_s is
-  hipLaunchKernelGGL(slab_reduce_kernel, dim3(grid_for(n / 4, 256)), dim3(256), 0, st, ws, sp, n, dw, accumulate);
+  const int64_t n = (int64_t)Cout * p.slab_taps * Cs;  // multiple of 4 because Cs is
+  hipLaunchKernelGGL(slab_reduce_kernel, dim3(grid_for(n / 4, 256)), dim3(256), 0, st, ws, p.splits, n, dw, accumulate & 1);
   SCAN_LAUNCH_CHECK("slab_reduce");
-  return 0;
+  // the bias gradient: dy's column sums, after the weight gradient on the same stream
+  return db ? colsum_launch(dy, yd->row_off[yd->n_levels], Cout, Cout_s, db, (accumulate >> 1) & 1, ws + p.colsum_off, st) : 0;
+}
+
+// the entry points of before the plan: plan under the knobs of the moment, run; the query reports the weight slabs alone
+extern "C" int64_t scan_conv2d_wgrad_ws_floats(const scan_pyramid_t* yd, int32_t Cin_s, int32_t Cout, int32_t ksize) {
+  WgradPlan p;
+  return wgrad_generic_plan("conv2d_wgrad_ws_floats", 0, ksize, 1, Cin_s, Cout, yd, &p) ? -1 : p.slab_floats;
+}
+extern "C" int scan_conv2d_wgrad(const float* x, const scan_pyramid_t* xd, int32_t Cin_s, const float* dy,
+                                 const scan_pyramid_t* yd, int32_t Cout, int32_t Cout_s, int32_t ksize, int32_t stride,
+                                 float* dw, int32_t accumulate, float* ws, void* stream) {
+  WgradPlan p;
+  if (int rc = wgrad_generic_plan("conv2d_wgrad", 0, ksize, stride, Cin_s, Cout, yd, &p)) return rc;
+  return wgrad_generic_run("conv2d_wgrad", p, x, xd, Cin_s, dy, yd, Cout, Cout_s, dw, nullptr, accumulate ? 1 : 0, ws, stream);
 }
 
 extern "C" int scan_weight_transpose(const float* w, int32_t Cout, int32_t T, int32_t Cin_s, float* wt, int32_t Cout_s,
@@ -542,27 +604,6 @@ extern "C" int scan_weight_transpose(const float* w, int32_t Cout, int32_t T, in
   dim3 grid((Cin_s + 31) / 32, (Cout_s + 31) / 32, T);
   hipLaunchKernelGGL(weight_transpose_kernel, grid, dim3(256), 0, as_stream(stream), w, Cout, T, Cin_s, wt, Cout_s);
   SCAN_LAUNCH_CHECK("weight_transpose");
-  return 0;
-}
-
-static int colsum_blocks(int64_t M) {
-  int64_t b = (M + 255) / 256;
-  if (b > 1024) b = 1024;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-extern "C" int64_t scan_colsum_ws_floats(int64_t M, int32_t C) { return (int64_t)colsum_blocks(M) * C; }
-
-extern "C" int scan_colsum(const float* dy, int64_t M, int32_t C, int32_t ld, float* db, int32_t accumulate, float* ws,
-                           void* stream) {
-  SCAN_CHECK_ARG(dy && db && ws && M >= 0 && C > 0 && ld >= C, "colsum: bad arguments");
-  const int nb = colsum_blocks(M);
-  const int64_t rpb = (M + nb - 1) / nb;
-  hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(colsum_partial_kernel, dim3(nb), dim3(256), 0, st, dy, M, C, ld, rpb > 0 ? rpb : 1, ws);
-  SCAN_LAUNCH_CHECK("colsum_partial");
-  hipLaunchKernelGGL(colsum_final_kernel, dim3((C + 255) / 256), dim3(256), 0, st, ws, nb, C, db, accumulate);
-  SCAN_LAUNCH_CHECK("colsum_final");
   return 0;
 }
 

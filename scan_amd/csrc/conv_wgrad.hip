@@ -23,6 +23,7 @@
 //                          Every 3x3 launch.
 #include "conv_launch.h"
 #include "conv_split.h"
+#include <string.h>
 #include <type_traits>
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
@@ -1010,10 +1011,25 @@ __global__ __launch_bounds__(256) void slab_bias_reduce_wino_kernel(const float*
 // F(2,3) across rows (a third fewer MFMAs); 0 = the direct form, bit for bit the kernels and split-K plan without it
 int g_scan_wgrad_wino = 1;
 
-// chunk table and split-K plan of a launch; wk = pixels per K chunk of the kernel that will run; wino: chunks are row PAIRS
-// and a tile group has four components where the direct form has KX row taps
-static void wgrad_plan(const scan_pyramid_t* d, int Cs, int Cout, int KX, int wk, ChunkTab* ct, int* n_tiles, int* c_tiles,
-                       int* splits, int* cps, bool wino = false) {
+// ---- the plan of a launch (WgradPlan, conv_launch.h).  The knobs that shape it are read in wgrad_variant and, for the splits,
+// in wgrad_layout(choose): nowhere else, and never at launch.
+
+// the kernel a launch with np pieces takes.  1x1 and wgrad_v6 = 0: conv_wgrad_v4_kernel; otherwise the producer / consumer kernel
+// on the wave tile wgrad_tile names, three pieces on its 32 x 64 tile (the one with the temporary accumulator) in the Winograd
+// form unless wgrad_wino = 0; wgrad_tile = 0 and wgrad_v6 = 0 keep their direct kernels
+static int wgrad_variant(int ksize, int np) {
+  if (ksize == 1 || !g_scan_wgrad_v6) return SCAN_WGRAD_V4;
+  if (!((g_scan_wgrad_tile == 0 || g_scan_wgrad_tile == 1) ? g_scan_wgrad_tile == 1 : np == 3)) return SCAN_WGRAD_V6_64X32;
+  return np == 3 && g_scan_wgrad_wino ? SCAN_WGRAD_V6_32X64_WINO : SCAN_WGRAD_V6_32X64;
+}
+
+// chunk table of d, split-K plan and workspace layout: everything that follows from the plan's shape fields, its variant and --
+// unless choose, which takes them from scan_tune "wgrad_wgs" -- its splits
+static void wgrad_layout(WgradPlan* p, const scan_pyramid_t* d, ChunkTab* ct, bool choose) {
+  // wino: chunks are row PAIRS and a tile group has four components where the direct form has KX row taps
+  const bool wino = p->variant == SCAN_WGRAD_V6_32X64_WINO;
+  const int KX = p->ksize, Cs = p->Cs, Cout = p->Cout;
+  const int wk = p->wk = (p->variant != SCAN_WGRAD_V4 && p->pieces == 3) ? 32 : WK;  // pixels per K chunk of the kernel that will run
   ct->chunk_off[0] = 0;
   for (int l = 0; l < SCAN_MAX_LEVELS; ++l) {
     if (l < d->n_levels) {
@@ -1024,44 +1040,43 @@ static void wgrad_plan(const scan_pyramid_t* d, int Cs, int Cout, int KX, int wk
       ct->chunk_off[l + 1] = ct->chunk_off[l];
     }
   }
-  const long long chunks = ct->chunk_off[d->n_levels];
-  *c_tiles = (Cs + 127) / 128;
-  *n_tiles = ((Cout + 127) / 128) * (wino ? 4 : KX) * *c_tiles;
-  // ~3 workgroups per CU in total.  Swept on the device (tower layer, two pieces, us): 256 -> 499, 512 -> 428, 768 -> 355,
-  // 1024 -> 414, 1536 -> 411, 2304 -> 486: fewer splits lengthen each workgroup's serial chunk chain, more splits
-  // cost slab traffic and leave partial rounds
-  // a thin last channel tile (264 / 268 input channels: 8 / 12 live of 128) leaves a third of the workgroups with one column
-  // tile of MFMAs: more, shorter workgroups balance that (class branches 264 -> 1024 3390 -> 3304 us, head_out 1181 -> 1104 at 1280)
-  const int target = (Cs > 128 && Cs % 128 != 0 && Cs % 128 <= 16) ? g_scan_wgrad_wgs * 5 / 3 : g_scan_wgrad_wgs;
-  long long s = target / *n_tiles;
-  if (s < 1) s = 1;
-  const long long smax = (chunks + 7) / 8;
-  if (s > smax) s = smax;
-  s = (s + 7) / 8 * 8;  // groups of 8 splits, one per XCD
-  *cps = (int)((chunks + s - 1) / s);
-  if (*cps < 1) *cps = 1;
-  *splits = (int)s;
+  const long long chunks = p->chunks = ct->chunk_off[d->n_levels];
+  p->c_tiles = (Cs + 127) / 128;
+  p->n_tiles = ((Cout + 127) / 128) * (wino ? 4 : KX) * p->c_tiles;
+  if (choose) {
+    // ~3 workgroups per CU in total.  Swept on the device (tower layer, two pieces, us): 256 -> 499, 512 -> 428, 768 -> 355,
+    // 1024 -> 414, 1536 -> 411, 2304 -> 486: fewer splits lengthen each workgroup's serial chunk chain, more splits
+    // cost slab traffic and leave partial rounds
+    // a thin last channel tile (264 / 268 input channels: 8 / 12 live of 128) leaves a third of the workgroups with one column
+    // tile of MFMAs: more, shorter workgroups balance that (class branches 264 -> 1024 3390 -> 3304 us, head_out 1181 -> 1104 at 1280)
+    const int target = (Cs > 128 && Cs % 128 != 0 && Cs % 128 <= 16) ? g_scan_wgrad_wgs * 5 / 3 : g_scan_wgrad_wgs;
+    long long s = target / p->n_tiles;
+    if (s < 1) s = 1;
+    const long long smax = (chunks + 7) / 8;
+    if (s > smax) s = smax;
+    p->splits = (int)((s + 7) / 8 * 8);  // groups of 8 splits, one per XCD
+  }
+  p->cps = (int)((chunks + p->splits - 1) / p->splits);
+  if (p->cps < 1) p->cps = 1;
+  // the workspace: [splits][Cout][slab_taps][Cs] weight slabs -- 12 (j * 3 + kx), 9 or 1 taps -- then [splits][Cout] bias slabs
+  p->slab_taps = wino ? 12 : KX * KX;
+  p->fused_db = 1, p->colsum_off = -1;
+  p->bias_off = p->slab_floats = (int64_t)p->splits * Cout * p->slab_taps * Cs;
+  p->ws_floats = p->slab_floats + (int64_t)p->splits * Cout;
 }
 
-// pixels per K chunk of the kernel a 3x3 launch with np pieces takes
-static inline int wgrad3_wk(int np) { return (g_scan_wgrad_v6 && np == 3) ? 32 : WK; }
-
-// whether a 3x3 launch with np pieces takes the Winograd form: three pieces on the producer / consumer kernel's 32 x 64 tile (the
-// one with the temporary accumulator); wgrad_tile = 0 and wgrad_v6 = 0 keep their direct kernels
-static inline bool wgrad3_wino(int np) { return np == 3 && g_scan_wgrad_v6 && g_scan_wgrad_wino && g_scan_wgrad_tile != 0; }
-
-static int64_t wgrad3_ws_floats(int np, const scan_pyramid_t* d, int32_t Cs, int32_t Cout) {
+int wgrad_split_plan(const char* name, int np, int ksize, int stride, int32_t Cs, int32_t Cout, const scan_pyramid_t* d, WgradPlan* p) {
+  SCAN_CHECK_ARG(d && d->n_levels >= 1 && d->n_levels <= SCAN_MAX_LEVELS && d->n_images >= 1, "%s: bad pyramid", name);
+  SCAN_CHECK_ARG(stride == 1 || (stride == 2 && ksize == 1), "%s: stride must be 1 or 2, got %d", name, stride);
+  SCAN_CHECK_ARG(Cs > 0 && Cs % 4 == 0, "%s: Cs=%d must be a positive multiple of 4", name, Cs);
+  SCAN_CHECK_ARG(Cout > 0, "%s: Cout=%d", name, Cout);
+  *p = WgradPlan{};
+  p->family = ksize == 3 ? SCAN_WGRAD_SPLIT3X3 : SCAN_WGRAD_SPLIT1X1;
+  p->pieces = np, p->ksize = ksize, p->stride = stride, p->Cs = Cs, p->Cout = Cout;
+  p->variant = wgrad_variant(ksize, np);
   ChunkTab ct;
-  int nt, ctl, sp, cps;
-  const bool wino = wgrad3_wino(np);
-  wgrad_plan(d, Cs, Cout, 3, wgrad3_wk(np), &ct, &nt, &ctl, &sp, &cps, wino);
-  return (int64_t)sp * Cout * (wino ? 12 : 9) * Cs + (int64_t)sp * Cout;  // slabs of 12 (j * 3 + kx) or 9 taps + bias slabs
-}
-extern "C" int64_t scan_conv3x3_wgrad_bf16x3_ws_floats(const scan_pyramid_t* d, int32_t Cs, int32_t Cout) {
-  return wgrad3_ws_floats(2, d, Cs, Cout);
-}
-extern "C" int64_t scan_conv3x3_wgrad_bf16x6_ws_floats(const scan_pyramid_t* d, int32_t Cs, int32_t Cout) {
-  return wgrad3_ws_floats(3, d, Cs, Cout);
+  wgrad_layout(p, d, &ct, true);
+  return 0;
 }
 
 template <typename K>
@@ -1069,22 +1084,46 @@ static void set_lds(K kernel, size_t bytes) {
   hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
+// a validated launch; d: the pyramid the K chunks walk (3x3: xd itself)
+struct WgradArgs {
+  const WgradPlan& p;
+  const ChunkTab& ct;
+  const float *x, *dy;
+  const scan_pyramid_t *xd, *d;
+  int32_t Cout_s, accumulate;
+  float *dw, *db, *ws;
+  hipStream_t st;
+  float* bias_slab() const { return db ? ws + p.bias_off : nullptr; }
+};
+// the argument lists of the two kernel signatures
+template <typename K>
+static void launch_v6(K kernel, size_t lds, const WgradArgs& a) {
+  hipLaunchKernelGGL(kernel, dim3(a.p.n_tiles * a.p.splits), dim3(W6_THREADS), lds, a.st, a.x, *a.d, a.p.Cs, a.dy, a.p.Cout, a.Cout_s,
+                     a.ws, a.bias_slab(), a.ct, a.p.n_tiles, a.p.c_tiles, a.p.cps, a.p.splits, g_scan_wgrad_prio);
+}
+template <typename K>
+static void launch_v4(K kernel, size_t lds, const WgradArgs& a) {
+  hipLaunchKernelGGL(kernel, dim3(a.p.n_tiles * a.p.splits), dim3(512), lds, a.st, a.x, *a.d, a.p.Cs, a.dy, a.p.Cout, a.Cout_s, a.ws,
+                     a.bias_slab(), a.ct, a.p.n_tiles, a.p.c_tiles, a.p.cps, a.p.splits, *a.xd);
+}
+// one launch reduces the weight slabs and (last block) the bias slabs
+static int wgrad_reduce(const WgradArgs& a) {
+  const int32_t Cs = a.p.Cs, Cout = a.p.Cout;
+  const int64_t n = (int64_t)Cout * a.p.ksize * a.p.ksize * Cs;
+  if (a.p.variant == SCAN_WGRAD_V6_32X64_WINO)
+    hipLaunchKernelGGL(slab_bias_reduce_wino_kernel, dim3(grid_for((int64_t)Cout * 3 * (Cs / 4), 256) + (a.db ? 1 : 0)), dim3(256), 0,
+                       a.st, a.ws, a.p.splits, Cout, Cs, a.dw, a.bias_slab(), a.db, a.accumulate);
+  else
+    hipLaunchKernelGGL(slab_bias_reduce_kernel, dim3(grid_for(n / 4, 256) + (a.db ? 1 : 0)), dim3(256), 0, a.st, a.ws, a.p.splits, n,
+                       a.dw, a.bias_slab(), Cout, a.db, a.accumulate);
+  SCAN_LAUNCH_CHECK("slab_bias_reduce");
+  return 0;
+}
+
 template <int NP>
-static int wgrad3_launch(const float* x, const scan_pyramid_t* d, int32_t Cs, const float* dy, int32_t Cout, int32_t Cout_s,
-                         float* dw, float* db, int32_t accumulate, float* ws, void* stream) {
-  const char* name = NP == 2 ? "conv3x3_wgrad_bf16x3" : "conv3x3_wgrad_bf16x6";
-  SCAN_CHECK_ARG(d && d->n_levels >= 1 && d->n_levels <= SCAN_MAX_LEVELS && d->n_images >= 1, "%s: bad pyramid", name);
-  SCAN_CHECK_ARG(Cs > 0 && Cs % 4 == 0, "%s: Cs=%d must be a positive multiple of 4", name, Cs);
-  SCAN_CHECK_ARG(Cout > 0 && Cout_s >= Cout && Cout_s % 4 == 0, "%s: Cout=%d Cout_s=%d (Cout_s a multiple of 4)", name, Cout, Cout_s);
-  SCAN_CHECK_ARG(x && dy && dw && ws, "%s: null pointer", name);
+static int wgrad3_launch(const char* name, const WgradArgs& a) {
   constexpr int WK6 = NP == 3 ? 32 : WK;
-  ChunkTab ct;
-  int nt, ctl, sp, cps;
-  const bool wino = wgrad3_wino(NP);
-  wgrad_plan(d, Cs, Cout, 3, wgrad3_wk(NP), &ct, &nt, &ctl, &sp, &cps, wino);
-  hipStream_t st = as_stream(stream);
-  float* bias_slab = db ? ws + (int64_t)sp * Cout * (wino ? 12 : 9) * Cs : nullptr;
-  if (g_scan_wgrad_v6) {
+  if (a.p.variant != SCAN_WGRAD_V4) {
     constexpr size_t sh6 = (size_t)2 * W6STAGE(NP, WK6, 3) * sizeof(__bf16);  // the Winograd instance stages the same LDS image
     static_assert(sh6 <= 160 * 1024, "LDS: 160 KB per CU");
     static bool done = false;
@@ -1094,16 +1133,12 @@ static int wgrad3_launch(const float* x, const scan_pyramid_t* d, int32_t Cs, co
       if constexpr (NP == 3) set_lds(conv_wgrad_v6_kernel<NP, WK6, 3, 2, 4, true>, sh6);
       done = true;
     }
-    if (wino) {  // only ever true for NP == 3 (wgrad3_wino)
-      if constexpr (NP == 3)
-        hipLaunchKernelGGL((conv_wgrad_v6_kernel<NP, WK6, 3, 2, 4, true>), dim3(nt * sp), dim3(W6_THREADS), sh6, st, x, *d, Cs, dy, Cout,
-                           Cout_s, ws, bias_slab, ct, nt, ctl, cps, sp, g_scan_wgrad_prio);
-    } else if ((g_scan_wgrad_tile == 0 || g_scan_wgrad_tile == 1) ? g_scan_wgrad_tile == 1 : NP == 3)
-      hipLaunchKernelGGL((conv_wgrad_v6_kernel<NP, WK6, 3, 2, 4>), dim3(nt * sp), dim3(W6_THREADS), sh6, st, x, *d, Cs, dy, Cout, Cout_s,
-                         ws, bias_slab, ct, nt, ctl, cps, sp, g_scan_wgrad_prio);
+    if (a.p.variant == SCAN_WGRAD_V6_32X64_WINO) {  // three pieces only (wgrad_variant; wgrad_split_run checks)
+      if constexpr (NP == 3) launch_v6(conv_wgrad_v6_kernel<NP, WK6, 3, 2, 4, true>, sh6, a);
+    } else if (a.p.variant == SCAN_WGRAD_V6_32X64)
+      launch_v6(conv_wgrad_v6_kernel<NP, WK6, 3, 2, 4>, sh6, a);
     else
-      hipLaunchKernelGGL((conv_wgrad_v6_kernel<NP, WK6, 3, 4, 2>), dim3(nt * sp), dim3(W6_THREADS), sh6, st, x, *d, Cs, dy, Cout, Cout_s,
-                         ws, bias_slab, ct, nt, ctl, cps, sp, g_scan_wgrad_prio);
+      launch_v6(conv_wgrad_v6_kernel<NP, WK6, 3, 4, 2>, sh6, a);
   } else {
     constexpr size_t sh = (size_t)WBUF(NP, 3) * sizeof(__bf16);
     static_assert(sh <= 160 * 1024, "LDS: 160 KB per CU");
@@ -1112,63 +1147,15 @@ static int wgrad3_launch(const float* x, const scan_pyramid_t* d, int32_t Cs, co
       set_lds(conv_wgrad_v4_kernel<NP, 3, 1>, sh);
       done = true;
     }
-    hipLaunchKernelGGL((conv_wgrad_v4_kernel<NP, 3, 1>), dim3(nt * sp), dim3(512), sh, st, x, *d, Cs, dy, Cout, Cout_s, ws,
-                       bias_slab, ct, nt, ctl, cps, sp, *d);
+    launch_v4(conv_wgrad_v4_kernel<NP, 3, 1>, sh, a);
   }
   SCAN_LAUNCH_CHECK(name);
-  // one launch reduces the weight slabs and (last block) the bias slabs
-  const int64_t n = (int64_t)Cout * 9 * Cs;
-  if (wino)
-    hipLaunchKernelGGL(slab_bias_reduce_wino_kernel, dim3(grid_for((int64_t)Cout * 3 * (Cs / 4), 256) + (db ? 1 : 0)), dim3(256), 0,
-                       st, ws, sp, Cout, Cs, dw, bias_slab, db, accumulate);
-  else
-    hipLaunchKernelGGL(slab_bias_reduce_kernel, dim3(grid_for(n / 4, 256) + (db ? 1 : 0)), dim3(256), 0, st, ws, sp, n, dw,
-                       bias_slab, Cout, db, accumulate);
-  SCAN_LAUNCH_CHECK("slab_bias_reduce");
-  return 0;
-}
-
-extern "C" int scan_conv3x3_wgrad_bf16x3(const float* x, const scan_pyramid_t* d, int32_t Cs, const float* dy,
-                                         int32_t Cout, int32_t Cout_s, float* dw, float* db, int32_t accumulate,
-                                         float* ws, void* stream) {
-  return wgrad3_launch<2>(x, d, Cs, dy, Cout, Cout_s, dw, db, accumulate, ws, stream);
-}
-extern "C" int scan_conv3x3_wgrad_bf16x6(const float* x, const scan_pyramid_t* d, int32_t Cs, const float* dy,
-                                         int32_t Cout, int32_t Cout_s, float* dw, float* db, int32_t accumulate,
-                                         float* ws, void* stream) {
-  return wgrad3_launch<3>(x, d, Cs, dy, Cout, Cout_s, dw, db, accumulate, ws, stream);
+  return wgrad_reduce(a);
 }
 
 // ---- 1x1 weight gradient (stride 1 or 2): dw[Cout][1][Cs] = sum_pixels dY^T X, conv_wgrad_v4_kernel with one tap.
-extern "C" int64_t scan_conv1x1_wgrad_bf16x3_ws_floats(const scan_pyramid_t* yd, int32_t Cs, int32_t Cout) {
-  ChunkTab ct;
-  int nt, ctl, sp, cps;
-  wgrad_plan(yd, Cs, Cout, 1, WK, &ct, &nt, &ctl, &sp, &cps);
-  return (int64_t)sp * Cout * Cs + (int64_t)sp * Cout;
-}
-extern "C" int64_t scan_conv1x1_wgrad_bf16x6_ws_floats(const scan_pyramid_t* yd, int32_t Cs, int32_t Cout) {
-  return scan_conv1x1_wgrad_bf16x3_ws_floats(yd, Cs, Cout);
-}
-
 template <int NP>
-static int wgrad1_launch(const float* x, const scan_pyramid_t* xd, int32_t Cs, const float* dy, const scan_pyramid_t* yd,
-                         int32_t Cout, int32_t Cout_s, int32_t stride, float* dw, float* db, int32_t accumulate, float* ws,
-                         void* stream) {
-  const char* name = NP == 2 ? "conv1x1_wgrad_bf16x3" : "conv1x1_wgrad_bf16x6";
-  SCAN_CHECK_ARG(xd && yd && yd->n_levels >= 1 && yd->n_levels <= SCAN_MAX_LEVELS && yd->n_images >= 1 &&
-                     xd->n_levels == yd->n_levels && xd->n_images == yd->n_images,
-                 "%s: bad pyramids", name);
-  SCAN_CHECK_ARG(stride == 1 || stride == 2, "%s: stride must be 1 or 2, got %d", name, stride);
-  for (int l = 0; l < yd->n_levels; ++l)
-    SCAN_CHECK_ARG((xd->h[l] - 1) / stride + 1 == yd->h[l] && (xd->w[l] - 1) / stride + 1 == yd->w[l],
-                   "%s: level %d sizes do not match stride %d", name, l, stride);
-  SCAN_CHECK_ARG(Cs > 0 && Cs % 4 == 0, "%s: Cs=%d must be a positive multiple of 4", name, Cs);
-  SCAN_CHECK_ARG(Cout > 0 && Cout_s >= Cout && Cout_s % 4 == 0, "%s: Cout=%d Cout_s=%d (Cout_s a multiple of 4)", name, Cout, Cout_s);
-  SCAN_CHECK_ARG(x && dy && dw && ws, "%s: null pointer", name);
-  ChunkTab ct;
-  int nt, ctl, sp, cps;
-  wgrad_plan(yd, Cs, Cout, 1, WK, &ct, &nt, &ctl, &sp, &cps);
-  hipStream_t st = as_stream(stream);
+static int wgrad1_launch(const char* name, const WgradArgs& a) {
   constexpr size_t sh = (size_t)WBUF(NP, 1) * sizeof(__bf16);
   static bool done = false;
   if (!done) {
@@ -1176,28 +1163,42 @@ static int wgrad1_launch(const float* x, const scan_pyramid_t* xd, int32_t Cs, c
     set_lds(conv_wgrad_v4_kernel<NP, 1, 2>, sh);
     done = true;
   }
-  float* bias_slab = db ? ws + (int64_t)sp * Cout * Cs : nullptr;
-  if (stride == 1)
-    hipLaunchKernelGGL((conv_wgrad_v4_kernel<NP, 1, 1>), dim3(nt * sp), dim3(512), sh, st, x, *yd, Cs, dy, Cout, Cout_s, ws,
-                       bias_slab, ct, nt, ctl, cps, sp, *xd);
+  if (a.p.stride == 1)
+    launch_v4(conv_wgrad_v4_kernel<NP, 1, 1>, sh, a);
   else
-    hipLaunchKernelGGL((conv_wgrad_v4_kernel<NP, 1, 2>), dim3(nt * sp), dim3(512), sh, st, x, *yd, Cs, dy, Cout, Cout_s, ws,
-                       bias_slab, ct, nt, ctl, cps, sp, *xd);
+    launch_v4(conv_wgrad_v4_kernel<NP, 1, 2>, sh, a);
   SCAN_LAUNCH_CHECK(name);
-  const int64_t n = (int64_t)Cout * Cs;
-  hipLaunchKernelGGL(slab_bias_reduce_kernel, dim3(grid_for(n / 4, 256) + (db ? 1 : 0)), dim3(256), 0, st, ws, sp, n, dw,
-                     bias_slab, Cout, db, accumulate);
-  SCAN_LAUNCH_CHECK("slab_bias_reduce");
-  return 0;
+  return wgrad_reduce(a);
 }
 
-extern "C" int scan_conv1x1_wgrad_bf16x3(const float* x, const scan_pyramid_t* xd, int32_t Cs, const float* dy,
-                                         const scan_pyramid_t* yd, int32_t Cout, int32_t Cout_s, int32_t stride,
-                                         float* dw, float* db, int32_t accumulate, float* ws, void* stream) {
-  return wgrad1_launch<2>(x, xd, Cs, dy, yd, Cout, Cout_s, stride, dw, db, accumulate, ws, stream);
-}
-extern "C" int scan_conv1x1_wgrad_bf16x6(const float* x, const scan_pyramid_t* xd, int32_t Cs, const float* dy,
-                                         const scan_pyramid_t* yd, int32_t Cout, int32_t Cout_s, int32_t stride,
-                                         float* dw, float* db, int32_t accumulate, float* ws, void* stream) {
-  return wgrad1_launch<3>(x, xd, Cs, dy, yd, Cout, Cout_s, stride, dw, db, accumulate, ws, stream);
+int wgrad_split_run(const char* name, const WgradPlan& p, const float* x, const scan_pyramid_t* xd, int32_t Cs, const float* dy,
+                    const scan_pyramid_t* yd, int32_t Cout, int32_t Cout_s, float* dw, float* db, int32_t accumulate, float* ws,
+                    void* stream) {
+  const bool k3 = p.family == SCAN_WGRAD_SPLIT3X3;
+  const scan_pyramid_t* d = k3 ? xd : yd;
+  SCAN_CHECK_ARG(d && d->n_levels >= 1 && d->n_levels <= SCAN_MAX_LEVELS && d->n_images >= 1 &&
+                     (k3 || (xd && xd->n_levels == yd->n_levels && xd->n_images == yd->n_images)),
+                 "%s: bad pyramid%s", name, k3 ? "" : "s");
+  // the plan: one of this file's families, and equal to its own layout re-derived on the pyramid passed in
+  const bool known = (p.pieces == 2 || p.pieces == 3) && p.Cs > 0 && p.Cs % 4 == 0 && p.Cout > 0 && p.splits >= 1 &&
+                     (k3 ? p.ksize == 3 && p.stride == 1 && p.variant >= SCAN_WGRAD_V4 && p.variant <= SCAN_WGRAD_V6_32X64_WINO &&
+                               (p.variant != SCAN_WGRAD_V6_32X64_WINO || p.pieces == 3)
+                         : p.family == SCAN_WGRAD_SPLIT1X1 && p.ksize == 1 && (p.stride == 1 || p.stride == 2) && p.variant == SCAN_WGRAD_V4);
+  SCAN_CHECK_ARG(known, "%s: not a plan scan_conv_wgrad_plan filled", name);
+  ChunkTab ct;
+  WgradPlan q = p;
+  wgrad_layout(&q, d, &ct, false);
+  SCAN_CHECK_ARG(memcmp(&q, &p, sizeof p) == 0, "%s: not a plan scan_conv_wgrad_plan filled for these pyramids (K chunks: planned %lld, here %lld)",
+                 name, (long long)p.chunks, (long long)q.chunks);
+  SCAN_CHECK_ARG(Cs == p.Cs && Cout == p.Cout, "%s: Cs=%d Cout=%d, planned for %d and %d", name, Cs, Cout, p.Cs, p.Cout);
+  if (!k3)
+    for (int l = 0; l < yd->n_levels; ++l)
+      SCAN_CHECK_ARG((xd->h[l] - 1) / p.stride + 1 == yd->h[l] && (xd->w[l] - 1) / p.stride + 1 == yd->w[l],
+                     "%s: level %d sizes do not match stride %d", name, l, p.stride);
+  SCAN_CHECK_ARG(Cout_s >= Cout && Cout_s % 4 == 0, "%s: Cout=%d Cout_s=%d (Cout_s a multiple of 4)", name, Cout, Cout_s);
+  SCAN_CHECK_ARG(x && dy && dw && ws, "%s: null pointer", name);
+  SCAN_CHECK_ARG(!db || (accumulate & 1) == ((accumulate >> 1) & 1), "%s: dw and db share one accumulate flag, got %d", name, accumulate);
+  const WgradArgs a{p, ct, x, dy, xd, d, Cout_s, accumulate & 1, dw, db, ws, as_stream(stream)};
+  if (k3) return p.pieces == 2 ? wgrad3_launch<2>(name, a) : wgrad3_launch<3>(name, a);
+  return p.pieces == 2 ? wgrad1_launch<2>(name, a) : wgrad1_launch<3>(name, a);
 }

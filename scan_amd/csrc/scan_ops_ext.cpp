@@ -224,29 +224,13 @@ std::vector<at::Tensor> conv_rows_backward(const at::Tensor& xr, const at::Tenso
   if (need_dw || need_db) {
     dw = at::empty({g.cout, T, g.cs}, xr.options());
     if (need_db) db = at::empty({g.cout}, xr.options());
-    if (g.k == 3 && g.stride == 1) {
-      at::Tensor ws = at::empty({scan_conv3x3_wgrad_bf16x6_ws_floats(&xd, (int32_t)g.cs, (int32_t)g.cout)}, xr.options());
-      check(scan_conv3x3_wgrad_bf16x6(xr.data_ptr<float>(), &xd, (int32_t)g.cs, dyr.data_ptr<float>(), (int32_t)g.cout, (int32_t)g.ns,
-                                      dw.data_ptr<float>(), need_db ? db.data_ptr<float>() : nullptr, 0, ws.data_ptr<float>(), st),
-            "scan_conv3x3_wgrad_bf16x6");
-    } else if (g.k == 1) {
-      at::Tensor ws = at::empty({scan_conv1x1_wgrad_bf16x6_ws_floats(&yd, (int32_t)g.cs, (int32_t)g.cout)}, xr.options());
-      check(scan_conv1x1_wgrad_bf16x6(xr.data_ptr<float>(), &xd, (int32_t)g.cs, dyr.data_ptr<float>(), &yd, (int32_t)g.cout, (int32_t)g.ns,
-                                      (int32_t)g.stride, dw.data_ptr<float>(), need_db ? db.data_ptr<float>() : nullptr, 0,
-                                      ws.data_ptr<float>(), st),
-            "scan_conv1x1_wgrad_bf16x6");
-    } else {
-      at::Tensor ws = at::empty({scan_conv2d_wgrad_ws_floats(&yd, (int32_t)g.cs, (int32_t)g.cout, 3)}, xr.options());
-      check(scan_conv2d_wgrad(xr.data_ptr<float>(), &xd, (int32_t)g.cs, dyr.data_ptr<float>(), &yd, (int32_t)g.cout, (int32_t)g.ns, 3, 2,
-                              dw.data_ptr<float>(), 0, ws.data_ptr<float>(), st),
-            "scan_conv2d_wgrad");
-      if (need_db) {
-        at::Tensor cws = at::empty({scan_colsum_ws_floats(yd.row_off[1], (int32_t)g.cout)}, xr.options());
-        check(scan_colsum(dyr.data_ptr<float>(), yd.row_off[1], (int32_t)g.cout, (int32_t)g.ns, db.data_ptr<float>(), 0,
-                          cws.data_ptr<float>(), st),
-              "scan_colsum");
-      }
-    }
+    // family, kernel, split-K cut and workspace as the library plans them (the launches scan_amd.ops makes: bit-identical)
+    scan_conv_wgrad_plan_t plan;
+    check(scan_conv_wgrad_plan(3, (int32_t)g.k, (int32_t)g.stride, (int32_t)g.cs, (int32_t)g.cout, &xd, &yd, &plan), "scan_conv_wgrad_plan");
+    at::Tensor ws = at::empty({plan.ws_floats}, xr.options());
+    check(scan_conv_wgrad_run(&plan, xr.data_ptr<float>(), &xd, (int32_t)g.cs, dyr.data_ptr<float>(), &yd, (int32_t)g.cout, (int32_t)g.ns,
+                              dw.data_ptr<float>(), need_db ? db.data_ptr<float>() : nullptr, 0, ws.data_ptr<float>(), st),
+          "scan_conv_wgrad_run");
   }
   return {dx, dw, db};
 }

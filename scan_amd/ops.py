@@ -553,50 +553,43 @@ class _Conv2d(torch.autograd.Function):
         direct_w = ctx.wgrad_buf is not None
         direct_b = direct_w and ctx.bgrad_buf is not None
         want_db = has_bias and ctx.needs_input_grad[2]
-        db_done = False
-
-        def wgrad(sym, label, ws_floats, geom, fused_db):
-            """one weight-gradient launch on the current stream: dw (and db, where the kernel fuses the column sums of dy)
-            straight into the flat gradient buffers or into fresh tensors -> dw for autograd (None when accumulated in place)"""
-            nonlocal db, db_done
-            ws = x.new_empty((ws_floats,))
-            dwp = ctx.wgrad_buf if direct_w else x.new_empty((cout, T, cs))
-            ev = kernel_timer.begin(label, 2.0 * oshape.rows * cout * T * cin)
-            if fused_db and want_db:
-                db = ctx.bgrad_buf if direct_b else x.new_empty((cout,))
-                db_done = True
-            call(sym, _ptr(x), shape.ref(), cs, _ptr(dy), *geom, _ptr(dwp), *([_ptr(db) if want_db else None] if fused_db else []),
-                 int(direct_w), _ptr(ws), _stream())
-            kernel_timer.end(ev)
-            if fused_db and want_db and direct_w and not direct_b:
-                raise RuntimeError("conv2d: flat weight gradient without a flat bias gradient")
-            if direct_b:
-                db = None
-            return None if direct_w else unpack_weight_grad(dwp, weight)
-
-        if ctx.needs_input_grad[1] and fast and ksize == 3:
-            side = WGRAD_STREAM if (direct_w and (direct_b or not want_db) and not kernel_timer.enabled) else None
+        if ctx.needs_input_grad[1]:
+            # family, kernel, split-K cut and workspace come from the library (scan_conv_wgrad_plan, include/scan_hip.h): the
+            # compiled operators (csrc/scan_ops_ext.cpp) ask the same function
+            plan = _lib.WgradPlan()
+            call("scan_conv_wgrad_plan", SPLIT_MODES[sfx] if fast else 0, ksize, stride, cs, cout, shape.ref(), oshape.ref(),
+                 ctypes.byref(plan))
+            split3 = plan.family == _lib.WGRAD_SPLIT3X3
+            label = "conv_wgrad" if plan.family == _lib.WGRAD_GENERIC else ("conv3x3_%s_wgrad" if split3 else "conv1x1_%s_wgrad") % sfx
+            side = WGRAD_STREAM if (split3 and direct_w and (direct_b or not want_db) and not kernel_timer.enabled) else None
             if side is not None:  # in place into the flat gradient buffers, nothing returned to autograd: off the chain
                 side.wait_stream(torch.cuda.current_stream())
                 x.record_stream(side)
                 dy.record_stream(side)
             with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
-                dw = wgrad("scan_conv3x3_wgrad_" + sfx, "conv3x3_%s_wgrad" % sfx,
-                           query("scan_conv3x3_wgrad_%s_ws_floats" % sfx, shape.ref(), cs, cout), (cout, cout_s), True)
-        elif ctx.needs_input_grad[1] and fast:  # 1x1, stride 1 or 2
-            dw = wgrad("scan_conv1x1_wgrad_" + sfx, "conv1x1_%s_wgrad" % sfx,
-                       query("scan_conv1x1_wgrad_%s_ws_floats" % sfx, oshape.ref(), cs, cout),
-                       (oshape.ref(), cout, cout_s, stride), True)
-        elif ctx.needs_input_grad[1]:
-            dw = wgrad("scan_conv2d_wgrad", "conv_wgrad", query("scan_conv2d_wgrad_ws_floats", oshape.ref(), cs, cout, ksize),
-                       (oshape.ref(), cout, cout_s, ksize, stride), False)
-        if has_bias and ctx.needs_input_grad[2] and not db_done:
+                # one launch sequence on the current stream: dw and db (the split kernels fuse dy's column sums, the generic one
+                # is followed by them) straight into the flat gradient buffers or into fresh tensors for autograd
+                ws = x.new_empty((plan.ws_floats,))
+                dwp = ctx.wgrad_buf if direct_w else x.new_empty((cout, T, cs))
+                if want_db:
+                    db = ctx.bgrad_buf if direct_b else x.new_empty((cout,))
+                ev = kernel_timer.begin(label, 2.0 * oshape.rows * cout * T * cin)
+                try:
+                    call("scan_conv_wgrad_run", ctypes.byref(plan), _ptr(x), shape.ref(), cs, _ptr(dy), oshape.ref(), cout, cout_s,
+                         _ptr(dwp), _ptr(db), int(direct_w) | 2 * int(direct_b), _ptr(ws), _stream())
+                except RuntimeError:
+                    if plan.fused_db and want_db and direct_w and not direct_b:  # the library refuses differing accumulate bits
+                        raise RuntimeError("conv2d: flat weight gradient without a flat bias gradient") from None
+                    raise
+                kernel_timer.end(ev)
+            dw = None if direct_w else unpack_weight_grad(dwp, weight)
+        elif want_db:  # a bias gradient alone (frozen weight): dy's column sums, no weight-gradient launch
             M = dy.shape[0]
             ws = x.new_empty((query("scan_colsum_ws_floats", M, cout),))
             db = ctx.bgrad_buf if direct_b else x.new_empty((cout,))
             call("scan_colsum", _ptr(dy), M, cout, cout_s, _ptr(db), int(direct_b), _ptr(ws), st)
-            if direct_b:
-                db = None
+        if direct_b:
+            db = None
         return dx, dw, db, None, None, None, None, None, None, None, None, None
 
 

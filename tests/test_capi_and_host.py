@@ -73,6 +73,49 @@ def test_argument_validation_without_device():
             refused(run(plan(72, 36, _lib.CONV_POOL, pieces=2), p2=None), "single-level pyramid")
     finally:
         L.scan_tune(b"conv_wino", old)
+    # the weight-gradient dispatcher: the same, and everything that could write past a workspace is refused
+    def wplan(pieces=3, ksize=3, stride=1, cs=36, cout=72, pyr=two):
+        p = _lib.WgradPlan()
+        _lib.call("scan_conv_wgrad_plan", pieces, ksize, stride, cs, cout, pyr.ref(), pyr.conv_out(ksize, stride).ref(), ctypes.byref(p))
+        return p
+
+    def wrun(p, pyr=two, cs=36, cout=72, db=None, acc=0, ws=fake):
+        out = pyr.conv_out(p.ksize, p.stride) if p is not None and p.ksize in (1, 3, 5, 7) and p.stride in (1, 2) else pyr
+        return L.scan_conv_wgrad_run(ctypes.byref(p) if p is not None else None, fake, pyr.ref(), cs, fake, out.ref(), cout, cout, fake,
+                                     db, acc, ws, None)
+
+    def edited(p, **kw):
+        for k, v in kw.items():
+            setattr(p, k, v)
+        return p
+
+    refused(wrun(None), "null plan")
+    assert L.scan_conv_wgrad_plan(3, 3, 1, 36, 72, two.ref(), two.ref(), None) == -1
+    refused(L.scan_conv_wgrad_plan(3, 4, 1, 36, 72, two.ref(), two.ref(), ctypes.byref(_lib.WgradPlan())), "ksize must be 1, 3, 5 or 7")
+    refused(L.scan_conv_wgrad_plan(3, 3, 3, 36, 72, two.ref(), two.ref(), ctypes.byref(_lib.WgradPlan())), "stride must be 1 or 2")
+    refused(L.scan_conv_wgrad_plan(3, 1, 4, 36, 72, two.ref(), two.ref(), ctypes.byref(_lib.WgradPlan())), "stride must be 1 or 2")
+    refused(L.scan_conv_wgrad_plan(1, 3, 1, 36, 72, two.ref(), two.ref(), ctypes.byref(_lib.WgradPlan())), "pieces")
+    refused(L.scan_conv_wgrad_plan(3, 3, 1, 38, 72, two.ref(), two.ref(), ctypes.byref(_lib.WgradPlan())), "multiple of 4")
+    for kw in (dict(), dict(ksize=1, stride=2), dict(pieces=0), dict(ksize=3, stride=2), dict(ksize=7, stride=2, cs=4)):
+        cs = kw.get("cs", 36)
+        assert wplan(**kw).family == (3 if kw.get("pieces") == 0 or kw.get("ksize", 3) == 7 or kw == dict(ksize=3, stride=2)
+                                      else 2 if kw.get("ksize") == 1 else 1)
+        refused(wrun(_lib.WgradPlan(), cs=cs), "not a plan")                                    # zeroed
+        refused(wrun(edited(wplan(**kw), splits=wplan(**kw).splits + 8), cs=cs), "not a plan")  # more slabs than were sized
+        refused(wrun(edited(wplan(**kw), splits=0), cs=cs), "not a plan")
+        refused(wrun(edited(wplan(**kw), ws_floats=16), cs=cs), "not a plan")
+        refused(wrun(edited(wplan(**kw), slab_taps=12 if wplan(**kw).slab_taps != 12 else 9), cs=cs), "not a plan")
+        refused(wrun(edited(wplan(**kw), cps=1), cs=cs), "not a plan")
+        refused(wrun(edited(wplan(**kw), variant=1 if wplan(**kw).variant != 1 else 0), cs=cs), "not a plan")
+        refused(wrun(edited(wplan(**kw), family=4), cs=cs), "not a plan")
+        refused(wrun(wplan(**kw), pyr=ops.PyramidShape(2, [(12, 20), (40, 10)]), cs=cs), r"planned (\d+), here (?!\1\))\d+")  # another pyramid than planned
+        refused(wrun(wplan(**kw), cs=cs + 4), "planned for")
+        refused(wrun(wplan(**kw), cs=cs, cout=76), "planned for")
+        refused(wrun(wplan(**kw), cs=cs, ws=None), "null pointer")
+        refused(wrun(wplan(**kw), cs=cs, acc=4), "accumulate")
+        if wplan(**kw).fused_db:  # one flag for dw and db
+            refused(wrun(wplan(**kw), cs=cs, db=fake, acc=1), "one accumulate flag")
+            refused(wrun(wplan(**kw), cs=cs, db=fake, acc=2), "one accumulate flag")
     assert _lib.query("scan_nms_ws_bytes", _lib.NMS_MAX + 1) == -1
     assert _lib.query("scan_nms_ws_bytes", 100) > 0
     # beyond one panel the mask is n x ceil(n / 64) words (the reference's own size, csrc/cuda/nms.cu:95-100) + sort keys
@@ -704,3 +747,78 @@ def test_conv_plan_equals_frozen_rules():
     finally:
         L.scan_tune(b"conv_wino", old)
     assert seen == {(True, True, True), (False, False, True), (False, True, False), (False, False, False)}
+
+
+def _frozen_wgrad_plan(npc, ksize, d, cs, cout, v6, tile, wino_knob, wgs):
+    """FROZEN -- do not edit with the library: wgrad_plan, wgrad3_wk, wgrad3_wino, the *_ws_floats queries and the kernel choice
+    of wgrad3_launch / wgrad1_launch as they stood in csrc/conv_wgrad.hip (commit f809b97, lines 1015-1059, 1087-1117, 1143-1148
+    and 1170-1185) before they became one plan.  d: the pyramid the K chunks walk (3x3: x's, 1x1: dy's)."""
+    if ksize == 3:
+        wk = 32 if (v6 and npc == 3) else 64
+        wino = bool(npc == 3 and v6 and wino_knob and tile != 0)
+    else:
+        wk, wino = 64, False
+    chunks = sum(d.n_images * ((h + 1) // 2 if wino else h) * ((w + wk - 1) // wk) for h, w in d.sizes)
+    c_tiles = (cs + 127) // 128
+    n_tiles = ((cout + 127) // 128) * (4 if wino else ksize) * c_tiles
+    target = wgs * 5 // 3 if (cs > 128 and cs % 128 != 0 and cs % 128 <= 16) else wgs
+    s = max(target // n_tiles, 1)
+    s = min(s, (chunks + 7) // 8)
+    s = (s + 7) // 8 * 8
+    cps = max((chunks + s - 1) // s, 1)
+    taps = 12 if wino else 9 if ksize == 3 else 1
+    if ksize == 1 or not v6:
+        variant = _lib.WGRAD_V4
+    elif wino:
+        variant = _lib.WGRAD_V6_32X64_WINO
+    elif (tile == 1) if tile in (0, 1) else (npc == 3):
+        variant = _lib.WGRAD_V6_32X64
+    else:
+        variant = _lib.WGRAD_V6_64X32
+    return {"family": 1 if ksize == 3 else 2, "pieces": npc, "ksize": ksize, "Cs": cs, "Cout": cout, "variant": variant, "wk": wk,
+            "n_tiles": n_tiles, "c_tiles": c_tiles, "splits": s, "cps": cps, "slab_taps": taps, "fused_db": 1, "chunks": chunks,
+            "slab_floats": s * cout * taps * cs, "bias_off": s * cout * taps * cs, "ws_floats": s * cout * taps * cs + s * cout}
+
+
+def test_wgrad_plan_equals_frozen_rules():
+    """scan_conv_wgrad_plan (csrc/conv_api.hip -> conv_wgrad.hip) against the frozen restatement above, over every setting of the
+    four knobs a plan decides: one and five levels, odd heights, widths that are no multiple of 32 or 64, 1 and 4 images; channel
+    counts with whole, ragged and thin (264 / 268) last tiles.  The older *_ws_floats queries report the plan's ws_floats under the
+    same knobs.  The generic family (fixed rule, no knob) against scan_conv2d_wgrad_ws_floats + scan_colsum_ws_floats.  Host-only."""
+    import itertools
+    L = _lib.lib()
+    pyr = [ops.PyramidShape(1, [(13, 20)]), ops.PyramidShape(4, [(37, 75)]), ops.PyramidShape(1, [(61, 100), (31, 50), (16, 25), (8, 13), (4, 7)]),
+           ops.PyramidShape(4, [(64, 96), (32, 48), (16, 24), (8, 12), (4, 6)])]
+    css, couts = (4, 64, 128, 136, 264, 268, 512), (8, 72, 256, 1024)
+    knobs = ("wgrad_v6", "wgrad_tile", "wgrad_wino", "wgrad_wgs")
+    saved = {k: L.scan_tune_get(k.encode()) for k in knobs}
+    variants = set()
+    try:
+        for setting in itertools.product((0, 1), (0, 1, 2), (0, 1), (512, 768, 1024)):
+            for k, v in zip(knobs, setting):
+                L.scan_tune(k.encode(), v)
+            for xd, cs, cout, npc, (ksize, stride) in itertools.product(pyr, css, couts, (2, 3), ((3, 1), (1, 1), (1, 2))):
+                yd = xd.conv_out(ksize, stride)
+                plan = _lib.WgradPlan()
+                assert L.scan_conv_wgrad_plan(npc, ksize, stride, cs, cout, xd.ref(), yd.ref(), ctypes.byref(plan)) == 0, L.scan_last_error()
+                want = _frozen_wgrad_plan(npc, ksize, xd if ksize == 3 else yd, cs, cout, *setting)
+                want["stride"] = stride
+                got = {f: getattr(plan, f) for f in want}
+                assert got == want, (setting, xd.sizes, cs, cout, npc, ksize, stride, got, want)
+                sfx = "bf16x6" if npc == 3 else "bf16x3"
+                old = getattr(L, "scan_conv%s_wgrad_%s_ws_floats" % ("3x3" if ksize == 3 else "1x1", sfx))
+                assert old((xd if ksize == 3 else yd).ref(), cs, cout) == plan.ws_floats
+                variants.add(plan.variant)
+    finally:
+        for k, v in saved.items():
+            L.scan_tune(k.encode(), v)
+    assert {k: L.scan_tune_get(k.encode()) for k in saved} == saved
+    assert variants == {_lib.WGRAD_V4, _lib.WGRAD_V6_64X32, _lib.WGRAD_V6_32X64, _lib.WGRAD_V6_32X64_WINO}
+    for xd, cs, cout, (npc, ksize, stride) in itertools.product(pyr, (4, 136), (8, 1024), ((0, 3, 1), (0, 1, 2), (3, 3, 2), (2, 7, 2), (3, 5, 1))):
+        yd = xd.conv_out(ksize, stride)
+        plan = _lib.WgradPlan()
+        assert L.scan_conv_wgrad_plan(npc, ksize, stride, cs, cout, xd.ref(), yd.ref(), ctypes.byref(plan)) == 0, L.scan_last_error()
+        slabs = L.scan_conv2d_wgrad_ws_floats(yd.ref(), cs, cout, ksize)
+        assert (plan.family, plan.variant, plan.fused_db, plan.slab_taps) == (_lib.WGRAD_GENERIC, _lib.WGRAD_FP32, 0, ksize * ksize)
+        assert plan.slab_floats == plan.colsum_off == slabs == plan.splits * cout * ksize * ksize * cs
+        assert plan.ws_floats == slabs + L.scan_colsum_ws_floats(yd.rows, cout)
