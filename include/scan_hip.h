@@ -99,8 +99,9 @@ int scan_abi_version(void);
  *   "deterministic" 0 (default): the callers of this library (scan_amd.ops, scan_amd.layers, the compiled scan_ops module) use
  *                 the atomic loss / GroupNorm reductions; 1: they call the *_ordered entry points below and take GroupNorm
  *                 statistics from scan_groupnorm_stats_ordered instead of a conv epilogue, so that a training step is
- *                 reproducible bit for bit.  The library only stores this knob: NO existing entry point changes its
- *                 signature or its behaviour with it, a C caller chooses by the symbol it calls. */
+ *                 reproducible bit for bit.  The library stores this knob and reads it in ONE place, scan_groupnorm_plan, which
+ *                 answers an ordered plan with it on: NO other entry point changes its signature or its behaviour with it, a
+ *                 C caller chooses by the symbol it calls. */
 #define SCAN_TUNE_UNKNOWN (-2147483647 - 1)
 int scan_tune(const char* key, int value);
 /* read-only: the current value of a knob (nothing is written), SCAN_TUNE_UNKNOWN for an unknown key */
@@ -562,6 +563,46 @@ int scan_groupnorm_relu_backward_ld_ordered(const float* x, const float* beta, c
                                             const scan_pyramid_t* d, int32_t C, int32_t G, const float* stats,
                                             const float* gamma, int32_t relu, float* dx, float* dgamma, float* dbeta,
                                             int32_t accumulate, float* ws, void* stream);
+/* ---- one plan and one launcher for the GroupNorm entry points above (no reference counterpart) ----
+ * Where the statistics come from, whether the reductions are atomic or ordered and how much workspace that takes are decided
+ * ONCE, by scan_groupnorm_plan, for every binding: plan, allocate what the plan says, run.  scan_groupnorm_plan is the only
+ * reader of scan_tune "deterministic" for GroupNorm; the run functions launch what was planned, whatever the knob says by then.
+ * The entry points above stay what they were: single steps for callers that choose themselves. */
+#define SCAN_GN_SUMS 1           /* flags: the caller holds conv-epilogue sums of x (scan_conv_run on a SCAN_CONV_SUMS plan) */
+#define SCAN_GN_SEPARATE_FINAL 2 /* flags, with SCAN_GN_SUMS: finalise them in a launch of their own instead of in the apply launch */
+#define SCAN_GN_FROM_X 0          /* source: scan_groupnorm_stats / _stats_ordered read x, then scan_groupnorm_relu_forward_ld */
+#define SCAN_GN_FROM_SUMS 1       /* source: scan_groupnorm_relu_forward_from_sums_ld, one launch */
+#define SCAN_GN_FROM_SUMS_FINAL 2 /* source: scan_groupnorm_stats_from_sums, then scan_groupnorm_relu_forward_ld */
+typedef struct {
+  int32_t C, G;           /* channels and groups as given: 256 and 32, the one built pair */
+  int32_t n_levels;       /* of the pyramid planned for */
+  int32_t n_images;       /* of the pyramid planned for */
+  int32_t blocks;         /* workgroups of the statistics, apply and backward launches: 256-row chunks of every (level, image) */
+  int32_t ordered;        /* 0: atomic reductions; 1: the ordered forms (scan_tune "deterministic" was on when planned) */
+  int32_t source;         /* SCAN_GN_FROM_X / _FROM_SUMS / _FROM_SUMS_FINAL.  Epilogue sums are atomic, so an ordered plan answers
+                             SCAN_GN_FROM_X whatever the flags offered: sums of a conv that ran before the knob was switched on are
+                             not read */
+  int32_t stats_floats;   /* floats of the (mean, rstd) table the forward writes and the backward reads: n_levels * N * G * 2 */
+  int32_t fwd_ws_doubles; /* fp64 values of run_forward's ws (read with SCAN_GN_FROM_X only; 16-byte aligned): half of
+                             scan_groupnorm_ws_floats, ordered: of scan_groupnorm_ordered_ws_floats */
+  int32_t bwd_ws_doubles; /* the same for run_backward's ws */
+} scan_groupnorm_plan_t;
+/* Fills *plan for GroupNorm(G, C) on pyramid d.  Host arithmetic under the knob of the moment; touches no device. */
+int scan_groupnorm_plan(const scan_pyramid_t* d, int32_t C, int32_t G, int32_t flags, scan_groupnorm_plan_t* plan);
+/* y [.., ldy] = GroupNorm(x) (ReLU with relu != 0); stats [plan->stats_floats] is written.  sums: the conv epilogue's fp64
+ * [n_levels * N * G][2] (a source from sums; not read otherwise, may be NULL); ws: plan->fwd_ws_doubles doubles (SCAN_GN_FROM_X;
+ * may be NULL otherwise).  Both run functions re-derive the plan's shape fields from d and refuse, before any launch, a plan that
+ * differs (zeroed, edited, made for another pyramid), a row stride that is < C or no multiple of 4, and a missing pointer. */
+int scan_groupnorm_run_forward(const scan_groupnorm_plan_t* plan, const float* x, const scan_pyramid_t* d, const float* sums,
+                               float eps, const float* gamma, const float* beta, int32_t relu, float* y, int32_t ldy,
+                               float* stats, float* ws, void* stream);
+/* Arguments as scan_groupnorm_relu_backward_ld; accumulate: 0, or 1 = add to dgamma / dbeta.  ws: plan->bwd_ws_doubles doubles;
+ * ws_cleared != 0: an atomic plan's ws arrives zeroed and the call does not clear it (ignored by an ordered plan, whose launch
+ * writes every slot). */
+int scan_groupnorm_run_backward(const scan_groupnorm_plan_t* plan, const float* x, const float* beta, const float* dy,
+                                int32_t lddy, const scan_pyramid_t* d, const float* stats, const float* gamma, int32_t relu,
+                                float* dx, float* dgamma, float* dbeta, int32_t accumulate, float* ws, int32_t ws_cleared,
+                                void* stream);
 
 /* ---- the source pass's ground-truth plan on the device (reference rpn/fcos/loss.py:40-133: FCOS location -> GT
  *      assignment and centerness targets; :428-463: graph-node sampling of the source branch).  Rows = pyramid rows

@@ -67,6 +67,18 @@ WGRAD_SPLIT3X3, WGRAD_SPLIT1X1, WGRAD_GENERIC = 1, 2, 3  # SCAN_WGRAD_* families
 WGRAD_FP32, WGRAD_V4, WGRAD_V6_64X32, WGRAD_V6_32X64, WGRAD_V6_32X64_WINO = range(5)  # SCAN_WGRAD_* variants
 _WP = ctypes.POINTER(WgradPlan)
 
+
+
+class GroupNormPlan(ctypes.Structure):
+    """scan_groupnorm_plan_t"""
+    _fields_ = [(n, c_i32) for n in ("C", "G", "n_levels", "n_images", "blocks", "ordered", "source", "stats_floats",
+                                     "fwd_ws_doubles", "bwd_ws_doubles")]
+
+
+GN_SUMS, GN_SEPARATE_FINAL = 1, 2  # SCAN_GN_* flags
+GN_FROM_X, GN_FROM_SUMS, GN_FROM_SUMS_FINAL = range(3)  # SCAN_GN_* sources
+_GP = ctypes.POINTER(GroupNormPlan)
+
 PACK_MAX_LEVELS = 8  # SCAN_PACK_MAX_LEVELS
 SGD_MAX_SEGMENTS = 32
 CKA_MAX_CLASSES = 16
@@ -225,6 +237,10 @@ SIGNATURES = {
                                                             c_i32, c_vp, c_vp]),
     "scan_groupnorm_relu_backward_ld_ordered": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, _PD, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp,
                                                                c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "scan_groupnorm_plan": (ctypes.c_int, [_PD, c_i32, c_i32, c_i32, _GP]),
+    "scan_groupnorm_run_forward": (ctypes.c_int, [_GP, c_vp, _PD, c_vp, c_f32, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "scan_groupnorm_run_backward": (ctypes.c_int, [_GP, c_vp, c_vp, c_vp, c_i32, _PD, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32,
+                                                   c_vp, c_i32, c_vp]),
     "scan_normalize_image_u8": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_f32),
                                                ctypes.POINTER(c_f32), c_vp, c_i32, c_i32, c_i32, c_vp]),
     "scan_pyramid_pack": (ctypes.c_int, [ctypes.POINTER(LevelDesc), c_i32, c_i32, c_i32, c_vp, c_i32, c_vp]),

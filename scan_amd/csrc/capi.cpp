@@ -20,7 +20,7 @@ extern "C" int scan_abi_version(void) { return 1; }
 
 // launch-selection knobs (scan_tune): defined next to the launch code that reads them, declared in conv_launch.h
 // "deterministic": read by the callers (scan_amd.ops, scan_amd.layers, scan_ops._ops), which then take the *_ordered entry
-// points; no entry point of the library changes its behaviour with it
+// points, and by scan_groupnorm_plan (groupnorm.hip, through scan_tune_get); no other entry point changes its behaviour with it
 int g_scan_deterministic = 0;
 
 struct Knob {

@@ -7,6 +7,9 @@
 //  discriminator/fcos_head_discriminator_con.py:31-32).
 #include "common.h"
 
+#include <limits.h>
+#include <string.h>
+
 #define GN_C 256
 #define GN_RPB 256  // rows per block (4 waves x 64 rows, four rows in flight per wave)
 #define GN_REP 8    // replicas of the per-channel fp64 sums (block b adds into replica b % 8: 8x fewer adders per address)
@@ -375,29 +378,96 @@ static int gn_tab(const scan_pyramid_t* d, GnTab* t) {
   }
   return t->blk_off[d->n_levels];
 }
-
-extern "C" int64_t scan_groupnorm_ws_floats(const scan_pyramid_t* d, int32_t C, int32_t G) {
-  return 2 * ((int64_t)d->n_levels * d->n_images * G * 2 + (int64_t)C * 2 * GN_REP);
+static int gn_blocks(const scan_pyramid_t* d) {
+  GnTab tab;
+  return gn_tab(d, &tab);
 }
 
-extern "C" int scan_groupnorm_stats(const float* x, const scan_pyramid_t* d, int32_t C, int32_t G, float eps,
-                                    float* stats, float* ws, void* stream) {
-  if (gn_check(d, C, G, "groupnorm_stats")) return -1;
-  SCAN_CHECK_ARG(x && stats && ws, "groupnorm_stats: null pointer");
-  hipStream_t st = as_stream(stream);
+// ld: y (forward) / dy (backward) may be a column slice of a wider row-major matrix -- ldy / lddy = its row stride in floats
+// (a multiple of 4, >= C; the slice starts at the pointer).  The CKA discriminators normalise straight into the first 256
+// columns of the [M, 256 + Cf] class-branch input and take the gradient back from the same columns of its data gradient:
+// no concatenation copy forward, no contiguous() copy backward.
+static int gn_ld_check(int ld, int C, const char* who) {
+  SCAN_CHECK_ARG(ld >= C && ld % 4 == 0, "%s: row stride %d must be a multiple of 4 and >= C", who, ld);
+  return 0;
+}
+
+// ---- the workspace, stated once.  fp64 values; the backward's need (the statistics use the first part only).
+// atomic:  [level * N + image][G][2] group sums + [GN_REP][C][2] channel-sum replicas, cleared before the launch
+// ordered: [block][G][2] + [block][C][2], a slot per block of the grid, never cleared
+static int64_t gn_ws_doubles(const scan_pyramid_t* d, int C, int G, bool ordered) {
+  const int64_t nblk = gn_blocks(d);
+  return ordered ? nblk * G * 2 + nblk * C * 2 : (int64_t)d->n_levels * d->n_images * G * 2 + (int64_t)C * 2 * GN_REP;
+}
+extern "C" int64_t scan_groupnorm_ws_floats(const scan_pyramid_t* d, int32_t C, int32_t G) {
+  return 2 * gn_ws_doubles(d, C, G, false);
+}
+extern "C" int64_t scan_groupnorm_ordered_ws_floats(const scan_pyramid_t* d, int32_t C, int32_t G) {
+  return 2 * gn_ws_doubles(d, C, G, true);
+}
+
+// ---- the launches.  The entry points below are argument checks around these helpers.
+// statistics pair: the chunk sums of x into ws (atomic: cleared here first), then (mean, rstd) into stats
+template <bool ORD>
+static int gn_launch_stats(const float* x, const scan_pyramid_t* d, int G, float eps, float* stats, float* ws, hipStream_t st) {
   double* wsd = reinterpret_cast<double*>(ws);
   const int total = d->n_levels * d->n_images * G;
-  if (hipMemsetAsync(wsd, 0, sizeof(double) * 2 * total, st) != hipSuccess) {
+  if (!ORD && hipMemsetAsync(wsd, 0, sizeof(double) * 2 * total, st) != hipSuccess) {
     scan_set_error("groupnorm_stats: memset failed");
     return -2;
   }
   GnTab tab;
   const int nblk = gn_tab(d, &tab);
-  hipLaunchKernelGGL(gn_stats_kernel<false>, dim3(nblk), dim3(256), 0, st, x, *d, tab, G, wsd);
-  SCAN_LAUNCH_CHECK("gn_stats");
-  hipLaunchKernelGGL(gn_stats_final_kernel<false>, dim3((total + 255) / 256), dim3(256), 0, st, wsd, *d, tab, G, eps, stats);
-  SCAN_LAUNCH_CHECK("gn_stats_final");
+  if (!ORD || nblk > 0) {
+    hipLaunchKernelGGL(gn_stats_kernel<ORD>, dim3(nblk), dim3(256), 0, st, x, *d, tab, G, wsd);
+    SCAN_LAUNCH_CHECK(ORD ? "gn_stats_ordered" : "gn_stats");
+  }
+  hipLaunchKernelGGL(gn_stats_final_kernel<ORD>, dim3((total + 255) / 256), dim3(256), 0, st, wsd, *d, tab, G, eps, stats);
+  SCAN_LAUNCH_CHECK(ORD ? "gn_stats_final_ordered" : "gn_stats_final");
   return 0;
+}
+
+// normalise (+ ReLU).  sums == nullptr: stats_in is read.  Otherwise the kernel finalises the sums itself and writes stats_out
+// for the backward pass: scan_groupnorm_stats_from_sums + scan_groupnorm_relu_forward in one launch.
+static int gn_launch_apply(const float* x, const scan_pyramid_t* d, int G, const float* stats_in, const float* gamma, const float* beta,
+                           int relu, float* y, int ldy, const float* sums, float eps, float* stats_out, hipStream_t st) {
+  GnTab tab;
+  const int nblk = gn_tab(d, &tab);
+  hipLaunchKernelGGL(gn_apply_kernel, dim3(nblk), dim3(256), 0, st, x, *d, tab, G, stats_in, gamma, beta, relu, y,
+                     reinterpret_cast<const double*>(sums), eps, stats_out, ldy);
+  SCAN_LAUNCH_CHECK(sums ? "gn_apply_from_sums" : "gn_apply");
+  return 0;
+}
+
+// backward pair: group / channel sums into ws (atomic: cleared here first unless it arrives cleared), then dx, dgamma, dbeta
+template <bool ORD>
+static int gn_launch_backward(const float* x, const float* beta, const float* dy, int lddy, const scan_pyramid_t* d, int C, int G,
+                              const float* stats, const float* gamma, int relu, float* dx, float* dgamma, float* dbeta, int accumulate,
+                              float* ws, bool cleared, hipStream_t st) {
+  GnTab tab;
+  const int nblk = gn_tab(d, &tab);
+  double* ws_g = reinterpret_cast<double*>(ws);
+  const int64_t ng = (ORD ? (int64_t)nblk : (int64_t)d->n_levels * d->n_images) * G * 2;
+  double* ws_c = ws_g + ng;
+  if (!ORD && !cleared && hipMemsetAsync(ws_g, 0, sizeof(double) * (ng + 2 * C * GN_REP), st) != hipSuccess) {
+    scan_set_error("groupnorm_relu_backward: memset failed");
+    return -2;
+  }
+  hipLaunchKernelGGL(gn_bwd_reduce_kernel<ORD>, dim3(nblk), dim3(256), 0, st, x, beta, dy, *d, tab, G, stats, gamma, relu, ws_g, ws_c,
+                     lddy);
+  SCAN_LAUNCH_CHECK(ORD ? "gn_bwd_reduce_ordered" : "gn_bwd_reduce");
+  hipLaunchKernelGGL(gn_bwd_apply_kernel<ORD>, dim3(nblk), dim3(256), 0, st, x, beta, dy, *d, tab, G, stats, gamma, relu, ws_g, dx, ws_c,
+                     dgamma, dbeta, accumulate, lddy);
+  SCAN_LAUNCH_CHECK(ORD ? "gn_bwd_apply_ordered" : "gn_bwd_apply");
+  return 0;
+}
+
+// ---- the older entry points: single steps for callers that choose themselves (tools/pointwise_roofline.py times them)
+extern "C" int scan_groupnorm_stats(const float* x, const scan_pyramid_t* d, int32_t C, int32_t G, float eps, float* stats,
+                                    float* ws, void* stream) {
+  if (gn_check(d, C, G, "groupnorm_stats")) return -1;
+  SCAN_CHECK_ARG(x && stats && ws, "groupnorm_stats: null pointer");
+  return gn_launch_stats<false>(x, d, G, eps, stats, ws, as_stream(stream));
 }
 
 // (mean, rstd) from sums accumulated elsewhere (scan_conv3x3_gn_bf16x3's epilogue): ws = fp64 [n_levels*N*G][2]
@@ -414,26 +484,12 @@ extern "C" int scan_groupnorm_stats_from_sums(const float* ws, const scan_pyrami
   return 0;
 }
 
-// ld variants: y (forward) / dy (backward) may be a column slice of a wider row-major matrix -- ldy / lddy = its row
-// stride in floats (a multiple of 4, >= C; the slice starts at the pointer).  The CKA discriminators normalise straight
-// into the first 256 columns of the [M, 256 + Cf] class-branch input and take the gradient back from the same columns
-// of its data gradient: no concatenation copy forward, no contiguous() copy backward.
-static int gn_ld_check(int ld, int C, const char* who) {
-  SCAN_CHECK_ARG(ld >= C && ld % 4 == 0, "%s: row stride %d must be a multiple of 4 and >= C", who, ld);
-  return 0;
-}
-
 extern "C" int scan_groupnorm_relu_forward_ld(const float* x, const scan_pyramid_t* d, int32_t C, int32_t G,
                                               const float* stats, const float* gamma, const float* beta, int32_t relu,
                                               float* y, int32_t ldy, void* stream) {
   if (gn_check(d, C, G, "groupnorm_relu_forward") || gn_ld_check(ldy, C, "groupnorm_relu_forward")) return -1;
   SCAN_CHECK_ARG(x && stats && gamma && beta && y, "groupnorm_relu_forward: null pointer");
-  GnTab tab;
-  const int nblk = gn_tab(d, &tab);
-  hipLaunchKernelGGL(gn_apply_kernel, dim3(nblk), dim3(256), 0, as_stream(stream), x, *d, tab, G, stats, gamma, beta, relu, y,
-                     (const double*)nullptr, 0.f, (float*)nullptr, ldy);
-  SCAN_LAUNCH_CHECK("gn_apply");
-  return 0;
+  return gn_launch_apply(x, d, G, stats, gamma, beta, relu, y, ldy, nullptr, 0.f, nullptr, as_stream(stream));
 }
 
 extern "C" int scan_groupnorm_relu_forward(const float* x, const scan_pyramid_t* d, int32_t C, int32_t G,
@@ -442,8 +498,6 @@ extern "C" int scan_groupnorm_relu_forward(const float* x, const scan_pyramid_t*
   return scan_groupnorm_relu_forward_ld(x, d, C, G, stats, gamma, beta, relu, y, C, stream);
 }
 
-// scan_groupnorm_stats_from_sums + scan_groupnorm_relu_forward in one launch: sums = fp64 [n_levels*N*G][2] from
-// scan_conv3x3_gn_bf16x3's epilogue; stats [n_levels*N*G][2] is written for the backward pass.
 extern "C" int scan_groupnorm_relu_forward_from_sums_ld(const float* x, const scan_pyramid_t* d, int32_t C, int32_t G,
                                                         const float* sums, float eps, const float* gamma,
                                                         const float* beta, int32_t relu, float* y, int32_t ldy,
@@ -451,12 +505,7 @@ extern "C" int scan_groupnorm_relu_forward_from_sums_ld(const float* x, const sc
   if (gn_check(d, C, G, "groupnorm_relu_forward_from_sums") || gn_ld_check(ldy, C, "groupnorm_relu_forward_from_sums"))
     return -1;
   SCAN_CHECK_ARG(x && sums && stats && gamma && beta && y, "groupnorm_relu_forward_from_sums: null pointer");
-  GnTab tab;
-  const int nblk = gn_tab(d, &tab);
-  hipLaunchKernelGGL(gn_apply_kernel, dim3(nblk), dim3(256), 0, as_stream(stream), x, *d, tab, G, (const float*)nullptr,
-                     gamma, beta, relu, y, reinterpret_cast<const double*>(sums), eps, stats, ldy);
-  SCAN_LAUNCH_CHECK("gn_apply_from_sums");
-  return 0;
+  return gn_launch_apply(x, d, G, nullptr, gamma, beta, relu, y, ldy, sums, eps, stats, as_stream(stream));
 }
 
 extern "C" int scan_groupnorm_relu_forward_from_sums(const float* x, const scan_pyramid_t* d, int32_t C, int32_t G,
@@ -466,31 +515,22 @@ extern "C" int scan_groupnorm_relu_forward_from_sums(const float* x, const scan_
   return scan_groupnorm_relu_forward_from_sums_ld(x, d, C, G, sums, eps, gamma, beta, relu, y, C, stats, stream);
 }
 
+// what every backward entry point checks, under its own name
+static int gn_bwd_check(const char* who, const scan_pyramid_t* d, int C, int G, int lddy, bool pointers) {
+  if (gn_check(d, C, G, who) || gn_ld_check(lddy, C, who)) return -1;
+  SCAN_CHECK_ARG(pointers, "%s: null pointer", who);
+  return 0;
+}
+#define GN_BWD_POINTERS (x && dy && stats && gamma && dx && dgamma && dbeta && ws && (beta || !relu))
+
+// accumulate bit 1: ws arrives cleared (a slice of the caller's once-per-iteration cleared buffer)
 extern "C" int scan_groupnorm_relu_backward_ld(const float* x, const float* beta, const float* dy, int32_t lddy,
                                                const scan_pyramid_t* d, int32_t C, int32_t G, const float* stats,
                                                const float* gamma, int32_t relu, float* dx, float* dgamma, float* dbeta,
                                                int32_t accumulate, float* ws, void* stream) {
-  if (gn_check(d, C, G, "groupnorm_relu_backward") || gn_ld_check(lddy, C, "groupnorm_relu_backward")) return -1;
-  SCAN_CHECK_ARG(x && dy && stats && gamma && dx && dgamma && dbeta && ws && (beta || !relu),
-                 "groupnorm_relu_backward: null pointer");
-  hipStream_t st = as_stream(stream);
-  double* ws_g = reinterpret_cast<double*>(ws);
-  const int64_t ng = (int64_t)d->n_levels * d->n_images * G * 2;
-  double* ws_c = ws_g + ng;
-  // accumulate bit 1: ws arrives cleared (a slice of the caller's once-per-iteration cleared buffer)
-  if (!(accumulate & 2) && hipMemsetAsync(ws_g, 0, sizeof(double) * (ng + 2 * C * GN_REP), st) != hipSuccess) {
-    scan_set_error("groupnorm_relu_backward: memset failed");
-    return -2;
-  }
-  GnTab tab;
-  const int nblk = gn_tab(d, &tab);
-  hipLaunchKernelGGL(gn_bwd_reduce_kernel<false>, dim3(nblk), dim3(256), 0, st, x, beta, dy, *d, tab, G, stats, gamma, relu, ws_g, ws_c,
-                     lddy);
-  SCAN_LAUNCH_CHECK("gn_bwd_reduce");
-  hipLaunchKernelGGL(gn_bwd_apply_kernel<false>, dim3(nblk), dim3(256), 0, st, x, beta, dy, *d, tab, G, stats, gamma, relu, ws_g, dx,
-                     ws_c, dgamma, dbeta, accumulate & 1, lddy);
-  SCAN_LAUNCH_CHECK("gn_bwd_apply");
-  return 0;
+  if (gn_bwd_check("groupnorm_relu_backward", d, C, G, lddy, GN_BWD_POINTERS)) return -1;
+  return gn_launch_backward<false>(x, beta, dy, lddy, d, C, G, stats, gamma, relu, dx, dgamma, dbeta, accumulate & 1, ws,
+                                   (accumulate & 2) != 0, as_stream(stream));
 }
 
 extern "C" int scan_groupnorm_relu_backward(const float* x, const float* beta, const float* dy, const scan_pyramid_t* d,
@@ -501,52 +541,21 @@ extern "C" int scan_groupnorm_relu_backward(const float* x, const float* beta, c
                                          stream);
 }
 
-// ---- ordered forms: the same kernels with ORD = true, per-block partial sums in ws instead of atomics ----
-// doubles: the backward's [blocks][G][2] + [blocks][C][2] (the statistics need the first part only)
-extern "C" int64_t scan_groupnorm_ordered_ws_floats(const scan_pyramid_t* d, int32_t C, int32_t G) {
-  GnTab tab;
-  const int64_t nblk = gn_tab(d, &tab);
-  return 2 * (nblk * G * 2 + nblk * C * 2);
-}
-
 extern "C" int scan_groupnorm_stats_ordered(const float* x, const scan_pyramid_t* d, int32_t C, int32_t G, float eps,
                                             float* stats, float* ws, void* stream) {
   if (gn_check(d, C, G, "groupnorm_stats_ordered")) return -1;
   SCAN_CHECK_ARG(x && stats && ws, "groupnorm_stats_ordered: null pointer");
-  hipStream_t st = as_stream(stream);
-  double* wsd = reinterpret_cast<double*>(ws);
-  const int total = d->n_levels * d->n_images * G;
-  GnTab tab;
-  const int nblk = gn_tab(d, &tab);
-  if (nblk > 0) {
-    hipLaunchKernelGGL(gn_stats_kernel<true>, dim3(nblk), dim3(256), 0, st, x, *d, tab, G, wsd);
-    SCAN_LAUNCH_CHECK("gn_stats_ordered");
-  }
-  hipLaunchKernelGGL(gn_stats_final_kernel<true>, dim3((total + 255) / 256), dim3(256), 0, st, wsd, *d, tab, G, eps, stats);
-  SCAN_LAUNCH_CHECK("gn_stats_final_ordered");
-  return 0;
+  return gn_launch_stats<true>(x, d, G, eps, stats, ws, as_stream(stream));
 }
 
 extern "C" int scan_groupnorm_relu_backward_ld_ordered(const float* x, const float* beta, const float* dy, int32_t lddy,
                                                        const scan_pyramid_t* d, int32_t C, int32_t G, const float* stats,
                                                        const float* gamma, int32_t relu, float* dx, float* dgamma,
                                                        float* dbeta, int32_t accumulate, float* ws, void* stream) {
-  if (gn_check(d, C, G, "groupnorm_relu_backward_ordered") || gn_ld_check(lddy, C, "groupnorm_relu_backward_ordered")) return -1;
-  SCAN_CHECK_ARG(x && dy && stats && gamma && dx && dgamma && dbeta && ws && (beta || !relu),
-                 "groupnorm_relu_backward_ordered: null pointer");
-  hipStream_t st = as_stream(stream);
-  GnTab tab;
-  const int nblk = gn_tab(d, &tab);
-  SCAN_CHECK_ARG(nblk > 0, "groupnorm_relu_backward_ordered: empty pyramid");
-  double* ws_g = reinterpret_cast<double*>(ws);
-  double* ws_c = ws_g + (int64_t)nblk * G * 2;
-  hipLaunchKernelGGL(gn_bwd_reduce_kernel<true>, dim3(nblk), dim3(256), 0, st, x, beta, dy, *d, tab, G, stats, gamma, relu, ws_g,
-                     ws_c, lddy);
-  SCAN_LAUNCH_CHECK("gn_bwd_reduce_ordered");
-  hipLaunchKernelGGL(gn_bwd_apply_kernel<true>, dim3(nblk), dim3(256), 0, st, x, beta, dy, *d, tab, G, stats, gamma, relu, ws_g, dx,
-                     ws_c, dgamma, dbeta, accumulate & 1, lddy);
-  SCAN_LAUNCH_CHECK("gn_bwd_apply_ordered");
-  return 0;
+  if (gn_bwd_check("groupnorm_relu_backward_ordered", d, C, G, lddy, GN_BWD_POINTERS)) return -1;
+  SCAN_CHECK_ARG(gn_blocks(d) > 0, "groupnorm_relu_backward_ordered: empty pyramid");
+  return gn_launch_backward<true>(x, beta, dy, lddy, d, C, G, stats, gamma, relu, dx, dgamma, dbeta, accumulate & 1, ws, false,
+                                  as_stream(stream));
 }
 
 extern "C" int scan_groupnorm_relu_backward_ordered(const float* x, const float* beta, const float* dy,
@@ -555,4 +564,68 @@ extern "C" int scan_groupnorm_relu_backward_ordered(const float* x, const float*
                                                     int32_t accumulate, float* ws, void* stream) {
   return scan_groupnorm_relu_backward_ld_ordered(x, beta, dy, C, d, C, G, stats, gamma, relu, dx, dgamma, dbeta, accumulate, ws,
                                                  stream);
+}
+
+// ---- plan + run (scan_hip.h): which statistics, which reduction and how much workspace, decided once for every binding
+static int gn_plan_fill(const char* who, const scan_pyramid_t* d, int C, int G, int ordered, int source, scan_groupnorm_plan_t* p) {
+  if (gn_check(d, C, G, who)) return -1;
+  const int64_t nblk = d->n_images >= 1 ? gn_blocks(d) : 0, ws = gn_ws_doubles(d, C, G, ordered != 0);
+  SCAN_CHECK_ARG(nblk > 0 && ws <= INT32_MAX, "%s: empty pyramid or workspace past 2^31 doubles", who);
+  *p = scan_groupnorm_plan_t{C, G, d->n_levels, d->n_images, (int32_t)nblk, ordered, source, d->n_levels * d->n_images * G * 2, (int32_t)ws,
+                             (int32_t)ws};
+  return 0;
+}
+
+extern "C" int scan_groupnorm_plan(const scan_pyramid_t* d, int32_t C, int32_t G, int32_t flags, scan_groupnorm_plan_t* plan) {
+  const char* who = "groupnorm_plan";
+  SCAN_CHECK_ARG(plan != nullptr, "%s: null plan", who);
+  SCAN_CHECK_ARG(flags == 0 || flags == SCAN_GN_SUMS || flags == (SCAN_GN_SUMS | SCAN_GN_SEPARATE_FINAL), "%s: flags=%d", who, flags);
+  // the one reader of the knob.  Epilogue sums are atomic: deterministic mode takes none, also not those of a conv that ran
+  // before the mode was switched on, and reads x once more with the ordered statistics kernel.
+  const int ordered = scan_tune_get("deterministic") == 1;
+  const int source = ordered || !(flags & SCAN_GN_SUMS) ? SCAN_GN_FROM_X
+                     : (flags & SCAN_GN_SEPARATE_FINAL) ? SCAN_GN_FROM_SUMS_FINAL : SCAN_GN_FROM_SUMS;
+  return gn_plan_fill(who, d, C, G, ordered, source, plan);
+}
+
+// the plan's shape fields re-derived on the pyramid passed in: a zeroed or edited plan, or one made for another pyramid, differs
+static int gn_plan_check(const char* who, const scan_groupnorm_plan_t* p, const scan_pyramid_t* d, int ld) {
+  SCAN_CHECK_ARG(p != nullptr, "%s: null plan", who);
+  scan_groupnorm_plan_t q;
+  SCAN_CHECK_ARG(p->C == GN_C && p->G == 32 && (p->ordered == 0 || p->ordered == 1) && p->source >= SCAN_GN_FROM_X &&
+                     p->source <= SCAN_GN_FROM_SUMS_FINAL && (!p->ordered || p->source == SCAN_GN_FROM_X),
+                 "%s: not a plan scan_groupnorm_plan filled", who);
+  if (gn_plan_fill(who, d, p->C, p->G, p->ordered, p->source, &q)) return -1;
+  SCAN_CHECK_ARG(memcmp(&q, p, sizeof q) == 0, "%s: not a plan scan_groupnorm_plan filled for this pyramid (blocks: planned %d, here %d)", who,
+                 p->blocks, q.blocks);
+  return gn_ld_check(ld, p->C, who);
+}
+
+extern "C" int scan_groupnorm_run_forward(const scan_groupnorm_plan_t* plan, const float* x, const scan_pyramid_t* d, const float* sums,
+                                          float eps, const float* gamma, const float* beta, int32_t relu, float* y, int32_t ldy,
+                                          float* stats, float* ws, void* stream) {
+  const char* who = "groupnorm_run_forward";
+  if (gn_plan_check(who, plan, d, ldy)) return -1;
+  const int src = plan->source, G = plan->G;
+  SCAN_CHECK_ARG(x && gamma && beta && y && stats && (src == SCAN_GN_FROM_X ? ws != nullptr : sums != nullptr), "%s: null pointer", who);
+  hipStream_t st = as_stream(stream);
+  const int rc = src == SCAN_GN_FROM_SUMS         ? 0
+                 : src == SCAN_GN_FROM_SUMS_FINAL ? scan_groupnorm_stats_from_sums(sums, d, plan->C, G, eps, stats, stream)
+                 : plan->ordered                  ? gn_launch_stats<true>(x, d, G, eps, stats, ws, st)
+                                                  : gn_launch_stats<false>(x, d, G, eps, stats, ws, st);
+  if (rc) return rc;
+  return src == SCAN_GN_FROM_SUMS ? gn_launch_apply(x, d, G, nullptr, gamma, beta, relu, y, ldy, sums, eps, stats, st)
+                                  : gn_launch_apply(x, d, G, stats, gamma, beta, relu, y, ldy, nullptr, 0.f, nullptr, st);
+}
+
+extern "C" int scan_groupnorm_run_backward(const scan_groupnorm_plan_t* plan, const float* x, const float* beta, const float* dy,
+                                           int32_t lddy, const scan_pyramid_t* d, const float* stats, const float* gamma, int32_t relu,
+                                           float* dx, float* dgamma, float* dbeta, int32_t accumulate, float* ws, int32_t ws_cleared,
+                                           void* stream) {
+  const char* who = "groupnorm_run_backward";
+  if (gn_plan_check(who, plan, d, lddy)) return -1;
+  SCAN_CHECK_ARG(accumulate == 0 || accumulate == 1, "%s: accumulate=%d (0 or 1; a cleared workspace is ws_cleared)", who, accumulate);
+  SCAN_CHECK_ARG(GN_BWD_POINTERS, "%s: null pointer", who);
+  auto run = plan->ordered ? gn_launch_backward<true> : gn_launch_backward<false>;
+  return run(x, beta, dy, lddy, d, plan->C, plan->G, stats, gamma, relu, dx, dgamma, dbeta, accumulate, ws, ws_cleared != 0, as_stream(stream));
 }

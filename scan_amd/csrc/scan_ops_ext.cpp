@@ -284,46 +284,38 @@ struct Conv2dFn : public torch::autograd::Function<Conv2dFn> {
 // ---- nn.GroupNorm(32, 256) (+ ReLU) on rows ------------------------------------------------------------------------------
 constexpr int kGroups = 32;
 
-// scan_tune "deterministic" (include/scan_hip.h), read at every call that chooses a reduction -- the library's knob is the
-// only copy of the switch, scan_amd.ops reads the same one: the ordered GroupNorm entry points, no conv-epilogue sums
-bool deterministic() { return scan_tune_get("deterministic") == 1; }
+// statistics from x or from a conv epilogue's sums, atomic or ordered reductions, workspace sizes: the library's one plan
+// (scan_groupnorm_plan, scan_hip.h), the only reader of scan_tune "deterministic" -- the function scan_amd.ops asks too
+scan_groupnorm_plan_t gn_plan(int64_t c, const scan_pyramid_t& d, int flags) {
+  scan_groupnorm_plan_t plan;
+  check(scan_groupnorm_plan(&d, (int32_t)c, kGroups, flags, &plan), "scan_groupnorm_plan");
+  return plan;
+}
+float* f64_ptr(const at::Tensor& t) { return t.defined() ? reinterpret_cast<float*>(t.data_ptr()) : nullptr; }
 
-// (mean, rstd) of rows xr -> stats, by the atomic or the ordered statistics kernels
-void gn_rows_stats(const at::Tensor& xr, const scan_pyramid_t& d, int32_t c, double eps, at::Tensor& stats) {
-  const bool det = deterministic();
-  const int64_t nws = det ? scan_groupnorm_ordered_ws_floats(&d, c, kGroups) : scan_groupnorm_ws_floats(&d, c, kGroups);
-  at::Tensor ws = at::empty({nws / 2 + 1}, xr.options().dtype(at::kDouble));
-  if (det)
-    check(scan_groupnorm_stats_ordered(xr.data_ptr<float>(), &d, c, kGroups, (float)eps, stats.data_ptr<float>(),
-                                       reinterpret_cast<float*>(ws.data_ptr()), cur_stream(xr)),
-          "scan_groupnorm_stats_ordered");
-  else
-    check(scan_groupnorm_stats(xr.data_ptr<float>(), &d, c, kGroups, (float)eps, stats.data_ptr<float>(),
-                               reinterpret_cast<float*>(ws.data_ptr()), cur_stream(xr)),
-          "scan_groupnorm_stats");
+// y = GroupNorm(xr) (+ ReLU) as planned, (mean, rstd) -> stats; sums: the conv epilogue's where the plan's source says so
+at::Tensor gn_rows_forward(const scan_groupnorm_plan_t& plan, const at::Tensor& xr, const scan_pyramid_t& d, const at::Tensor& sums,
+                           const at::Tensor& gamma, const at::Tensor& beta, double eps, bool relu, at::Tensor& stats) {
+  stats = at::empty({plan.stats_floats}, xr.options());
+  at::Tensor y = at::empty_like(xr), ws;
+  if (plan.source == SCAN_GN_FROM_X) ws = at::empty({plan.fwd_ws_doubles}, xr.options().dtype(at::kDouble));
+  check(scan_groupnorm_run_forward(&plan, xr.data_ptr<float>(), &d, f64_ptr(sums), (float)eps, gamma.data_ptr<float>(), beta.data_ptr<float>(),
+                                   relu ? 1 : 0, y.data_ptr<float>(), (int32_t)xr.size(1), stats.data_ptr<float>(), f64_ptr(ws), cur_stream(xr)),
+        "scan_groupnorm_run_forward");
+  return y;
 }
 
 at::Tensor gn_rows_backward(const at::Tensor& xr, const at::Tensor& gamma, const at::Tensor& beta, const at::Tensor& stats,
                             const at::Tensor& dyr, const scan_pyramid_t& d, bool relu, at::Tensor& dgamma, at::Tensor& dbeta) {
-  const int32_t C = (int32_t)xr.size(1);
-  at::Tensor dx = at::empty_like(xr);
+  const int64_t C = xr.size(1);
+  const scan_groupnorm_plan_t plan = gn_plan(C, d, 0);  // under the knob of the moment, as the forward's
+  at::Tensor dx = at::empty_like(xr), ws = at::empty({plan.bwd_ws_doubles}, xr.options().dtype(at::kDouble));
   dgamma = at::empty({C}, xr.options());
   dbeta = at::empty({C}, xr.options());
-  if (deterministic()) {
-    at::Tensor ws = at::empty({scan_groupnorm_ordered_ws_floats(&d, C, kGroups) / 2 + 1}, xr.options().dtype(at::kDouble));
-    check(scan_groupnorm_relu_backward_ordered(xr.data_ptr<float>(), beta.data_ptr<float>(), dyr.data_ptr<float>(), &d, C, kGroups,
-                                               stats.data_ptr<float>(), gamma.data_ptr<float>(), relu ? 1 : 0, dx.data_ptr<float>(),
-                                               dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), 0,
-                                               reinterpret_cast<float*>(ws.data_ptr()), cur_stream(xr)),
-          "scan_groupnorm_relu_backward_ordered");
-    return dx;
-  }
-  at::Tensor ws = at::empty({scan_groupnorm_ws_floats(&d, C, kGroups) / 2 + 1}, xr.options().dtype(at::kDouble));
-  check(scan_groupnorm_relu_backward(xr.data_ptr<float>(), beta.data_ptr<float>(), dyr.data_ptr<float>(), &d, C, kGroups,
-                                     stats.data_ptr<float>(), gamma.data_ptr<float>(), relu ? 1 : 0, dx.data_ptr<float>(),
-                                     dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), 0, reinterpret_cast<float*>(ws.data_ptr()),
-                                     cur_stream(xr)),
-        "scan_groupnorm_relu_backward");
+  check(scan_groupnorm_run_backward(&plan, xr.data_ptr<float>(), beta.data_ptr<float>(), dyr.data_ptr<float>(), (int32_t)C, &d,
+                                    stats.data_ptr<float>(), gamma.data_ptr<float>(), relu ? 1 : 0, dx.data_ptr<float>(),
+                                    dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), 0, f64_ptr(ws), 0, cur_stream(xr)),
+        "scan_groupnorm_run_backward");
   return dx;
 }
 
@@ -334,12 +326,8 @@ struct GroupNormReluFn : public torch::autograd::Function<GroupNormReluFn> {
     const int64_t n = dims[0], c = dims[1], h = dims[2], w = dims[3];
     const scan_pyramid_t d = one_level(n, h, w);
     at::Tensor gc = gamma.contiguous(), bc = beta.contiguous();
-    at::Tensor stats = at::empty({n * kGroups * 2}, xr.options()), y = at::empty_like(xr);
-    void* st = cur_stream(xr);
-    gn_rows_stats(xr, d, (int32_t)c, eps, stats);
-    check(scan_groupnorm_relu_forward(xr.data_ptr<float>(), &d, (int32_t)c, kGroups, stats.data_ptr<float>(), gc.data_ptr<float>(),
-                                      bc.data_ptr<float>(), relu ? 1 : 0, y.data_ptr<float>(), st),
-          "scan_groupnorm_relu_forward");
+    at::Tensor stats;
+    at::Tensor y = gn_rows_forward(gn_plan(c, d, 0), xr, d, at::Tensor(), gc, bc, eps, relu, stats);
     ctx->save_for_backward({xr, gc, bc, stats});
     ctx->saved_data["dims"] = dims;
     ctx->saved_data["relu"] = relu;
@@ -366,23 +354,14 @@ struct ConvGnReluFn : public torch::autograd::Function<ConvGnReluFn> {
     at::Tensor wp = pack_weight(weight), gc = gamma.contiguous(), bc = beta.contiguous();
     at::Tensor cb = bias.defined() ? bias.contiguous() : bias;
     const scan_pyramid_t d = one_level(g.n, g.h, g.w);
-    // deterministic mode: the conv runs without epilogue sums (they are atomic), the ordered statistics kernel reads its output
-    const bool det = deterministic();
-    at::Tensor sums = det ? at::Tensor() : at::empty({g.n * kGroups * 2}, xr.options().dtype(at::kDouble));  // cleared by the conv launch
+    // the plan says whether the conv accumulates the GroupNorm sums in its epilogue (not in deterministic mode: they are atomic)
+    const scan_groupnorm_plan_t plan = gn_plan(g.ns, d, SCAN_GN_SUMS);
+    at::Tensor sums = plan.source == SCAN_GN_FROM_X ? at::Tensor() : at::empty({plan.stats_floats}, xr.options().dtype(at::kDouble));  // cleared by the conv launch
     const bool wp_view = wp.data_ptr() == weight.data_ptr();
     at::Tensor c = conv_rows_forward(xr, wp, cb, g, false, sums, wp_view ? wp : at::Tensor());
     ctx->saved_data["wp_view"] = wp_view;
-    at::Tensor stats = at::empty({g.n * kGroups * 2}, xr.options()), y = at::empty_like(c);
-    if (det) {
-      gn_rows_stats(c, d, 256, eps, stats);
-      check(scan_groupnorm_relu_forward(c.data_ptr<float>(), &d, 256, kGroups, stats.data_ptr<float>(), gc.data_ptr<float>(),
-                                        bc.data_ptr<float>(), relu ? 1 : 0, y.data_ptr<float>(), cur_stream(xr)),
-            "scan_groupnorm_relu_forward");
-    } else
-      check(scan_groupnorm_relu_forward_from_sums(c.data_ptr<float>(), &d, 256, kGroups, reinterpret_cast<float*>(sums.data_ptr()),
-                                                (float)eps, gc.data_ptr<float>(), bc.data_ptr<float>(), relu ? 1 : 0, y.data_ptr<float>(),
-                                                stats.data_ptr<float>(), cur_stream(xr)),
-          "scan_groupnorm_relu_forward_from_sums");
+    at::Tensor stats;
+    at::Tensor y = gn_rows_forward(plan, c, d, sums, gc, bc, eps, relu, stats);
     ctx->save_for_backward({xr, wp, c, gc, bc, stats});
     ctx->saved_data["geom"] = gv;
     ctx->saved_data["relu"] = relu;

@@ -47,8 +47,10 @@ def pad4(c):
 
 # ----------------------------------------------------------------------------- deterministic mode
 # scan_tune "deterministic" (SCAN_TUNE=deterministic=1) lives in the library and is the only copy of the switch: it is read
-# at every call that chooses between an atomic reduction and its *_ordered twin -- here, in scan_amd.layers and in the
-# compiled scan_ops module -- never cached.  With it on, two runs from one seed end with the same bits.
+# at every call that chooses between an atomic reduction and its *_ordered twin, never cached -- for the losses and the conv
+# epilogue's GroupNorm sums here (_call_reduction, _Conv2d), for GroupNorm itself in the library (scan_groupnorm_plan, which
+# this module and the compiled scan_ops module both ask).  With it on, two runs from one seed end with the same bits
+# (DESIGN.md section 4).
 def deterministic():
     return query("scan_tune_get", b"deterministic") == 1
 
@@ -62,6 +64,15 @@ def _partials(name, like, *args):
     """the per-workgroup slots of an *_ordered call (name: its *_ordered_ws_floats query): one fresh buffer per call, so
     calls on side streams never share one; not cleared -- every workgroup of the launch writes all of its slots"""
     return torch.empty((max(int(query(name, *args)), 1),), dtype=torch.float32, device=like.device)
+
+
+def _call_reduction(base, fwd, like, ws_args, *args):
+    """a loss forward that ends in a sum: ``base + fwd`` with atomics, or in deterministic mode its *_ordered twin (the same
+    arguments + the per-workgroup slots before the stream; base + "_ordered_ws_floats"(*ws_args) sizes them)"""
+    if deterministic():
+        call(base + fwd + "_ordered", *args, _ptr(_partials(base + "_ordered_ws_floats", like, *ws_args)), _stream())
+    else:
+        call(base + fwd, *args, _stream())
 
 
 class KernelTimer:
@@ -299,7 +310,7 @@ class SplitPlan:
 # GroupNorm workspaces (fp64 sums the kernels accumulate into with atomics) must start at zero.  Cleared one by one that is a
 # memset launch per conv-with-sums and per GroupNorm backward, 60 per training step; instead they are slices of one buffer
 # that begin_weight_epoch() clears with ONE memset (what the previous iteration used of it), and the library is told not to
-# clear (scan_conv3x3_gn_acc_bf16x3; bit 1 of scan_groupnorm_relu_backward's accumulate).  Outside an epoch, or when the buffer
+# clear (scan_conv3x3_gn_acc_bf16x3; scan_groupnorm_run_backward's ws_cleared).  Outside an epoch, or when the buffer
 # runs out, the workspace is a fresh allocation the library call clears itself.
 ZERO_POOL = os.environ.get("SCAN_ZERO_POOL", "1") != "0"
 _zero_pool = {"buf": None, "off": 0, "active": False}
@@ -967,16 +978,24 @@ def _col_slice_ld(t, C):
     return None
 
 
+def _gn_plan(shape, C, flags=0):
+    """statistics from x or from a conv epilogue's sums, atomic or ordered reductions, workspace sizes: the library decides
+    (scan_groupnorm_plan, include/scan_hip.h) -- the compiled operators (csrc/scan_ops_ext.cpp) ask the same function"""
+    plan = _lib.GroupNormPlan()
+    call("scan_groupnorm_plan", shape.ref(), C, 32, flags, ctypes.byref(plan))
+    return plan
+
+
 class _GroupNormReLU(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, shape, relu, eps, out_buf=None):
         _chk(x, gamma, beta)
         C = x.shape[1]
-        st = _stream()
-        stats = x.new_empty((shape.n_levels * shape.n_images * 32 * 2,))
+        # accumulated by the epilogue of the conv that produced x: one launch normalises and leaves (mean, rstd) behind for the
+        # backward (SCAN_BATCHED=0: a launch of its own finalises them first)
         sums = _gn_sums.pop(x.data_ptr(), None)
-        if sums is not None and deterministic():  # epilogue sums of a conv that ran before the mode was switched on
-            sums = None
+        plan = _gn_plan(shape, C, 0 if sums is None else _lib.GN_SUMS | (0 if BATCHED else _lib.GN_SEPARATE_FINAL))
+        stats = x.new_empty((plan.stats_floats,))
         if out_buf is None:
             y, ldy = torch.empty_like(x), C
         else:  # normalise straight into the first C columns of a wider matrix (cat_into completes it)
@@ -985,22 +1004,9 @@ class _GroupNormReLU(torch.autograd.Function):
                 raise RuntimeError("groupnorm_relu: out_buf must be a contiguous fp32 [M, >= C] GPU matrix with a row "
                                    "length that is a multiple of 4")
             y, ldy = out_buf[:, :C], out_buf.shape[1]
-        if sums is not None and not BATCHED:
-            call("scan_groupnorm_stats_from_sums", _ptr(sums), shape.ref(), C, 32, eps, _ptr(stats), st)
-            call("scan_groupnorm_relu_forward_ld", _ptr(x), shape.ref(), C, 32, _ptr(stats), _ptr(gamma), _ptr(beta),
-                 int(relu), _ptr(y), ldy, st)
-        elif sums is not None:  # accumulated by the epilogue of the conv that produced x: one launch normalises and
-            # leaves (mean, rstd) behind for the backward
-            call("scan_groupnorm_relu_forward_from_sums_ld", _ptr(x), shape.ref(), C, 32, _ptr(sums), eps, _ptr(gamma),
-                 _ptr(beta), int(relu), _ptr(y), ldy, _ptr(stats), st)
-        else:
-            det = deterministic()
-            nws = query("scan_groupnorm_ordered_ws_floats" if det else "scan_groupnorm_ws_floats", shape.ref(), C, 32)
-            ws = torch.empty((nws // 2 + 1,), dtype=torch.float64, device=x.device)
-            call("scan_groupnorm_stats_ordered" if det else "scan_groupnorm_stats", _ptr(x), shape.ref(), C, 32, eps,
-                 _ptr(stats), _ptr(ws), st)
-            call("scan_groupnorm_relu_forward_ld", _ptr(x), shape.ref(), C, 32, _ptr(stats), _ptr(gamma), _ptr(beta),
-                 int(relu), _ptr(y), ldy, st)
+        ws = torch.empty((plan.fwd_ws_doubles,), dtype=torch.float64, device=x.device) if plan.source == _lib.GN_FROM_X else None
+        call("scan_groupnorm_run_forward", ctypes.byref(plan), _ptr(x), shape.ref(), _ptr(sums), eps, _ptr(gamma), _ptr(beta),
+             int(relu), _ptr(y), ldy, _ptr(stats), _ptr(ws), _stream())
         ctx.save_for_backward(x, beta, gamma, stats)  # the backward recomputes the ReLU mask from x: y is not kept
         ctx.cfg = (shape, relu)
         ctx.gbuf = ctx.bbuf = None
@@ -1021,21 +1027,13 @@ class _GroupNormReLU(torch.autograd.Function):
         direct = ctx.gbuf is not None
         dg = ctx.gbuf if direct else x.new_empty((C,))
         db = ctx.bbuf if direct else x.new_empty((C,))
-        if deterministic():  # per-block slots, all written by the launch: no zeroed pool slice needed
-            nws = query("scan_groupnorm_ordered_ws_floats", shape.ref(), C, 32)
-            ws = torch.empty((nws // 2 + 1,), dtype=torch.float64, device=x.device)
-            call("scan_groupnorm_relu_backward_ld_ordered", _ptr(x), _ptr(beta), _ptr(dy), lddy, shape.ref(), C, 32,
-                 _ptr(stats), _ptr(gamma), int(relu), _ptr(dx), _ptr(dg), _ptr(db), int(direct), _ptr(ws), _stream())
-            if direct:
-                return dx, None, None, None, None, None, None
-            return dx, dg, db, None, None, None, None
-        nws = query("scan_groupnorm_ws_floats", shape.ref(), C, 32)
-        ws, cleared = _ws_f64(nws // 2 + 1, x.device)
-        call("scan_groupnorm_relu_backward_ld", _ptr(x), _ptr(beta), _ptr(dy), lddy, shape.ref(), C, 32, _ptr(stats),
-             _ptr(gamma), int(relu), _ptr(dx), _ptr(dg), _ptr(db), int(direct) | (2 if cleared else 0), _ptr(ws), _stream())
-        if direct:
-            return dx, None, None, None, None, None, None
-        return dx, dg, db, None, None, None, None
+        plan = _gn_plan(shape, C)  # under the knob of the moment, as the forward's
+        # atomic sums: a slice of the zeroed pool where there is one.  Ordered: per-block slots, all written by the launch
+        ws, cleared = _ws_f64(plan.bwd_ws_doubles, x.device) if not plan.ordered \
+            else (torch.empty((plan.bwd_ws_doubles,), dtype=torch.float64, device=x.device), False)
+        call("scan_groupnorm_run_backward", ctypes.byref(plan), _ptr(x), _ptr(beta), _ptr(dy), lddy, shape.ref(), _ptr(stats),
+             _ptr(gamma), int(relu), _ptr(dx), _ptr(dg), _ptr(db), int(direct), _ptr(ws), int(cleared), _stream())
+        return dx, None if direct else dg, None if direct else db, None, None, None, None
 
 
 def groupnorm_relu(x, gamma, beta, shape, relu=True, eps=1e-5, out_buf=None):
@@ -1047,7 +1045,7 @@ def groupnorm_relu(x, gamma, beta, shape, relu=True, eps=1e-5, out_buf=None):
 class _CatInto(torch.autograd.Function):
     """cat([y, extra, zeros], 1) where y already IS the first C columns of ``buf`` (groupnorm_relu(out_buf=buf)): only
     the few extra columns are copied.  Backward: the two column slices of the gradient, as views -- the GroupNorm
-    backward reads its slice in place (scan_groupnorm_relu_backward_ld)."""
+    backward reads its slice in place (scan_groupnorm_run_backward's lddy)."""
 
     @staticmethod
     def forward(ctx, y, extra, buf):
@@ -1166,13 +1164,8 @@ class _SigmoidFocalSum(torch.autograd.Function):
             raise RuntimeError("targets must be int32")
         M, C = logits.shape
         out = logits.new_zeros((1,))
-        if deterministic():
-            ws = _partials("scan_sigmoid_focal_loss_ordered_ws_floats", logits, M, C)
-            call("scan_sigmoid_focal_loss_forward_ordered", _ptr(logits), _ptr(targets), M, C, gamma, alpha, None, _ptr(out),
-                 _ptr(ws), _stream())
-        else:
-            call("scan_sigmoid_focal_loss_forward", _ptr(logits), _ptr(targets), M, C, gamma, alpha, None, _ptr(out),
-                 _stream())
+        _call_reduction("scan_sigmoid_focal_loss", "_forward", logits, (M, C), _ptr(logits), _ptr(targets), M, C, gamma, alpha, None,
+                        _ptr(out))
         ctx.save_for_backward(logits, targets)
         ctx.cfg = (gamma, alpha)
         return out[0]
@@ -1225,11 +1218,7 @@ class _IouLoss(torch.autograd.Function):
         _chk(pred, target, weight)
         P = pred.shape[0]
         out = pred.new_zeros((2,))
-        if deterministic():
-            ws = _partials("scan_iou_loss_ordered_ws_floats", pred, P)
-            call("scan_iou_loss_forward_ordered", _ptr(pred), _ptr(target), _ptr(weight), P, _ptr(out), _ptr(ws), _stream())
-        else:
-            call("scan_iou_loss_forward", _ptr(pred), _ptr(target), _ptr(weight), P, _ptr(out), _stream())
+        _call_reduction("scan_iou_loss", "_forward", pred, (P,), _ptr(pred), _ptr(target), _ptr(weight), P, _ptr(out))
         ctx.save_for_backward(pred, target, weight, out)
         return out[0] / out[1]
 
@@ -1254,11 +1243,7 @@ class _BceLogitsMean(torch.autograd.Function):
         _chk(logits, targets)
         M = logits.numel()
         out = logits.new_zeros((2,))
-        if deterministic():
-            ws = _partials("scan_bce_logits_ordered_ws_floats", logits, M)
-            call("scan_bce_logits_forward_ordered", _ptr(logits), _ptr(targets), 0.0, None, 0, M, _ptr(out), _ptr(ws), _stream())
-        else:
-            call("scan_bce_logits_forward", _ptr(logits), _ptr(targets), 0.0, None, 0, M, _ptr(out), _stream())
+        _call_reduction("scan_bce_logits", "_forward", logits, (M,), _ptr(logits), _ptr(targets), 0.0, None, 0, M, _ptr(out))
         ctx.save_for_backward(logits, targets)
         return out[0] / M
 
@@ -1278,11 +1263,7 @@ def bce_with_logits_mean(logits, targets):
 
 def _cka_forward_loss(logits, act, M, cf, target, out):
     """out [2 cf + 2]: the per-class sums, a ticket word, the loss (atomic form: last block; ordered form: second launch)"""
-    if deterministic():
-        ws = _partials("scan_cka_bce_ordered_ws_floats", logits, M, cf)
-        call("scan_cka_bce_forward_loss_ordered", _ptr(logits), _ptr(act), M, cf, target, _ptr(out), _ptr(ws), _stream())
-    else:
-        call("scan_cka_bce_forward_loss", _ptr(logits), _ptr(act), M, cf, target, _ptr(out), _stream())
+    _call_reduction("scan_cka_bce", "_forward_loss", logits, (M, cf), _ptr(logits), _ptr(act), M, cf, target, _ptr(out))
 
 
 class _CkaBce(torch.autograd.Function):
@@ -1392,11 +1373,7 @@ class _SoftmaxFocalMean(torch.autograd.Function):
             raise RuntimeError("labels must be int64")
         M, K = logits.shape
         out = logits.new_zeros((1,))
-        if deterministic():
-            ws = _partials("scan_softmax_focal_ordered_ws_floats", logits, M)
-            call("scan_softmax_focal_forward_ordered", _ptr(logits), _ptr(labels), M, K, gamma, _ptr(out), _ptr(ws), _stream())
-        else:
-            call("scan_softmax_focal_forward", _ptr(logits), _ptr(labels), M, K, gamma, _ptr(out), _stream())
+        _call_reduction("scan_softmax_focal", "_forward", logits, (M,), _ptr(logits), _ptr(labels), M, K, gamma, _ptr(out))
         ctx.save_for_backward(logits, labels)
         ctx.gamma = gamma
         return out[0] / M

@@ -116,6 +116,44 @@ def test_argument_validation_without_device():
         if wplan(**kw).fused_db:  # one flag for dw and db
             refused(wrun(wplan(**kw), cs=cs, db=fake, acc=1), "one accumulate flag")
             refused(wrun(wplan(**kw), cs=cs, db=fake, acc=2), "one accumulate flag")
+    # the GroupNorm plan + launcher: the same
+    def gplan(pyr=two, flags=0, C=256, G=32):
+        p = _lib.GroupNormPlan()
+        rc = L.scan_groupnorm_plan(pyr.ref() if pyr is not None else None, C, G, flags, ctypes.byref(p))
+        return p if rc == 0 else rc
+
+    def gfwd(p, ld=256, pyr=two, sums=None, ws=fake):
+        return L.scan_groupnorm_run_forward(ctypes.byref(p) if p is not None else None, fake, pyr.ref() if pyr is not None else None, sums,
+                                            1e-5, fake, fake, 1, fake, ld, fake, ws, None)
+
+    def gbwd(p, ld=256, pyr=two, acc=0, ws=fake):
+        return L.scan_groupnorm_run_backward(ctypes.byref(p) if p is not None else None, fake, fake, fake, ld, pyr.ref() if pyr is not None else None,
+                                             fake, fake, 1, fake, fake, fake, acc, ws, 0, None)
+
+    refused(gplan(C=128), "only C=256, G=32")
+    refused(gplan(G=16), "only C=256, G=32")
+    refused(gplan(pyr=None), "bad pyramid")
+    refused(gplan(flags=_lib.GN_SEPARATE_FINAL), "flags")  # a launch of their own for sums nobody has
+    refused(gplan(flags=4), "flags")
+    assert L.scan_groupnorm_plan(two.ref(), 256, 32, 0, None) == -1
+    other = ops.PyramidShape(2, [(12, 20), (40, 10)])
+    for run in (gfwd, gbwd):
+        refused(run(None), "null plan")
+        refused(run(_lib.GroupNormPlan()), "not a plan")  # zeroed
+        refused(run(edited(gplan(), blocks=gplan().blocks + 1)), "not a plan")
+        refused(run(edited(gplan(), bwd_ws_doubles=16)), "not a plan")
+        refused(run(edited(gplan(), ordered=2)), "not a plan")
+        refused(run(edited(gplan(), source=3)), "not a plan")
+        refused(run(gplan(), pyr=other), r"for this pyramid \(blocks: planned 4, here 6\)")
+        refused(run(gplan(pyr=ops.PyramidShape(1, two.sizes))), "for this pyramid")  # another image count
+        refused(run(gplan(), pyr=None), "bad pyramid")
+        refused(run(gplan(), ws=None), "null pointer")
+        for ld in (252, 258, 0, -256):
+            refused(run(gplan(), ld), "row stride")
+    for flags in (_lib.GN_SUMS, _lib.GN_SUMS | _lib.GN_SEPARATE_FINAL):
+        assert gplan(flags=flags).source == (_lib.GN_FROM_SUMS if flags == _lib.GN_SUMS else _lib.GN_FROM_SUMS_FINAL)
+        refused(gfwd(gplan(flags=flags), sums=None), "null pointer")  # planned on sums, run without
+    refused(gbwd(gplan(), acc=2), "accumulate")  # a cleared workspace is ws_cleared now, not bit 1
     assert _lib.query("scan_nms_ws_bytes", _lib.NMS_MAX + 1) == -1
     assert _lib.query("scan_nms_ws_bytes", 100) > 0
     # beyond one panel the mask is n x ceil(n / 64) words (the reference's own size, csrc/cuda/nms.cu:95-100) + sort keys
@@ -822,3 +860,49 @@ def test_wgrad_plan_equals_frozen_rules():
         assert (plan.family, plan.variant, plan.fused_db, plan.slab_taps) == (_lib.WGRAD_GENERIC, _lib.WGRAD_FP32, 0, ksize * ksize)
         assert plan.slab_floats == plan.colsum_off == slabs == plan.splits * cout * ksize * ksize * cs
         assert plan.ws_floats == slabs + L.scan_colsum_ws_floats(yd.rows, cout)
+
+
+def _frozen_groupnorm_rules(det, sums, separate, n_images, sizes):
+    """FROZEN -- do not edit with the library: the choices of ops._GroupNormReLU (commit ae08abd, scan_amd/ops.py lines 976-1003 and
+    1024-1035), of gn_rows_stats / gn_rows_backward / ConvGnReluFn (csrc/scan_ops_ext.cpp lines 292-328 and 369-385) and the grid and
+    workspace formulas of csrc/groupnorm.hip (gn_tab, scan_groupnorm_ws_floats, scan_groupnorm_ordered_ws_floats: lines 365-381 and
+    506-510) as they stood before they became one plan."""
+    C, G = 256, 32
+    blocks = sum(n_images * ((h * w + 255) // 256) for h, w in sizes)
+    groups = len(sizes) * n_images * G
+    if sums and det:  # "epilogue sums of a conv that ran before the mode was switched on"
+        sums = False
+    source = 0 if not sums else 2 if separate else 1  # statistics kernels on x / fused into the apply launch / a final launch first
+    ws_floats = 2 * (blocks * G * 2 + blocks * C * 2) if det else 2 * (groups * 2 + C * 2 * 8)
+    return {"C": C, "G": G, "n_levels": len(sizes), "n_images": n_images, "blocks": blocks, "ordered": int(det), "source": source,
+            "stats_floats": groups * 2, "fwd_ws_doubles": ws_floats // 2, "bwd_ws_doubles": ws_floats // 2}
+
+
+def test_groupnorm_plan_equals_frozen_rules():
+    """scan_groupnorm_plan (csrc/groupnorm.hip), field by field, against the frozen restatement above: the knob on and off, no sums /
+    sums / sums with a final launch of their own; one level with one image (exactly one 256-row block, and 15 rows: less than one),
+    two levels with two images (6,144 rows = 24 whole blocks beside 35 rows; 260 rows = one block + a 4-row tail beside 15), five
+    levels with sizes that are no multiple of 256.  The workspace fields are half of what the kept queries report.  Host-only."""
+    import itertools
+    L = _lib.lib()
+    pyramids = [(1, [(16, 16)]), (1, [(3, 5)]), (2, [(64, 96), (7, 5)]), (2, [(20, 13), (3, 5)]),
+                (2, [(100, 168), (50, 84), (25, 42), (13, 21), (7, 11)])]
+    fields = [n for n, _ in _lib.GroupNormPlan._fields_]
+    seen = set()
+    old = L.scan_tune_get(b"deterministic")
+    try:
+        for det, flags, (n, sizes) in itertools.product((0, 1), (0, _lib.GN_SUMS, _lib.GN_SUMS | _lib.GN_SEPARATE_FINAL), pyramids):
+            L.scan_tune(b"deterministic", det)
+            d = ops.PyramidShape(n, sizes)
+            plan = _lib.GroupNormPlan()
+            assert L.scan_groupnorm_plan(d.ref(), 256, 32, flags, ctypes.byref(plan)) == 0, L.scan_last_error()
+            want = _frozen_groupnorm_rules(bool(det), bool(flags & 1), bool(flags & 2), n, sizes)
+            for f in fields:  # ordered, source, the block count, stats_floats and both workspace sizes among them
+                assert getattr(plan, f) == want[f], (det, flags, n, sizes, f, getattr(plan, f), want[f])
+            query = L.scan_groupnorm_ordered_ws_floats if det else L.scan_groupnorm_ws_floats
+            assert 2 * plan.fwd_ws_doubles == 2 * plan.bwd_ws_doubles == query(d.ref(), 256, 32)
+            seen.add((plan.ordered, plan.source))
+    finally:
+        L.scan_tune(b"deterministic", old)
+    assert L.scan_tune_get(b"deterministic") == old
+    assert seen == {(0, 0), (0, 1), (0, 2), (1, 0)}
