@@ -136,7 +136,9 @@ int scan_conv1x1_bf16x6_instance(const scan_pyramid_t* yd, int32_t Nout, int32_t
  * logits [M,C] fp32, targets [M] int32 (0 = bg, c = class c, <0 = ignore).
  * losses may be NULL; loss_sum (1 float, pre-zeroed by caller) may be NULL:
  * when given, the wavefront-reduced total is atomically added to it, which is
- * what layers/sigmoid_focal_loss.py:56-70 (`loss.sum()`) consumes. */
+ * what layers/sigmoid_focal_loss.py:56-70 (`loss.sum()`) consumes.
+ * Any 4-byte aligned pointer is accepted: the float4 forms run only when M*C is a multiple of 4 and logits, losses, d_losses
+ * and d_logits (those given) are all 16-byte aligned; otherwise the scalar form of the same arithmetic. */
 int scan_sigmoid_focal_loss_forward(const float* logits, const int32_t* targets, int64_t M, int32_t C,
                                     float gamma, float alpha, float* losses, float* loss_sum, void* stream);
 /* d_losses [M,C] or NULL; when NULL every element uses d_scale (the fused
@@ -147,7 +149,9 @@ int scan_sigmoid_focal_loss_backward(const float* logits, const int32_t* targets
 
 /* ---- IOULoss (replaces layers/iou_loss.py:5-36) ----
  * pred/target [P,4] (l,t,r,b), weight [P] or NULL.  out[0] += sum(loss*w),
- * out[1] += sum(w) (w = 1 when NULL); caller pre-zeroes out[2] and divides. */
+ * out[1] += sum(w) (w = 1 when NULL); caller pre-zeroes out[2] and divides.  The reference takes the weighted mean only
+ * when sum(w) > 0 and the plain mean otherwise: a caller that may see such a weight also asks for the unweighted pair
+ * (weight = NULL) and selects on out[1] (scan_amd.ops.iou_loss does, on the device).  pred / target: 16-byte aligned. */
 int scan_iou_loss_forward(const float* pred, const float* target, const float* weight, int64_t P,
                           float* out2, void* stream);
 /* d_pred[i,:] = g_num * w_i * dloss_i/dpred  with g_num = upstream / sum(w) read from g_num_dev[0]. */

@@ -113,13 +113,12 @@ __device__ __forceinline__ void block_result(float* __restrict__ dst, int k, int
 
 template <int CT, bool G2, bool ORD = false>
 __global__ __launch_bounds__(256) void focal_fwd_kernel(const float* __restrict__ logits,
-                                                        const int* __restrict__ targets, int64_t total, int C,
-                                                        float gamma, float alpha, float* __restrict__ losses,
+                                                        const int* __restrict__ targets, int64_t total, bool vec,
+                                                        int C, float gamma, float alpha, float* __restrict__ losses,
                                                         float* __restrict__ loss_sum) {
   __shared__ float red[4];
   float acc = 0.f;
   const int64_t n4 = (total + 3) >> 2;
-  const bool vec = (total & 3) == 0;
   for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n4; q += (int64_t)gridDim.x * blockDim.x) {
     const int64_t i0 = q << 2;
     float x[4], l[4];
@@ -157,10 +156,9 @@ template <int CT, bool G2, bool ORD = false>  // ORD: unused, FOCAL_DISPATCH nam
 __global__ __launch_bounds__(256) void focal_bwd_kernel(const float* __restrict__ logits,
                                                         const int* __restrict__ targets,
                                                         const float* __restrict__ d_losses, float d_scale,
-                                                        int64_t total, int C, float gamma, float alpha,
+                                                        int64_t total, bool vec, int C, float gamma, float alpha,
                                                         float* __restrict__ d_logits) {
   const int64_t n4 = (total + 3) >> 2;
-  const bool vec = (total & 3) == 0;
   for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n4; q += (int64_t)gridDim.x * blockDim.x) {
     const int64_t i0 = q << 2;
     float x[4], up[4], g[4];
@@ -210,14 +208,19 @@ static inline int grid_reduce(int64_t work_items, int block, bool light = false)
   return (int)g;
 }
 
+// vec: the float4 form -- total a multiple of 4 AND every pointer the kernel would use as float4 16-byte aligned (focal_vec_ok;
+// the kernel takes the same fact as its `vec` argument).  The C = 8 / C = 1 instances exist in that form only: anything else
+// (a tail, or a contiguous view that starts 4 bytes into an allocation) runs the generic kernel's scalar loads and stores.
+static inline bool focal_vec_ok(int64_t total, const void* a, const void* b, const void* c = nullptr) {
+  return (total & 3) == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
+}
 #define FOCAL_DISPATCH(KERNEL, ORD, GRID, ...)                                                                          \
   do {                                                                                                              \
     const bool g2 = gamma == 2.0f;                                                                                  \
-    const bool al = (total & 3) == 0;                                                                               \
-    if (C == 8 && al) {                                                                                             \
+    if (C == 8 && vec) {                                                                                            \
       if (g2) hipLaunchKernelGGL((KERNEL<8, true, ORD>), dim3(GRID), dim3(256), 0, as_stream(stream), __VA_ARGS__);      \
       else hipLaunchKernelGGL((KERNEL<8, false, ORD>), dim3(GRID), dim3(256), 0, as_stream(stream), __VA_ARGS__);        \
-    } else if (C == 1 && al && (reinterpret_cast<uintptr_t>(targets) & 15) == 0) {                                  \
+    } else if (C == 1 && vec && (reinterpret_cast<uintptr_t>(targets) & 15) == 0) {                                 \
       if (g2) hipLaunchKernelGGL((KERNEL<1, true, ORD>), dim3(GRID), dim3(256), 0, as_stream(stream), __VA_ARGS__);      \
       else hipLaunchKernelGGL((KERNEL<1, false, ORD>), dim3(GRID), dim3(256), 0, as_stream(stream), __VA_ARGS__);        \
     } else {                                                                                                        \
@@ -235,7 +238,8 @@ extern "C" int scan_sigmoid_focal_loss_forward(const float* logits, const int32_
   SCAN_CHECK_ARG(logits && targets, "sigmoid_focal_loss_forward: null input");
   const int64_t total = M * C;
   const int grid = loss_sum ? grid_reduce((total + 3) / 4, 256) : grid_for((total + 3) / 4, 256);
-  FOCAL_DISPATCH(focal_fwd_kernel, false, grid, logits, targets, total, C, gamma, alpha, losses, loss_sum);
+  const bool vec = focal_vec_ok(total, logits, losses);  // losses == nullptr: not written
+  FOCAL_DISPATCH(focal_fwd_kernel, false, grid, logits, targets, total, vec, C, gamma, alpha, losses, loss_sum);
   SCAN_LAUNCH_CHECK("focal_fwd");
   return 0;
 }
@@ -248,7 +252,8 @@ extern "C" int scan_sigmoid_focal_loss_backward(const float* logits, const int32
   SCAN_CHECK_ARG(logits && targets && d_logits, "sigmoid_focal_loss_backward: null pointer");
   const int64_t total = M * C;
   const int grid = grid_for((total + 3) / 4, 256);
-  FOCAL_DISPATCH(focal_bwd_kernel, false, grid, logits, targets, d_losses, d_scale, total, C, gamma, alpha, d_logits);
+  const bool vec = focal_vec_ok(total, logits, d_logits, d_losses);  // d_losses == nullptr: d_scale instead
+  FOCAL_DISPATCH(focal_bwd_kernel, false, grid, logits, targets, d_losses, d_scale, total, vec, C, gamma, alpha, d_logits);
   SCAN_LAUNCH_CHECK("focal_bwd");
   return 0;
 }
@@ -853,7 +858,8 @@ extern "C" int scan_sigmoid_focal_loss_forward_ordered(const float* logits, cons
   SCAN_CHECK_ARG(logits && targets, "sigmoid_focal_loss_forward_ordered: null input");
   const int64_t total = M * C;
   const int grid = grid_reduce((total + 3) / 4, 256);
-  FOCAL_DISPATCH(focal_fwd_kernel, true, grid, logits, targets, total, C, gamma, alpha, losses, ws);
+  const bool vec = focal_vec_ok(total, logits, losses);
+  FOCAL_DISPATCH(focal_fwd_kernel, true, grid, logits, targets, total, vec, C, gamma, alpha, losses, ws);
   SCAN_LAUNCH_CHECK("focal_fwd_ordered");
   return ordered_sum_launch(ws, grid, 1, loss_sum, 0, nullptr, stream, "focal_fwd_ordered_sum");
 }

@@ -1213,19 +1213,32 @@ class _SigmoidFocalElem(torch.autograd.Function):
 
 
 class _IouLoss(torch.autograd.Function):
+    """the reference's rule (layers/iou_loss.py:32-36): the weighted mean when a weight is given AND sums to more than 0, the plain
+    mean otherwise.  Which of the two holds is known on the device only, and nothing here waits for it: with a weight, a second,
+    unweighted launch fills out[2:4], torch.where on the device sum of weights picks the pair the value is formed from, and the
+    backward gets the weight that goes with it (the weight itself, or ones) and the matching normaliser."""
+
     @staticmethod
     def forward(ctx, pred, target, weight):
         _chk(pred, target, weight)
         P = pred.shape[0]
-        out = pred.new_zeros((2,))
+        out = pred.new_zeros((4,))
         _call_reduction("scan_iou_loss", "_forward", pred, (P,), _ptr(pred), _ptr(target), _ptr(weight), P, _ptr(out))
-        ctx.save_for_backward(pred, target, weight, out)
-        return out[0] / out[1]
+        if weight is None:
+            use, sel = None, out[:2]
+        else:
+            _call_reduction("scan_iou_loss", "_forward", pred, (P,), _ptr(pred), _ptr(target), None, P, _ptr(out[2:]))
+            use = out[1] > 0
+            sel = torch.where(use, out[:2], out[2:])
+        ctx.save_for_backward(pred, target, weight, sel, use)
+        return sel[0] / sel[1]
 
     @staticmethod
     def backward(ctx, g):
-        pred, target, weight, out = ctx.saved_tensors
-        gn = (g / out[1]).reshape(1).contiguous()
+        pred, target, weight, sel, use = ctx.saved_tensors
+        gn = (g / sel[1]).reshape(1).contiguous()
+        if weight is not None:
+            weight = torch.where(use, weight, 1.0)
         d = torch.empty_like(pred)
         call("scan_iou_loss_backward", _ptr(pred), _ptr(target), _ptr(weight), pred.shape[0], _ptr(gn), _ptr(d),
              _stream())
