@@ -830,6 +830,37 @@ int scan_pyramid_pack(const scan_level_t* levels, int32_t n_levels, int32_t n_im
 int scan_pyramid_unpack(const float* rows, int32_t Cs, const scan_level_t* levels, int32_t n_levels, int32_t n_images,
                         int32_t C, void* stream);
 
+/* ---- deformable convolution v2 (DCNv2), the sampling half ----
+ * The reference exports fcos_core.layers.DFConv2d (layers/misc.py:113-184) but holds no arithmetic for it (it imports an absent
+ * package), so these kernels implement the published definition (Zhu et al., "Deformable ConvNets v2", 2019; the mmcv /
+ * torchvision deform_conv2d semantics): 3x3 kernel, stride 1, padding 1, dilation 1, one group, one deformable group, input
+ * and output on one pyramid.  For output row m = (level l, image n, y, x) and tap k = 3 i + j:
+ *   h = float(y - 1 + i) + off[m][2k],  w = float(x - 1 + j) + off[m][2k + 1]      (dy first; ONE fp32 add each)
+ *   val[c] = 0 when h <= -1 || w <= -1 || h >= H_l || w >= W_l (decided in floating point), otherwise the bilinear sample of
+ *            x on the cell [floor h, floor h + 1] x [floor w, floor w + 1], a corner outside the image counting zero
+ *   cols[m][k * Cs + c] = mask[m][k] * val[c]   (mask == NULL: 1, plain DCNv1); columns C..Cs-1 of every tap are zeros
+ * The convolution itself is the library's 1x1 convolution over cols [M, 9 Cs] (scan_conv_plan with taps = 1), its gradients
+ * the 1x1 data and weight gradients.  floor carries zero derivative: at integer positions the gradients are those of the cell
+ * floor selects.  x: [M, Cs] rows; off: [M, ld_off >= 18]; mask: [M, ld_mask >= 9]; x, cols, dcols, dx 16-byte aligned.
+ * Every element of cols is written. */
+int scan_deform_sample_forward(const float* x, const scan_pyramid_t* d, int32_t C, int32_t Cs, const float* off, int32_t ld_off,
+                               const float* mask, int32_t ld_mask, float* cols, void* stream);
+/* layers/misc.py:113-184, gradients of the sampling above for dcols [M, 9 Cs]: doff [M, ld_doff >= 18] and dmask [M, ld_dmask
+ * >= 9] (skipped when mask == NULL) are channel sums inside one wave in a fixed order, their columns past 18 / 9 are written as
+ * zeros.  The data gradient is left as an inverted index instead of float atomics: for each of the 4 * 9 * M entries
+ * e = (m * 9 + k) * 4 + corner (corner = 2 * (h high) + (w high)), keys[e] = the row of dx the corner adds to, or M for a
+ * corner outside the image or a skipped tap, and wgts[e] = mask * bilinear weight.  The caller sorts the keys (stable) and
+ * hands the permutation to the gather below. */
+int scan_deform_sample_backward(const float* x, const scan_pyramid_t* d, int32_t C, int32_t Cs, const float* dcols, const float* off,
+                                int32_t ld_off, const float* mask, int32_t ld_mask, float* doff, int32_t ld_doff, float* dmask,
+                                int32_t ld_dmask, int32_t* keys, float* wgts, void* stream);
+/* layers/misc.py:113-184, the data gradient of the DCNv2 definition above: dx[p][:] = sum over e = perm[s], s in
+ * [seg_start[p], seg_start[p + 1]) in that order, of wgts[e] * dcols[e / 4][:], with dcols read as [9 M, Cs] rows.  perm: the
+ * int64 permutation of a stable sort of keys; seg_start: M + 1 int64 first positions of the keys 0..M in the sorted order.
+ * One wave per row of dx, every row written (zeros for an empty segment): the sum is bit-reproducible. */
+int scan_deform_dx_gather(const float* dcols, const int64_t* perm, const int64_t* seg_start, const float* wgts, int64_t M, int32_t C,
+                          int32_t Cs, float* dx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

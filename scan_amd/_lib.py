@@ -245,6 +245,10 @@ SIGNATURES = {
                                                ctypes.POINTER(c_f32), c_vp, c_i32, c_i32, c_i32, c_vp]),
     "scan_pyramid_pack": (ctypes.c_int, [ctypes.POINTER(LevelDesc), c_i32, c_i32, c_i32, c_vp, c_i32, c_vp]),
     "scan_pyramid_unpack": (ctypes.c_int, [c_vp, c_i32, ctypes.POINTER(LevelDesc), c_i32, c_i32, c_i32, c_vp]),
+    "scan_deform_sample_forward": (ctypes.c_int, [c_vp, _PD, c_i32, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp]),
+    "scan_deform_sample_backward": (ctypes.c_int, [c_vp, _PD, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp,
+                                                   c_i32, c_vp, c_vp, c_vp]),
+    "scan_deform_dx_gather": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp]),
 }
 
 _lib = None

@@ -43,13 +43,16 @@ CONFIGS = {name: config.settings(config.load(name)) for name in ("c2f", "s2c", "
 
 
 def build_model(num_classes=9, test_mode="precision", device="cuda", attn_dropout=0.1, transfer_cfg=("NODES", "ADJ"),
-                conv_body="VGG-16-FPN-RETINANET", settings=None):
+                conv_body="VGG-16-FPN-RETINANET", settings=None, dcn_in_tower=False):
     """dict MODEL{backbone, middle_head, fcos, dis_P*_CON} like tools/train_net_da.py:43-48,223-274.
-    settings: a config.settings(cfg) dict (e.g. engine.CONFIGS["s2c"]); it overrides the four model keywords."""
+    settings: a config.settings(cfg) dict (e.g. engine.CONFIGS["s2c"]); it overrides the four model keywords.
+    dcn_in_tower: the last conv of the FCOS head's two towers is a deformable one (layers.DFConv2d; upstream FCOS's
+    MODEL.FCOS.USE_DCN_IN_TOWER).  A keyword only: no shipped config has the key."""
     s = dict(CONFIGS["c2f"])
     s.update(num_classes=num_classes, test_mode=test_mode, transfer_cfg=tuple(transfer_cfg), conv_body=conv_body)
     if settings is not None:
         s.update(settings)
+    s["dcn_in_tower"] = bool(dcn_in_tower)
     if not 2 <= s["num_classes"] <= ops.dynconv_max_classes():
         raise ValueError("num_classes=%d (background included): the kernels are built for 2..%d classes"
                          % (s["num_classes"], ops.dynconv_max_classes()))

@@ -223,3 +223,100 @@ def dynamic_conv_softmax(features, kernel_par):
     h, w = shape.sizes[0]
     back = lambda t: t.view(shape.n_images, h, w, t.shape[1]).permute(0, 3, 1, 2)
     return back(logits), back(probs)
+
+
+# ----------------------------------------------------------------------------- deformable convolution (DCNv2)
+# The reference exports DFConv2d (layers/__init__.py:8,29, layers/misc.py:113-184) on top of the ModulatedDeformConv / DeformConv
+# of a package it does not ship, so there is no reference arithmetic: these modules implement the published DCNv2 definition
+# (the mmcv / torchvision semantics, include/scan_hip.h: scan_deform_sample_forward) -- Python backend only, scan_ops._ops has
+# no binding for it.
+def _dcn_unsupported(name, kernel_size, stride, padding, dilation, groups, deformable_groups):
+    pair = lambda v: tuple(v) if isinstance(v, (list, tuple)) else (v, v)
+    if (pair(kernel_size) != (3, 3) or pair(stride) != (1, 1) or pair(padding) != (1, 1) or pair(dilation) != (1, 1)
+            or groups != 1 or deformable_groups != 1):
+        raise RuntimeError("scan_amd.layers.%s: only kernel 3, stride 1, padding 1, dilation 1, groups 1, "
+                           "deformable_groups 1 are built (what the FCOS tower uses)" % name)
+
+
+class ModulatedDeformConv(nn.Module):
+    """mmcv-style ModulatedDeformConv(in_channels, out_channels, kernel_size, ...): weight [O, C, 3, 3] (channels_last) and an
+    optional bias; forward(x, offset, mask) on NCHW tensors, offset [N, 18, H, W] (dy, dx per tap), mask [N, 9, H, W]."""
+    modulated = True
+
+    def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, padding=1, dilation=1, groups=1,
+                 deformable_groups=1, bias=True):
+        super().__init__()
+        _dcn_unsupported(type(self).__name__, kernel_size, stride, padding, dilation, groups, deformable_groups)
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels, 3, 3).contiguous(memory_format=torch.channels_last))
+        self.bias = nn.Parameter(torch.zeros(out_channels)) if bias else None
+        stdv = 1.0 / (in_channels * 9) ** 0.5  # mmcv's reset_parameters
+        nn.init.uniform_(self.weight, -stdv, stdv)
+
+    def rows_forward(self, rows, offset, mask, shape, gn_sums=False):
+        """the op on pyramid rows: offset [M, >= 18], mask [M, >= 9] or None (ops.deform_conv2d)"""
+        w = self.weight
+        if not w.permute(0, 2, 3, 1).is_contiguous():  # kernels read [Cout][k*k][Cin]
+            w = w.contiguous(memory_format=torch.channels_last)
+        return ops.deform_conv2d(rows, offset, mask, w, self.bias, shape, gn_sums=gn_sums)
+
+    def forward(self, x, offset, mask=None):
+        if self.modulated and mask is None:
+            raise RuntimeError("ModulatedDeformConv: forward(x, offset, mask) needs a mask")
+        if offset.shape[1] != 18 or (mask is not None and mask.shape[1] != 9) or x.shape[1] != self.in_channels:
+            raise RuntimeError("deformable conv: x %s, offset %s (18 channels), mask %s (9 channels) do not fit"
+                               % (tuple(x.shape), tuple(offset.shape), None if mask is None else tuple(mask.shape)))
+        rows, shape, _ = _to_rows(x)
+        off = _to_rows(offset)[0]
+        msk = _to_rows(mask)[0] if mask is not None else None
+        return _to_nchw(self.rows_forward(rows, off, msk, shape), shape, self.out_channels)
+
+
+class DeformConv(ModulatedDeformConv):
+    """DCNv1: forward(x, offset), the mask is 1."""
+    modulated = False
+
+    def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, padding=1, dilation=1, groups=1,
+                 deformable_groups=1, bias=False):
+        super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, deformable_groups, bias)
+
+    def forward(self, x, offset):
+        return super().forward(x, offset, None)
+
+
+class DFConv2d(nn.Module):
+    """reference layers/misc.py:113-184: ``offset`` = Conv2d(in, 27 or 18, 3, 1, 1) predicting the offsets (and the mask
+    logits), ``conv`` = ModulatedDeformConv or DeformConv; state_dict keys offset.weight, offset.bias, conv.weight(, conv.bias)."""
+
+    def __init__(self, in_channels, out_channels, with_modulated_dcn=True, kernel_size=3, stride=1, groups=1, padding=1,
+                 dilation=1, deformable_groups=1, bias=False):
+        super().__init__()
+        _dcn_unsupported("DFConv2d", kernel_size, stride, padding, dilation, groups, deformable_groups)
+        self.offset_base_channels = 9
+        self.offset = Conv2d(in_channels, 27 if with_modulated_dcn else 18, kernel_size=3, stride=1, padding=1)
+        nn.init.kaiming_uniform_(self.offset.weight, a=1)
+        nn.init.constant_(self.offset.bias, 0.)
+        self.offset.weight.data = self.offset.weight.data.contiguous(memory_format=torch.channels_last)
+        self.conv = (ModulatedDeformConv if with_modulated_dcn else DeformConv)(in_channels, out_channels, bias=bias)
+        self.with_modulated_dcn = with_modulated_dcn
+        self.kernel_size, self.stride, self.padding, self.dilation = kernel_size, stride, padding, dilation
+
+    def rows_forward(self, rows, shape, gn_sums=False):
+        """the layer on pyramid rows (modeling.fcos.run_tower): ONE conv gives the 27 (18) offset / mask channels at pitch 28
+        (20); the deformable conv reads its offsets as the first 18 columns of that matrix."""
+        w = self.offset.weight
+        if not w.permute(0, 2, 3, 1).is_contiguous():
+            w = w.contiguous(memory_format=torch.channels_last)
+        om = ops.conv2d(rows, w, self.offset.bias, shape, 3, 1)
+        mask = om[:, 18:27].sigmoid() if self.with_modulated_dcn else None
+        return self.conv.rows_forward(rows, om, mask, shape, gn_sums=gn_sums)
+
+    def forward(self, x):
+        assert x.numel() > 0, "only non-empty tensors are supported"
+        if not x.is_cuda:
+            raise RuntimeError("scan_amd.layers.DFConv2d runs only on the GPU (HIP) -- got a %s tensor; no CPU fallback" % x.device)
+        if not self.with_modulated_dcn:
+            return self.conv(x, self.offset(x))
+        offset_mask = self.offset(x)
+        split_point = self.offset_base_channels * 2
+        return self.conv(x, offset_mask[:, :split_point, :, :], offset_mask[:, split_point:, :, :].sigmoid())

@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from .. import ops
-from ..layers import IOULoss, Scale, SigmoidFocalLoss
+from ..layers import DFConv2d, IOULoss, Scale, SigmoidFocalLoss
 from .backbone import conv_holder
 
 INF = 100000000  # reference rpn/fcos/loss.py:22
@@ -23,10 +23,13 @@ SIZES_OF_INTEREST = ((-1, 64), (64, 128), (128, 256), (256, 512), (512, INF))  #
 FPN_STRIDES = (8, 16, 32, 64, 128)
 
 
-def make_tower(n, c=256):
+def make_tower(n, c=256, dcn_last=False):
+    """dcn_last: the LAST conv is a layers.DFConv2d(c, c, bias=True) in the same Sequential slot (MODEL.FCOS.USE_DCN_IN_TOWER of
+    upstream FCOS / ATSS, reference rpn/atss/atss.py:110-112): keys <3 * (n - 1)>.offset.* and <3 * (n - 1)>.conv.*"""
     layers = []
-    for _ in range(n):
-        layers += [conv_holder(c, c, 3), nn.GroupNorm(32, c), nn.ReLU()]
+    for i in range(n):
+        conv = DFConv2d(c, c, bias=True) if dcn_last and i == n - 1 else conv_holder(c, c, 3)
+        layers += [conv, nn.GroupNorm(32, c), nn.ReLU()]
     return nn.Sequential(*layers)
 
 
@@ -36,7 +39,10 @@ def run_tower(tower, rows, shape, n, out_buf=None):
     the tower's output (ops.groupnorm_relu(out_buf=...)); the returned rows are that column slice."""
     for i in range(n):
         conv, gn = tower[3 * i], tower[3 * i + 1]
-        rows = ops.conv2d(rows, conv.weight, conv.bias, shape, 3, 1, gn_sums=True)  # GN sums from the conv epilogue
+        if isinstance(conv, DFConv2d):  # offset conv + deformable conv; its 1x1 contraction has no sums epilogue
+            rows = conv.rows_forward(rows, shape, gn_sums=True)
+        else:
+            rows = ops.conv2d(rows, conv.weight, conv.bias, shape, 3, 1, gn_sums=True)  # GN sums from the conv epilogue
         rows = ops.groupnorm_relu(rows, gn.weight, gn.bias, shape, relu=True, eps=gn.eps,
                                   out_buf=out_buf if i == n - 1 else None)
     return rows
@@ -255,12 +261,12 @@ def centerness_targets(reg):
 class FCOSHead(nn.Module):
     """reference fcos.py:13-114 with REG_CTR_ON True."""
 
-    def __init__(self, num_classes=9, num_convs=4, prior_prob=0.01):
+    def __init__(self, num_classes=9, num_convs=4, prior_prob=0.01, use_dcn_in_tower=False):
         super().__init__()
         self.num_fg = num_classes - 1
         self.num_convs = num_convs
-        self.cls_tower = make_tower(num_convs)
-        self.bbox_tower = make_tower(num_convs)
+        self.cls_tower = make_tower(num_convs, dcn_last=use_dcn_in_tower)
+        self.bbox_tower = make_tower(num_convs, dcn_last=use_dcn_in_tower)
         self.cls_logits = conv_holder(256, self.num_fg, 3)
         self.bbox_pred = conv_holder(256, 4, 3)
         self.centerness = conv_holder(256, 1, 3)
@@ -494,7 +500,8 @@ class FCOSModule(nn.Module):
         c = cfg or {}
         if c.get("num_convs_cls", 4) != c.get("num_convs_reg", 4):
             raise ValueError("MODEL.FCOS.NUM_CONVS_CLS != NUM_CONVS_REG is not built")
-        self.head = FCOSHead(num_classes, c.get("num_convs_cls", 4), c.get("prior_prob", 0.01))
+        self.head = FCOSHead(num_classes, c.get("num_convs_cls", 4), c.get("prior_prob", 0.01),
+                             use_dcn_in_tower=bool(c.get("dcn_in_tower", False)))
         self.loss_evaluator = FCOSLossComputation(c.get("loss_gamma", 2.0), c.get("loss_alpha", 0.25))
         # reference rpn/fcos/inference.py:197-217 make_fcos_postprocessor
         self.box_selector_test = FCOSPostProcessor(

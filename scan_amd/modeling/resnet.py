@@ -13,7 +13,8 @@ FrozenBatchNorm2d (layers/batch_norm.py:5-24: y = x * w * rsqrt(var) + (b - mean
 affine per output channel of the conv in front of it: it is folded into that conv's weights and bias, so conv + BN
 (+ ReLU) is ONE launch of the conv kernels (3x3/stride 1 on the bf16x3 matrix-core kernel, 1x1 / stride 2 / 7x7 on the
 fp32 implicit-GEMM kernel).  DCNv2: the reference has no source for it (layers/misc.py:135-141 imports an absent
-package; USE_DCN_IN_TOWER False) -- not built.
+package; USE_DCN_IN_TOWER False); it is built from the published definition as layers.DFConv2d / ops.deform_conv2d
+(csrc/deform.hip) and sits in the FCOS towers behind FCOSHead(use_dcn_in_tower=True), off by default.
 """
 import torch
 from torch import nn

@@ -629,6 +629,93 @@ def conv_pool_fusable(x, weight, bias, shape):
 
 
 # ----------------------------------------------------------------------------- pyramid row split
+# ----------------------------------------------------------------------------- deformable convolution (DCNv2)
+def _row_pitch(t, cols, name):
+    """offset / mask operands: fp32 GPU matrices with at least `cols` columns whose rows are contiguous; a column slice of a
+    wider matrix is taken as it is (its pitch is passed on)"""
+    if not t.is_cuda:
+        raise RuntimeError("scan_amd ops run only on the GPU (HIP) -- got a %s tensor; no CPU fallback" % t.device)
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] < cols or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        raise RuntimeError("deform_conv2d: %s must be an fp32 [M, >= %d] matrix with contiguous rows" % (name, cols))
+    return t.stride(0)
+
+
+class _DeformSample(torch.autograd.Function):
+    """rows [M, Cs], offset [M, >= 18], mask [M, >= 9] or None -> cols [M, 9 * Cs] (csrc/deform.hip).  The backward has no
+    float atomics: the sampling gradient writes (destination row, weight) per (row, tap, corner), a stable sort of the
+    destinations and a per-row sum in sorted order give dx -- bit-reproducible with ``deterministic`` on or off."""
+
+    @staticmethod
+    def forward(ctx, x, offset, mask, shape, c):
+        _chk(x)
+        ld_off = _row_pitch(offset, 18, "offset")
+        ld_mask = _row_pitch(mask, 9, "mask") if mask is not None else 0
+        M, cs = x.shape
+        if M != shape.rows or offset.shape[0] != M or (mask is not None and mask.shape[0] != M):
+            raise RuntimeError("deform_conv2d: rows %d, offset %d, mask %s do not match %r"
+                               % (M, offset.shape[0], None if mask is None else mask.shape[0], shape))
+        cols = x.new_empty((M, 9 * cs))
+        call("scan_deform_sample_forward", _ptr(x), shape.ref(), c, cs, _ptr(offset), ld_off, _ptr(mask), ld_mask, _ptr(cols),
+             _stream())
+        ctx.save_for_backward(x, offset, mask)
+        ctx.cfg = (shape, c)
+        return cols
+
+    @staticmethod
+    def backward(ctx, dcols):
+        x, offset, mask = ctx.saved_tensors
+        shape, c = ctx.cfg
+        M, cs = x.shape
+        st = _stream()
+        dcols = dcols.contiguous()
+        doff = torch.empty(offset.shape, dtype=torch.float32, device=x.device)
+        dmask = torch.empty(mask.shape, dtype=torch.float32, device=x.device) if mask is not None else None
+        keys = torch.empty((36 * M,), dtype=torch.int32, device=x.device)
+        wgts = torch.empty((36 * M,), dtype=torch.float32, device=x.device)
+        call("scan_deform_sample_backward", _ptr(x), shape.ref(), c, cs, _ptr(dcols), _ptr(offset), offset.stride(0), _ptr(mask),
+             mask.stride(0) if mask is not None else 0, _ptr(doff), doff.shape[1], _ptr(dmask),
+             dmask.shape[1] if dmask is not None else 0, _ptr(keys), _ptr(wgts), st)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            # the inverted index: entries grouped by destination row, original order kept inside a group (key M = no destination)
+            skeys, perm = torch.sort(keys, stable=True)
+            seg = torch.searchsorted(skeys, torch.arange(M + 1, dtype=torch.int32, device=x.device))
+            dx = torch.empty_like(x)
+            call("scan_deform_dx_gather", _ptr(dcols), _ptr(perm), _ptr(seg), _ptr(wgts), M, c, cs, _ptr(dx), st)
+        return dx, doff if ctx.needs_input_grad[1] else None, dmask if mask is not None and ctx.needs_input_grad[2] else None, \
+            None, None
+
+
+def deform_conv2d(rows, offset, mask, weight, bias, shape, relu=False, cout_s=None, gn_sums=False):
+    """Modulated deformable 3x3 convolution (DCNv2; mask=None: DCNv1) on a pyramid: stride 1, padding 1, dilation 1, one
+    group, one deformable group, input and output on the same pyramid, all levels in one launch.  Returns rows [M, Cout_s].
+
+    rows [M, Cs]; offset [M, >= 18], column 2k = dy and 2k + 1 = dx of tap k = 3 i + j (the mmcv / torchvision order); mask
+    [M, >= 9] or None -- both may be column slices of one wider matrix; weight [O, C, 3, 3] (channels_last, as for conv2d).
+    The definition is include/scan_hip.h's (scan_deform_sample_forward).
+
+    Two steps: the nine taps are sampled into cols [M, 9 * Cs] (csrc/deform.hip), then y is conv2d's 1x1 convolution over cols
+    with the weight read as [O, 9 * Cs] -- so the op runs in the current CONV_MODE with that mode's error contract, and its
+    weight and bias gradients are the 1x1 ones.  The weight planes are split by that conv2d call under conv2d's own rules (a
+    view of the parameter is a temporary there: split per call, never cached, so there is nothing of this op's to invalidate).
+    gn_sums is accepted for symmetry with conv2d: the 1x1 kernels have no GroupNorm-sums epilogue, so groupnorm_relu takes its
+    own statistics pass.
+
+    Memory: cols is kept for the backward and its gradient dcols has the same size, M * 9 * Cs floats each -- about 1.6 GB
+    each on the bench pyramid (N = 4, 1024 x 2048, C = 256).  That fits this board and is not chunked."""
+    if not (rows.is_cuda and weight.is_cuda):
+        raise RuntimeError("scan_amd ops run only on the GPU (HIP); no CPU fallback")
+    o, c, kh, kw = weight.shape
+    cs = rows.shape[1]
+    if (kh, kw) != (3, 3) or c > cs:
+        raise RuntimeError("deform_conv2d: needs a [O, C, 3, 3] weight with C <= Cs (got %s, Cs=%d)" % (tuple(weight.shape), cs))
+    if gn_sums:
+        _gn_sums.clear()  # this output carries no sums: a pending hand-over must not be matched to its address
+    cols = _DeformSample.apply(rows, offset, mask, shape, c)
+    w1 = pack_weight(weight, cs).reshape(o, 9 * cs, 1, 1)  # [O][tap][Cs]: the column order of cols
+    return conv2d(cols, w1, bias, shape, 1, 1, relu=relu, cout_s=cout_s, gn_sums=gn_sums)
+
+
 class _SplitLevels(torch.autograd.Function):
     """rows [M, C] -> one view per level.  The backward concatenates the level gradients once instead of
     autograd's per-slice zero-fill + add of full-size tensors."""
