@@ -627,6 +627,45 @@ int scan_fcos_nodes(const scan_pyramid_t* d, const int32_t* level_pos, const int
                     const int32_t* pos_list, const int32_t* neg_list, int64_t* node_index, int64_t* node_labels,
                     int64_t* pos_inds, float* reg_pos, float* ctr_pos, void* stream);
 
+/* ---- the ATSS head's ground-truth plan and GIoU loss (csrc/atss.hip; reference rpn/atss/loss.py:159-218, 354, 360-373 for
+ *      POSITIVE_TYPE 'ATSS', REGRESSION_TYPE 'BOX', one anchor per location).  The anchor of pyramid row (level l, y, x) has
+ *      centre (x * s + (s - 1) / 2, y * s + (s - 1) / 2) and corners centre -/+ (a - 1) / 2 with s = strides[l],
+ *      a = anchor_sizes[l]; no anchor tensor exists.  Inputs as scan_fcos_assign (boxes 16-byte aligned, ng[n] <= G), topk in
+ *      1..64.  Per image and box: candidates = per level the min(topk, anchors) anchors nearest to the box centre (fp32
+ *      sqrt(dx * dx + dy * dy), ties to the smaller row); threshold = mean + unbiased std of the candidates' IoUs (+1 widths;
+ *      fp64 sums rounded to fp32 once); positive = IoU >= threshold and centre inside the box with min(l, t, r, b) > 0.01; a
+ *      contested anchor takes the box of largest IoU, ties to the smaller box index; no positive box: label 0 (also every row
+ *      of an image with ng = 0 -- the reference raises there).  The tie rules are this library's; the reference leaves them
+ *      to torch.topk / torch.max.  Bit-reproducible whatever scan_tune "deterministic" says (integer max, no float atomics).
+ *      scan_atss_assign: labels [M] (+ int32 copy), matched [M] = box index (0 where background), level_pos
+ *      [SCAN_MAX_LEVELS] device counters; ws: scan_atss_assign_ws_bytes bytes, 8-byte aligned.  scan_fcos_compact on labels
+ *      lists the positives; scan_atss_targets (level_pos: HOST copy) writes pos_inds [n_pos] in row order, reg_pos [n_pos][4]
+ *      = BoxCoder.encode(matched box, anchor) (weights 10, 10, 5, 5) and ctr_pos [n_pos] = centerness of decode(encode(..))
+ *      against the anchor centre, both formed in fp64 and rounded to fp32 once. ---- */
+int64_t scan_atss_assign_ws_bytes(const scan_pyramid_t* d, int32_t G, int32_t topk);
+int scan_atss_assign(const scan_pyramid_t* d, const int32_t* strides, const float* anchor_sizes, const float* boxes,
+                     const int64_t* glabels, const int32_t* ng, int32_t G, int32_t topk, int64_t* labels,
+                     int32_t* labels_i32, int32_t* matched, int32_t* level_pos, void* ws, void* stream);
+int scan_atss_targets(const scan_pyramid_t* d, const int32_t* strides, const float* anchor_sizes, const int32_t* level_pos,
+                      const float* boxes, int32_t G, const int32_t* matched, const int32_t* pos_list, int64_t* pos_inds,
+                      float* reg_pos, float* ctr_pos, void* stream);
+/* GIoU loss of anchor deltas (loss.py:64-105): pred / target [P][4] deltas (16-byte aligned) of the pyramid rows rows [P],
+ * weight [P] (required).  Forward ADDS sum(w * (1 - GIoU)) to out2[0] and sum(w) to out2[1] (clear them first); the _ordered
+ * twin writes both from per-block slots in a fixed order (ws: scan_atss_giou_ordered_ws_floats floats).  Decode clamps dw, dh
+ * at log(1000 / 16), corners are centre -/+ 0.5 * (w - 1), the prediction takes x2 = max(x1, x2), the intersection counts only
+ * where both extents are positive, 1e-7 is added to enclosure and union.  Backward: d_pred [P][4] = g_num_dev[0] * d(sum)/d pred;
+ * where a min / max has equal arguments the gradient goes to its first argument (the prediction's corner; x1 in max(x1, x2)). */
+int scan_atss_giou_forward(const scan_pyramid_t* d, const int32_t* strides, const float* anchor_sizes, const float* pred,
+                           const float* target, const int64_t* rows, const float* weight, int64_t P, float* out2,
+                           void* stream);
+int64_t scan_atss_giou_ordered_ws_floats(int64_t P);
+int scan_atss_giou_forward_ordered(const scan_pyramid_t* d, const int32_t* strides, const float* anchor_sizes,
+                                   const float* pred, const float* target, const int64_t* rows, const float* weight,
+                                   int64_t P, float* out2, float* ws, void* stream);
+int scan_atss_giou_backward(const scan_pyramid_t* d, const int32_t* strides, const float* anchor_sizes, const float* pred,
+                            const float* target, const int64_t* rows, const float* weight, int64_t P,
+                            const float* g_num_dev, float* d_pred, void* stream);
+
 /* ---- FPN top-down join on NHWC rows (reference backbone/fpn.py:62-75: inner = lateral + F.interpolate(top,
  *      scale_factor=2, mode="nearest")).  lat / y [N, 2h, 2w, C], coarse [N, h, w, C], C % 4 == 0.  Backward:
  *      d_lateral is the incoming gradient itself, d_coarse its 2x2 window sums (scan_downsample2x_sum: g [N, 2h, 2w, C]

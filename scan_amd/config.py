@@ -71,6 +71,18 @@ DEFAULTS = {
 }
 
 
+# The ATSS head (MODEL.ATSS_ON, modeling/atss.py) with the reference's defaults (defaults.py:287-333; LOSS_GAMMA is assigned
+# twice there and ends at 5.0).  Kept OUT of DEFAULTS: hot_path_view is compared key for key with the golden cfg of the shipped
+# experiments, none of which builds this head.  atss_settings(cfg) reads a cfg's MODEL.ATSS block over these.
+ATSS_DEFAULTS = {
+    "NUM_CLASSES": 81, "ANCHOR_SIZES": (64, 128, 256, 512, 1024), "ASPECT_RATIOS": (1.0,),
+    "ANCHOR_STRIDES": (8, 16, 32, 64, 128), "STRADDLE_THRESH": 0, "OCTAVE": 2.0, "SCALES_PER_OCTAVE": 1, "NUM_CONVS": 4,
+    "USE_DCN_IN_TOWER": False, "LOSS_ALPHA": 0.25, "LOSS_GAMMA": 5.0, "POSITIVE_TYPE": "ATSS", "FG_IOU_THRESHOLD": 0.5,
+    "BG_IOU_THRESHOLD": 0.4, "TOPK": 9, "REGRESSION_TYPE": "BOX", "REG_LOSS_WEIGHT": 2.0, "PRIOR_PROB": 0.01,
+    "INFERENCE_TH": 0.05, "NMS_TH": 0.6, "PRE_NMS_TOP_N": 1000,
+}
+
+
 class Cfg(dict):
     """Nested dict with attribute access (what the path needs of yacs.config.CfgNode)."""
 
@@ -246,3 +258,36 @@ def settings(cfg):
         val_iter=int(cfg.SOLVER.VAL_ITER), val_type=str(cfg.SOLVER.VAL_TYPE), adapt_val_on=bool(cfg.SOLVER.ADAPT_VAL_ON),
         solver={k: solver_group(cfg, k) for k in ("backbone", "fcos", "middle_head", "dis")},
     )
+
+
+def atss_settings(cfg):
+    """Flat view of MODEL.ATSS for modeling.atss.ATSSModule; raises, naming the key, on every value that is not built: the
+    head is the one the reference's configs/epm/da_ga_sim10k_VGG_16_FPN_4x_atss.yaml selects (POSITIVE_TYPE 'ATSS',
+    REGRESSION_TYPE 'BOX', one anchor per location on the five pyramid levels)."""
+    A = Cfg(ATSS_DEFAULTS)
+    A._merge(cfg.MODEL.get("ATSS", {}))
+    if A.POSITIVE_TYPE != "ATSS":
+        raise ValueError("MODEL.ATSS.POSITIVE_TYPE %r is not built (only 'ATSS'; not SSC, IoU, TOPK, ADAPT_ATSS)" % (A.POSITIVE_TYPE,))
+    if A.REGRESSION_TYPE != "BOX":
+        raise ValueError("MODEL.ATSS.REGRESSION_TYPE %r is not built (only 'BOX')" % (A.REGRESSION_TYPE,))
+    if tuple(A.ASPECT_RATIOS) != (1.0,):
+        raise ValueError("MODEL.ATSS.ASPECT_RATIOS %r: one anchor per location, ratio 1.0, is what is built" % (A.ASPECT_RATIOS,))
+    if int(A.SCALES_PER_OCTAVE) != 1:
+        raise ValueError("MODEL.ATSS.SCALES_PER_OCTAVE %r: one anchor per location is what is built" % (A.SCALES_PER_OCTAVE,))
+    if tuple(A.ANCHOR_STRIDES) != (8, 16, 32, 64, 128):
+        raise ValueError("MODEL.ATSS.ANCHOR_STRIDES %r: the pyramid has strides (8, 16, 32, 64, 128)" % (A.ANCHOR_STRIDES,))
+    if len(A.ANCHOR_SIZES) != 5 or any(float(a) < 1 for a in A.ANCHOR_SIZES):
+        raise ValueError("MODEL.ATSS.ANCHOR_SIZES %r: one size >= 1 per pyramid level" % (A.ANCHOR_SIZES,))
+    if not 1 <= int(A.TOPK) <= 64:
+        raise ValueError("MODEL.ATSS.TOPK %r: 1..64 are built" % (A.TOPK,))
+    if not 2 <= int(A.NUM_CLASSES) <= 32:
+        raise ValueError("MODEL.ATSS.NUM_CLASSES %r (background included): 2..32 are built" % (A.NUM_CLASSES,))
+    if int(A.NUM_CONVS) < 1:
+        raise ValueError("MODEL.ATSS.NUM_CONVS %r: at least one tower conv" % (A.NUM_CONVS,))
+    return dict(
+        num_classes=int(A.NUM_CLASSES), anchor_sizes=tuple(float(a) for a in A.ANCHOR_SIZES),
+        anchor_strides=tuple(int(s) for s in A.ANCHOR_STRIDES), num_convs=int(A.NUM_CONVS),
+        dcn_in_tower=bool(A.USE_DCN_IN_TOWER), loss_alpha=float(A.LOSS_ALPHA), loss_gamma=float(A.LOSS_GAMMA),
+        topk=int(A.TOPK), reg_loss_weight=float(A.REG_LOSS_WEIGHT), prior_prob=float(A.PRIOR_PROB),
+        inference_th=float(A.INFERENCE_TH), pre_nms_top_n=int(A.PRE_NMS_TOP_N), nms_th=float(A.NMS_TH),
+        detections_per_img=int(cfg.TEST.DETECTIONS_PER_IMG))

@@ -23,6 +23,7 @@ from .modeling.backbone import build_backbone
 from .modeling.condgraph import build_condgraph
 from .modeling.discriminator import FCOSDiscriminator_con
 from .modeling import fcos as fcos_mod
+from .modeling.atss import ATSSModule, build_atss
 from .modeling.fcos import build_fcos
 from .modeling.resnet import build_resnet_fpn_backbone
 
@@ -43,11 +44,16 @@ CONFIGS = {name: config.settings(config.load(name)) for name in ("c2f", "s2c", "
 
 
 def build_model(num_classes=9, test_mode="precision", device="cuda", attn_dropout=0.1, transfer_cfg=("NODES", "ADJ"),
-                conv_body="VGG-16-FPN-RETINANET", settings=None, dcn_in_tower=False):
+                conv_body="VGG-16-FPN-RETINANET", settings=None, dcn_in_tower=False, rpn="fcos", atss_settings=None):
     """dict MODEL{backbone, middle_head, fcos, dis_P*_CON} like tools/train_net_da.py:43-48,223-274.
     settings: a config.settings(cfg) dict (e.g. engine.CONFIGS["s2c"]); it overrides the four model keywords.
     dcn_in_tower: the last conv of the FCOS head's two towers is a deformable one (layers.DFConv2d; upstream FCOS's
-    MODEL.FCOS.USE_DCN_IN_TOWER).  A keyword only: no shipped config has the key."""
+    MODEL.FCOS.USE_DCN_IN_TOWER).  A keyword only: no shipped config has the key.
+    rpn: "fcos" or "atss" -- model["fcos"] is then the ATSS head (modeling/atss.py; the reference keeps that dictionary key
+    whichever head build_rpn returns), built from the reference's defaults with this model's num_classes and
+    dcn_in_tower, overridden by atss_settings (config.atss_settings keys)."""
+    if rpn not in ("fcos", "atss"):
+        raise ValueError("rpn=%r: 'fcos' or 'atss'" % (rpn,))
     s = dict(CONFIGS["c2f"])
     s.update(num_classes=num_classes, test_mode=test_mode, transfer_cfg=tuple(transfer_cfg), conv_body=conv_body)
     if settings is not None:
@@ -66,7 +72,8 @@ def build_model(num_classes=9, test_mode="precision", device="cuda", attn_dropou
     model = {
         "backbone": backbone,
         "middle_head": build_condgraph(s, 256, s["num_classes"], s["transfer_cfg"]),
-        "fcos": build_fcos(s, s["num_classes"], s["test_mode"]),
+        "fcos": build_fcos(s, s["num_classes"], s["test_mode"]) if rpn == "fcos" else
+        build_atss(dict({"num_classes": s["num_classes"], "dcn_in_tower": s["dcn_in_tower"]}, **(atss_settings or {}))),
     }
     model["middle_head"].multihead_attn.dropout.p = attn_dropout
     model["middle_head"].multihead_attn.attn_dropout.p = attn_dropout
@@ -322,6 +329,10 @@ class Trainer:
         default: the C2F yaml.  base_lr / con_dis_lambda override it."""
         self.model = model
         self.settings = settings = dict(settings or CONFIGS["c2f"])
+        world = dist.get_world_size() if dist.is_initialized() else 1
+        if isinstance(model.get("fcos"), ATSSModule) and (distributed or (distributed is None and world > 1)):
+            # reference rpn/atss/loss.py:385, 393 all-reduces n_pos and the centerness sum across ranks: not built
+            raise ValueError("a distributed Trainer with the ATSS head is not built (its loss normalisers are per rank)")
         self.con_dis_lambda = settings["con_dis_lambda"] if con_dis_lambda is None else con_dis_lambda
         # ONE gradient arena for all sub-models, ordered so that what becomes final together is contiguous: the FCOS
         # head, the discriminators, then middle head and backbone.  Gradient zeroing is one fill and data parallelism

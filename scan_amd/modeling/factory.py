@@ -23,6 +23,7 @@ import torch
 from .. import config, ops
 from ..structures import BoxList, to_image_list
 from . import fcos as fcos_mod
+from .atss import ATSSModule
 from .backbone import VGG16FPN
 from .condgraph import GRAPHModule
 from .discriminator import FCOSDiscriminator_con
@@ -131,8 +132,9 @@ def build_middle_head(cfg, in_channels):
     return _channels_last_(m)
 
 
-class FCOSModuleNCHW(FCOSModule):
-    """FCOSModule.forward of the reference (rpn/fcos/fcos.py:144-232)."""
+class _RpnForwardNCHW:
+    """the reference's dense-head call (rpn/fcos/fcos.py:144-232, rpn/atss/atss.py:205-270) over an engine module that has
+    head / loss_evaluator / box_selector_test and forward(image_sizes, rows, shape, targets, act_maps)"""
 
     def forward(self, images, features, targets=None, return_maps=False, act_maps=None):
         """training: (None, losses, score_maps | None) -- score_maps = {"box_cls", "box_regression", "centerness"} as
@@ -143,7 +145,7 @@ class FCOSModuleNCHW(FCOSModule):
         rows, shape = ops.pack_levels(features)
         targets = target_tuples(targets)
         if not self.training:
-            maps = _rows_exact(act_maps)[0] if act_maps is not None else None
+            maps = _rows_exact(act_maps)[0] if act_maps is not None and self.mode != "common" else None  # 'common' scores alone
             dets, _ = super().forward(il.image_sizes, rows, shape, act_maps=maps)
             boxlists = []
             for (boxes, scores, labels), (h, w) in zip(dets, il.image_sizes):
@@ -165,12 +167,24 @@ class FCOSModuleNCHW(FCOSModule):
         return None, losses, score_maps
 
 
+class FCOSModuleNCHW(_RpnForwardNCHW, FCOSModule):
+    """FCOSModule.forward of the reference (rpn/fcos/fcos.py:144-232)."""
+
+
+class ATSSModuleNCHW(_RpnForwardNCHW, ATSSModule):
+    """ATSSModule.forward of the reference (rpn/atss/atss.py:205-270) with the ``act_maps`` argument foward_detector passes
+    (engine/trainer.py:20-72): accepted and ignored.  The reference's own ATSSModule.forward lacks it and cannot be called
+    by that function."""
+
+
 def build_rpn(cfg, in_channels):
-    """reference modeling/rpn/rpn.py:201-212."""
-    if not cfg.MODEL.get("FCOS_ON", False):
-        raise ValueError("MODEL.FCOS_ON is False: only the FCOS head is built (no RPN / RetinaNet / ATSS)")
+    """reference modeling/rpn/rpn.py:201-212: ATSS_ON -> the ATSS head, else FCOS_ON -> the FCOS head."""
     if in_channels != 256:
-        raise ValueError("the FCOS head is built for 256 input channels, got %d" % in_channels)
+        raise ValueError("the dense heads are built for 256 input channels, got %d" % in_channels)
+    if cfg.MODEL.get("ATSS_ON", False):
+        return _channels_last_(ATSSModuleNCHW(cfg=config.atss_settings(cfg)))
+    if not cfg.MODEL.get("FCOS_ON", False):
+        raise ValueError("MODEL.ATSS_ON and MODEL.FCOS_ON are False: only those two heads are built (no RPN / RetinaNet)")
     s = config.settings(cfg)
     return _channels_last_(FCOSModuleNCHW(s["num_classes"], s["test_mode"], s))
 

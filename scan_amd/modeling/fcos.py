@@ -70,11 +70,13 @@ class TargetPlan:
 
 
 _plan = [None]
+_plan_caches = [_plan]  # every head's one-slot plan cache (modeling/atss.py adds its own)
 
 
 def reset_target_plan():
     """engine.Trainer calls this at the top of every iteration: a plan never outlives its batch."""
-    _plan[0] = None
+    for c in _plan_caches:
+        c[0] = None
 
 
 def source_node_index(labels, shape):
@@ -98,11 +100,13 @@ def source_node_index(labels, shape):
     return torch.cat([neg, pos], 0), torch.cat([labels.new_zeros(neg.numel()), labels[pos]], 0)
 
 
-def target_plan(shape, targets, device, side_stream=None, after=None):
+def target_plan(shape, targets, device, side_stream=None, after=None, build=None, cache=None):
     """The TargetPlan of (shape, targets); cached for the current batch.  With ``side_stream`` the plan is built
-    there (after event ``after``) and the calling stream is made to wait for it."""
+    there (after event ``after``) and the calling stream is made to wait for it.  build / cache: another head's plan
+    builder (shape, targets, device) -> plan and its one-slot cache (modeling/atss.py); default: the FCOS plan."""
+    build, cache = build or _build_plan, cache or _plan
     key = (id(targets), tuple(shape.sizes), shape.n_images, str(device))
-    p = _plan[0]
+    p = cache[0]
     if p is not None and p.key == key and p.targets is targets:
         return p
     cur = torch.cuda.current_stream() if device.type == "cuda" else None
@@ -111,18 +115,18 @@ def target_plan(shape, targets, device, side_stream=None, after=None):
         if after is not None and not host_targets:  # device-resident ground truth was produced on the calling stream
             side_stream.wait_event(after)
         with torch.cuda.stream(side_stream):
-            p = _build_plan(shape, targets, device)
+            p = build(shape, targets, device)
             p.ready = torch.cuda.Event()
             p.ready.record(side_stream)
         cur.wait_event(p.ready)
-        for name in TargetPlan.__slots__:
+        for name in type(p).__slots__:
             t = getattr(p, name, None)
             if isinstance(t, torch.Tensor):
                 t.record_stream(cur)
     else:
-        p = _build_plan(shape, targets, device)
+        p = build(shape, targets, device)
     p.key, p.targets = key, targets
-    _plan[0] = p
+    cache[0] = p
     return p
 
 
@@ -130,12 +134,8 @@ DEVICE_PLAN = True  # False: the torch spelling below also on the GPU (A/B, cros
 _plan_staging = {}  # (N, device) -> pinned host buffers of the packed ground truth, grown (never shrunk) to a power of two of boxes
 
 
-def _build_plan_device(shape, targets, device):
-    """The plan in three launches of csrc/targets.hip and ONE host read (the five per-level positive counts) instead of
-    ~115 torch launches with a dozen host round trips; bit-identical to the torch spelling below."""
-    p = TargetPlan()
-    p.ready = None
-    N, L, M = shape.n_images, shape.n_levels, shape.rows
+def upload_ground_truth(N, targets, device):
+    """(boxes [N, G, 4] fp32 xyxy zero-padded, labels [N, G] int64, counts [N] int32, G) of a batch on ``device``."""
     G = max(1, max(int(b.shape[0]) for b, _ in targets))
     if all(not b.is_cuda and not l.is_cuda for b, l in targets):
         # ground truth as the collator hands it over (host tensors): packed in pinned staging buffers and uploaded on
@@ -170,6 +170,16 @@ def _build_plan_device(shape, targets, device):
                 boxes[i, :g] = b.to(device=device, dtype=torch.float32)
                 glab[i, :g] = l.to(device=device, dtype=torch.int64)
         ng = torch.tensor([int(b.shape[0]) for b, _ in targets], dtype=torch.int32).to(device)
+    return boxes, glab, ng, G
+
+
+def _build_plan_device(shape, targets, device):
+    """The plan in three launches of csrc/targets.hip and ONE host read (the five per-level positive counts) instead of
+    ~115 torch launches with a dozen host round trips; bit-identical to the torch spelling below."""
+    p = TargetPlan()
+    p.ready = None
+    N, L, M = shape.n_images, shape.n_levels, shape.rows
+    boxes, glab, ng, G = upload_ground_truth(N, targets, device)
     st = ops._stream()
     p.labels = torch.empty((M,), dtype=torch.int64, device=device)
     p.labels_i32 = torch.empty((M,), dtype=torch.int32, device=device)
@@ -260,6 +270,7 @@ def centerness_targets(reg):
 
 class FCOSHead(nn.Module):
     """reference fcos.py:13-114 with REG_CTR_ON True."""
+    exp_reg = True  # bbox_reg = exp(scale * bbox_pred); the ATSS head (modeling/atss.py) regresses plain deltas
 
     def __init__(self, num_classes=9, num_convs=4, prior_prob=0.01, use_dcn_in_tower=False):
         super().__init__()
@@ -290,8 +301,8 @@ class FCOSHead(nn.Module):
         out = ops.conv2d(rt, w, b, shape, 3, 1, cout_s=8)
         scale_rows = torch.cat([self.scales[l].scale.expand(shape.row_off[l + 1] - shape.row_off[l])
                                 for l in range(shape.n_levels)], 0)
-        bbox_reg = torch.exp(out[:, :4] * scale_rows[:, None])
-        return logits, bbox_reg, out[:, 4]
+        bbox_reg = out[:, :4] * scale_rows[:, None]
+        return logits, torch.exp(bbox_reg) if self.exp_reg else bbox_reg, out[:, 4]
 
 
 class FCOSLossComputation:
@@ -337,6 +348,7 @@ class _PendingDetections:
         self.main = torch.cuda.current_stream() if det.is_cuda else None
         self.results = None
         self.inputs = None
+        self.rows = None
         if self.main is not None:
             self.counts = torch.empty((n_images,), dtype=torch.int64, pin_memory=True)
             self.counts.copy_(ok.sum(1), non_blocking=True)
@@ -446,6 +458,15 @@ class FCOSPostProcessor:
                 t.record_stream(s_)
         return pend
 
+    def _level_points(self, shape, dev):
+        """per level, what _decode needs of each location ([h * w, D]): here the FCOS locations"""
+        return compute_locations(shape, dev)
+
+    def _decode(self, lc, rg):
+        """boxes [N, K, 4] of the selected rows' points lc [N, K, D] and regression outputs rg [N, K, 4]"""
+        return torch.stack([lc[..., 0] - rg[..., 0], lc[..., 1] - rg[..., 1], lc[..., 0] + rg[..., 2],
+                            lc[..., 1] + rg[..., 3]], -1)
+
     def _select(self, shape, box_cls, box_regression, centerness, image_sizes):
         """box_cls [M,C] (logits for 'common', fused probabilities otherwise), box_regression [M,4],
         centerness [M] logits.  Returns per image (boxes [k,4], scores [k], labels [k]) -- or, with self.deferred, the
@@ -458,7 +479,7 @@ class FCOSPostProcessor:
         classes and one host round trip for the candidate counts instead of one per (level, image)."""
         N, C = shape.n_images, box_cls.shape[1]
         dev = box_cls.device
-        locs = compute_locations(shape, dev)
+        locs = self._level_points(shape, dev)
         prob = box_cls.sigmoid() if self.mode == "common" else box_cls
         score = torch.where(prob > self.pre_nms_thresh, prob * centerness.sigmoid()[:, None], prob.new_full((), -1.0))
         sel_score, sel_cls, sel_row, sel_loc = [], [], [], []
@@ -478,10 +499,9 @@ class FCOSPostProcessor:
             sel_loc.append(locs[l][loc])
         val = torch.cat(sel_score, 1)  # [N, K]
         lab = torch.cat(sel_cls, 1)
-        rg = box_regression[torch.cat(sel_row, 1)]  # [N, K, 4]
-        lc = torch.cat(sel_loc, 1)  # [N, K, 2]
-        det = torch.stack([lc[..., 0] - rg[..., 0], lc[..., 1] - rg[..., 1], lc[..., 0] + rg[..., 2],
-                           lc[..., 1] + rg[..., 3]], -1)
+        rows = torch.cat(sel_row, 1)
+        rg = box_regression[rows]  # [N, K, 4]
+        det = self._decode(torch.cat(sel_loc, 1), rg)
         # BoxList.clip_to_image (TO_REMOVE = 1) against each image's true size
         lim = torch.tensor([[w - 1, h - 1, w - 1, h - 1] for h, w in image_sizes], dtype=det.dtype, pin_memory=det.is_cuda)
         lim = lim.to(dev, non_blocking=True)
@@ -489,6 +509,7 @@ class FCOSPostProcessor:
         ws, hs = det[..., 2] - det[..., 0] + 1, det[..., 3] - det[..., 1] + 1
         ok = (val > 0) & (ws >= self.min_size) & (hs >= self.min_size)
         pend = _PendingDetections(self, ok, det, val, lab, N, self.deferred)
+        pend.rows = rows  # pyramid row of every selected (location, class), beside ok / det / val / lab
         return pend if self.deferred else pend.finish()
 
 

@@ -1337,6 +1337,41 @@ def iou_loss(pred, target, weight=None):
     return _IouLoss.apply(pred.contiguous(), target.contiguous(), weight.contiguous() if weight is not None else None)
 
 
+class _AtssGiouLoss(torch.autograd.Function):
+    """sum(w * (1 - GIoU)) / sum(w) of anchor deltas (reference rpn/atss/loss.py:64-105, 396-397); the anchors are formed in the
+    kernel from the rows (csrc/atss.hip).  The weight is a target (the centerness of the matched box): no gradient to it."""
+
+    @staticmethod
+    def forward(ctx, pred, target, rows, weight, shape, strides, sizes):
+        _chk(pred, target, rows, weight)
+        P = pred.shape[0]
+        out = pred.new_zeros((2,))
+        geo = (shape.ref(), (ctypes.c_int32 * shape.n_levels)(*strides), (ctypes.c_float * shape.n_levels)(*sizes))
+        _call_reduction("scan_atss_giou", "_forward", pred, (P,), *geo, _ptr(pred), _ptr(target), _ptr(rows), _ptr(weight), P,
+                        _ptr(out))
+        ctx.save_for_backward(pred, target, rows, weight, out)
+        ctx.geo = geo + (shape,)  # (the shape owns the descriptor geo[0] points to)
+        return out[0] / out[1]
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, target, rows, weight, out = ctx.saved_tensors
+        gn = (g / out[1]).reshape(1).contiguous()
+        d = torch.empty_like(pred)
+        call("scan_atss_giou_backward", *ctx.geo[:3], _ptr(pred), _ptr(target), _ptr(rows), _ptr(weight), pred.shape[0], _ptr(gn),
+             _ptr(d), _stream())
+        return d, None, None, None, None, None, None
+
+
+def atss_giou_loss(pred, target, rows, weight, shape, strides, sizes):
+    """pred / target [P, 4] BoxCoder deltas of the pyramid rows ``rows`` [P] int64, weight [P]: the centerness-weighted GIoU
+    loss of the ATSS head, normalised by the sum of the weights."""
+    if len(strides) != shape.n_levels or len(sizes) != shape.n_levels:
+        raise ValueError("atss_giou_loss: %d strides / %d anchor sizes for %d levels" % (len(strides), len(sizes), shape.n_levels))
+    return _AtssGiouLoss.apply(pred.contiguous(), target.contiguous(), rows.contiguous(), weight.contiguous(), shape,
+                               [int(s) for s in strides], [float(a) for a in sizes])
+
+
 class _BceLogitsMean(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, targets):
