@@ -698,11 +698,21 @@ int scan_add_relu(const float* a, const float* b, float* y, int64_t n, void* str
  *      prepare: neighbour bit matrix (fp32 matrix-core P P^T, fp64 re-check at the threshold), core mask, seed;
  *               info[0] <- lowest core index (n when there is no core point).
  *      bfs_step: one breadth-first level over the core graph; call with parity 0, 1, 0, ... while *changed reads 1.
- *      finish:  in_cluster0[i] = 1 iff sklearn would label point i with 0. ---- */
+ *      neighbor_counts: counts[i] (device, n int32) <- the number of points within eps of point i, itself included, as
+ *               the last prepare on this workspace found them; a device-to-device copy, nothing in ws changes.
+ *      finish:  in_cluster0[i] = 1 iff sklearn would label point i with 0.
+ *      eps is a float: a caller's double is rounded to fp32 FIRST and that value is squared in double, so the threshold is
+ *      fp32(eps)^2.  sklearn squares the double; the two decide differently only for a pair whose distance lies between eps
+ *      and fp32(eps), i.e. within 6e-8 relative of an eps that fp32 does not represent.
+ *      Re-check band: a pair goes to the fp64 re-check when |d2 - eps^2| in fp32 is within bandc (|pi|^2 + |pj|^2) (+ 1e-6
+ *      eps^2) of 0.  bandc covers the worst-case error of a D-term dot product, (D - 1) 2^-24 for the fp32 matrix cores and
+ *      (3 D - 1) 2^-24 + 3 * 2^-18 for bf16x3, with 12 % / 3 % on top: 1.7e-5 / 5.9e-5 for every D <= 256, the same bounds
+ *      scaled by the same headroom for larger D. ---- */
 #define SCAN_DBSCAN_MAX 1200000
 int64_t scan_dbscan_ws_bytes(int64_t n);
 int scan_dbscan_prepare(const float* pts, int64_t n, int32_t D, float eps, int32_t min_samples, void* ws,
                         int32_t* info, void* stream);
+int scan_dbscan_neighbor_counts(int64_t n, const void* ws, int32_t* counts, void* stream);
 int scan_dbscan_bfs_step(int64_t n, void* ws, int32_t parity, int32_t* changed, void* stream);
 int scan_dbscan_finish(int64_t n, void* ws, uint8_t* in_cluster0, void* stream);
 

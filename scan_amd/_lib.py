@@ -199,6 +199,7 @@ SIGNATURES = {
     "scan_downsample2x_sum": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "scan_add_relu": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp]),
     "scan_dbscan_prepare": (ctypes.c_int, [c_vp, c_i64, c_i32, c_f32, c_i32, c_vp, c_vp, c_vp]),
+    "scan_dbscan_neighbor_counts": (ctypes.c_int, [c_i64, c_vp, c_vp, c_vp]),
     "scan_dbscan_bfs_step": (ctypes.c_int, [c_i64, c_vp, c_i32, c_vp, c_vp]),
     "scan_dbscan_finish": (ctypes.c_int, [c_i64, c_vp, c_vp, c_vp]),
     "scan_sgd_momentum": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_i32, c_vp]),

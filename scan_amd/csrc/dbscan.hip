@@ -54,7 +54,7 @@ __device__ __forceinline__ void db_split4(const float4 v, db_bf16x4& hi, db_bf16
 
 template <bool BF>
 __global__ __launch_bounds__(256) void dbscan_neighbors_kernel(const float* __restrict__ p, int64_t n, int D,
-                                                               const double* __restrict__ sq, double eps2,
+                                                               const double* __restrict__ sq, double eps2, float bandc,
                                                                uint32_t* __restrict__ bits, int64_t nw) {
   // fp32: As / Bs [128][36] floats; bf16x3: four planes (A hi, A lo, B hi, B lo) [128][40] bf16 in the same bytes
   constexpr int F32_FLOATS = 2 * DB_T * DB_LD, BF_FLOATS = 4 * DB_T * DB_LDH / 2;
@@ -179,7 +179,6 @@ __global__ __launch_bounds__(256) void dbscan_neighbors_kernel(const float* __re
   }
   __syncthreads();
   const float eps2f = (float)eps2;
-  const float bandc = BF ? 5.9e-5f : 1.7e-5f;
 #pragma unroll
   for (int tn = 0; tn < 2; ++tn) {
     const int64_t j = j0 + (wn * 2 + tn) * 32 + lrow;
@@ -194,11 +193,12 @@ __global__ __launch_bounds__(256) void dbscan_neighbors_kernel(const float* __re
         const int64_t i = i0 + (wm * 2 + tm) * 32 + rr;
         const bool valid = i < n && j < n;
         const float ssum = sqa[(wm * 2 + tm) * 32 + rr] + sjf;
-        // d2 - eps2 in fp32.  Band: worst-case fp32 accumulation error of the 256-term dot product, (K - 1) 2^-24
-        // sum |a_k b_k| <= 1.53e-5 (si + sj) / 2, doubled by the factor 2 in front of it.  bf16x3: with a = ah + al + da,
-        // |da| <= 2^-18 |a| (two round-to-nearest bf16 steps), the dropped part of a product is al bl + da b + a db,
-        // <= 3 * 2^-18 |a b| = 1.15e-5 |a b|; the products kept are exact in fp32 and there are three times as many
-        // of them to add up, (3 K - 1) 2^-24 = 4.6e-5 in the same worst-case count: 5.8e-5 (si + sj) on d2
+        // d2 - eps2 in fp32.  Band (bandc, from db_bandc on the host; the figures are those of K = D = 256): worst-case fp32
+        // accumulation error of the K-term dot product, (K - 1) 2^-24 sum |a_k b_k| <= 1.53e-5 (si + sj) / 2, doubled by the
+        // factor 2 in front of it.  bf16x3: with a = ah + al + da, |da| <= 2^-18 |a| (two round-to-nearest bf16 steps), the
+        // dropped part of a product is al bl + da b + a db, <= 3 * 2^-18 |a b| = 1.15e-5 |a b|; the products kept are exact in
+        // fp32 and there are three times as many of them to add up, (3 K - 1) 2^-24 = 4.6e-5 in the same worst-case count:
+        // 5.8e-5 (si + sj) on d2
         const float t = __builtin_fmaf(-2.0f, acc[tm][tn][r], ssum - eps2f);
         const float band = __builtin_fmaf(bandc, ssum, 1e-6f * eps2f + 1e-9f);
         const bool inband = valid && fabsf(t) <= band;
@@ -350,6 +350,18 @@ static DbWs db_split(void* ws, int64_t n) {
   return w;
 }
 
+// Relative half-width of the re-check band around eps^2, in units of (si + sj): the worst-case bounds derived in the epilogue
+// of dbscan_neighbors_kernel for a D-term dot product, (D - 1) 2^-24 (fp32) and (3 D - 1) 2^-24 + 3 * 2^-18 (bf16x3), times the
+// headroom the constants 1.7e-5 / 5.9e-5 have over those bounds at D = 256 (the fp32 epilogue's own 4 * 2^-24 lives in it).
+// D <= 256 keeps the two constants themselves: the band only has to be wide enough, and the workload (D = 256) keeps its bits.
+static float db_bandc(int D, bool bf) {
+  const double u = 1.0 / 16777216.0, c256 = bf ? 5.9e-5 : 1.7e-5;
+  if (D <= 256) return (float)c256;
+  const double bound = bf ? (3.0 * D - 1.0) * u + 3.0 / 262144.0 : (D - 1.0) * u;
+  const double bound256 = bf ? (3.0 * 256 - 1.0) * u + 3.0 / 262144.0 : (256 - 1.0) * u;
+  return (float)(bound * (c256 / bound256));
+}
+
 // steps 1-2 and the seed of step 3.  info (device, int32[2]) <- {lowest core index or n if there is none, 0}
 // scan_tune "dbscan_bf16x3": 1 (default) = the pairwise-distance GEMM runs as bf16x3 (three bf16 MFMAs per product) with the
 // wider exact re-check band; 0 = exact fp32 MFMA.  Same neighbour bits either way (the band decides in fp64).
@@ -357,10 +369,13 @@ int g_scan_dbscan_bf16x3 = 1;
 
 extern "C" int scan_dbscan_prepare(const float* pts, int64_t n, int32_t D, float eps, int32_t min_samples, void* ws,
                                    int32_t* info, void* stream) {
-  SCAN_CHECK_ARG(pts && ws && info, "dbscan_prepare: null pointer");
+  SCAN_CHECK_ARG(pts, "dbscan_prepare: pts is a null pointer");
+  SCAN_CHECK_ARG(ws, "dbscan_prepare: ws is a null pointer");
+  SCAN_CHECK_ARG(info, "dbscan_prepare: info is a null pointer");
   SCAN_CHECK_ARG(n > 0 && n <= SCAN_DBSCAN_MAX, "dbscan_prepare: n=%lld out of range (SCAN_DBSCAN_MAX)", (long long)n);
   SCAN_CHECK_ARG(D > 0 && D % 4 == 0, "dbscan_prepare: D=%d must be a positive multiple of 4", D);
-  SCAN_CHECK_ARG(eps > 0.f && min_samples >= 1, "dbscan_prepare: eps / min_samples");
+  SCAN_CHECK_ARG(eps > 0.f, "dbscan_prepare: eps=%g must be positive", (double)eps);
+  SCAN_CHECK_ARG(min_samples >= 1, "dbscan_prepare: min_samples=%d must be at least 1", min_samples);
   hipStream_t st = as_stream(stream);
   DbWs w = db_split(ws, n);
   // everything after the bit matrix and the norms starts at zero; first_core starts at n
@@ -373,10 +388,10 @@ extern "C" int scan_dbscan_prepare(const float* pts, int64_t n, int32_t D, float
   const unsigned tiles = (unsigned)((n + DB_T - 1) / DB_T);
   if (g_scan_dbscan_bf16x3)
     hipLaunchKernelGGL(dbscan_neighbors_kernel<true>, dim3(tiles, tiles), dim3(256), 0, st, pts, n, D, w.sq,
-                       (double)eps * (double)eps, w.bits, w.nw);
+                       (double)eps * (double)eps, db_bandc(D, true), w.bits, w.nw);
   else
     hipLaunchKernelGGL(dbscan_neighbors_kernel<false>, dim3(tiles, tiles), dim3(256), 0, st, pts, n, D, w.sq,
-                       (double)eps * (double)eps, w.bits, w.nw);
+                       (double)eps * (double)eps, db_bandc(D, false), w.bits, w.nw);
   hipLaunchKernelGGL(dbscan_core_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, w.bits, n, w.nw, min_samples,
                      w.counts, w.core, w.first_core);
   hipLaunchKernelGGL(dbscan_seed_kernel, dim3(1), dim3(1), 0, st, w.first_core, n, w.visited, w.fa);
@@ -388,10 +403,25 @@ extern "C" int scan_dbscan_prepare(const float* pts, int64_t n, int32_t D, float
   return 0;
 }
 
+// read-only: counts [n] (device, int32) <- the neighbour counts (self included) of the last scan_dbscan_prepare on this workspace
+extern "C" int scan_dbscan_neighbor_counts(int64_t n, const void* ws, int32_t* counts, void* stream) {
+  SCAN_CHECK_ARG(ws, "dbscan_neighbor_counts: ws is a null pointer");
+  SCAN_CHECK_ARG(counts, "dbscan_neighbor_counts: counts is a null pointer");
+  SCAN_CHECK_ARG(n > 0 && n <= SCAN_DBSCAN_MAX, "dbscan_neighbor_counts: n=%lld out of range (SCAN_DBSCAN_MAX)", (long long)n);
+  DbWs w = db_split(const_cast<void*>(ws), n);
+  if (hipMemcpyAsync(counts, w.counts, (size_t)n * 4, hipMemcpyDeviceToDevice, as_stream(stream)) != hipSuccess) {
+    scan_set_error("dbscan_neighbor_counts: copy failed");
+    return -2;
+  }
+  return 0;
+}
+
 // one breadth-first level; parity = 0, 1, 0, ... selects which frontier buffer is read.  changed (device int32) is
 // cleared, then set to 1 if the level reached new core points: the caller loops while it reads 1.
 extern "C" int scan_dbscan_bfs_step(int64_t n, void* ws, int32_t parity, int32_t* changed, void* stream) {
-  SCAN_CHECK_ARG(ws && changed && n > 0 && n <= SCAN_DBSCAN_MAX, "dbscan_bfs_step: bad arguments");
+  SCAN_CHECK_ARG(ws, "dbscan_bfs_step: ws is a null pointer");
+  SCAN_CHECK_ARG(changed, "dbscan_bfs_step: changed is a null pointer");
+  SCAN_CHECK_ARG(n > 0 && n <= SCAN_DBSCAN_MAX, "dbscan_bfs_step: n=%lld out of range (SCAN_DBSCAN_MAX)", (long long)n);
   hipStream_t st = as_stream(stream);
   DbWs w = db_split(ws, n);
   uint32_t* cur = parity ? w.fb : w.fa;
@@ -408,7 +438,9 @@ extern "C" int scan_dbscan_bfs_step(int64_t n, void* ws, int32_t parity, int32_t
 
 // in_cluster0 [n] (uint8): 1 where sklearn's label would be 0
 extern "C" int scan_dbscan_finish(int64_t n, void* ws, uint8_t* in_cluster0, void* stream) {
-  SCAN_CHECK_ARG(ws && in_cluster0 && n > 0 && n <= SCAN_DBSCAN_MAX, "dbscan_finish: bad arguments");
+  SCAN_CHECK_ARG(ws, "dbscan_finish: ws is a null pointer");
+  SCAN_CHECK_ARG(in_cluster0, "dbscan_finish: in_cluster0 is a null pointer");
+  SCAN_CHECK_ARG(n > 0 && n <= SCAN_DBSCAN_MAX, "dbscan_finish: n=%lld out of range (SCAN_DBSCAN_MAX)", (long long)n);
   DbWs w = db_split(ws, n);
   hipLaunchKernelGGL(dbscan_finish_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, as_stream(stream), w.bits, n,
                      w.nw, w.core, w.visited, in_cluster0);

@@ -1616,7 +1616,10 @@ def dbscan_in_cluster0(pts, eps, min_samples=5):
     """bool [n]: True where sklearn.cluster.DBSCAN(eps, min_samples).fit_predict(pts) would return label 0 -- all the
     target-node sampling needs (reference rpn/fcos/loss.py:397-423: noise -> 1, cluster 0 -> 0, selected = non-zero).
     Neighbour search, core test, breadth-first growth of cluster 0 and border assignment run on the device
-    (scan_dbscan_*); the host only reads one flag per breadth-first level."""
+    (scan_dbscan_*); the host only reads one flag per breadth-first level.
+    eps is rounded to fp32 before it is squared (the C entry point takes a float): the threshold is fp32(eps)^2, where sklearn
+    -- and condgraph's "host" backend -- squares the Python double.  The two differ only for a pair whose distance lies between eps and
+    fp32(eps): within 6e-8 relative (half an fp32 ulp) of an eps that fp32 does not represent."""
     _chk(pts)
     n, d = pts.shape
     if n == 0:
