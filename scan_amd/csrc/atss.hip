@@ -526,35 +526,39 @@ static int giou_check(const scan_pyramid_t* d, const int32_t* strides, const flo
   return 0;
 }
 
-extern "C" int scan_atss_giou_forward(const scan_pyramid_t* d, const int32_t* strides, const float* anchor_sizes,
-                                      const float* pred, const float* target, const int64_t* rows, const float* weight,
-                                      int64_t P, float* out2, void* stream) {
-  SCAN_CHECK_ARG(P >= 0 && out2, "atss_giou_forward: bad arguments");
+extern "C" int64_t scan_atss_giou_ordered_ws_floats(int64_t P) { return 2 * (int64_t)giou_grid(P); }
+
+// ORD = false: float atomics on out2.  ORD = true: the blocks' sums go to ws [giou_grid(P)][2], giou_ordered_sum_kernel forms out2
+template <bool ORD>
+static int giou_forward_launch(const scan_pyramid_t* d, const int32_t* strides, const float* anchor_sizes, const float* pred,
+                               const float* target, const int64_t* rows, const float* weight, int64_t P, float* out2, float* ws,
+                               void* stream, const char* who) {
+  SCAN_CHECK_ARG(P >= 0 && out2, "%s: bad arguments", who);
   if (P == 0) return 0;
   AtssLevels lv;
-  if (giou_check(d, strides, anchor_sizes, pred, target, rows, weight, &lv, "atss_giou_forward")) return -1;
-  hipLaunchKernelGGL(giou_fwd_kernel<false>, dim3(giou_grid(P)), dim3(256), 0, as_stream(stream), *d, lv, pred, target, rows,
-                     weight, P, out2);
-  SCAN_LAUNCH_CHECK("atss_giou_fwd");
+  if (giou_check(d, strides, anchor_sizes, pred, target, rows, weight, &lv, who)) return -1;
+  const int grid = giou_grid(P);
+  hipLaunchKernelGGL(giou_fwd_kernel<ORD>, dim3(grid), dim3(256), 0, as_stream(stream), *d, lv, pred, target, rows, weight, P,
+                     ORD ? ws : out2);
+  SCAN_LAUNCH_CHECK(ORD ? "atss_giou_fwd_ordered" : "atss_giou_fwd");
+  if (ORD) {
+    hipLaunchKernelGGL(giou_ordered_sum_kernel, dim3(1), dim3(128), 0, as_stream(stream), ws, grid, out2);
+    SCAN_LAUNCH_CHECK("atss_giou_fwd_ordered_sum");
+  }
   return 0;
 }
 
-extern "C" int64_t scan_atss_giou_ordered_ws_floats(int64_t P) { return 2 * (int64_t)giou_grid(P); }
+extern "C" int scan_atss_giou_forward(const scan_pyramid_t* d, const int32_t* strides, const float* anchor_sizes,
+                                      const float* pred, const float* target, const int64_t* rows, const float* weight,
+                                      int64_t P, float* out2, void* stream) {
+  return giou_forward_launch<false>(d, strides, anchor_sizes, pred, target, rows, weight, P, out2, nullptr, stream, "atss_giou_forward");
+}
 
 extern "C" int scan_atss_giou_forward_ordered(const scan_pyramid_t* d, const int32_t* strides, const float* anchor_sizes,
                                               const float* pred, const float* target, const int64_t* rows,
                                               const float* weight, int64_t P, float* out2, float* ws, void* stream) {
-  SCAN_CHECK_ARG(P >= 0 && out2 && ws, "atss_giou_forward_ordered: bad arguments");
-  if (P == 0) return 0;
-  AtssLevels lv;
-  if (giou_check(d, strides, anchor_sizes, pred, target, rows, weight, &lv, "atss_giou_forward_ordered")) return -1;
-  const int grid = giou_grid(P);
-  hipLaunchKernelGGL(giou_fwd_kernel<true>, dim3(grid), dim3(256), 0, as_stream(stream), *d, lv, pred, target, rows, weight, P,
-                     ws);
-  SCAN_LAUNCH_CHECK("atss_giou_fwd_ordered");
-  hipLaunchKernelGGL(giou_ordered_sum_kernel, dim3(1), dim3(128), 0, as_stream(stream), ws, grid, out2);
-  SCAN_LAUNCH_CHECK("atss_giou_fwd_ordered_sum");
-  return 0;
+  SCAN_CHECK_ARG(ws, "atss_giou_forward_ordered: bad arguments");
+  return giou_forward_launch<true>(d, strides, anchor_sizes, pred, target, rows, weight, P, out2, ws, stream, "atss_giou_forward_ordered");
 }
 
 extern "C" int scan_atss_giou_backward(const scan_pyramid_t* d, const int32_t* strides, const float* anchor_sizes,

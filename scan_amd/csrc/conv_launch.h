@@ -23,7 +23,7 @@ extern int g_scan_wgrad_v6, g_scan_wgrad_prio, g_scan_wgrad_tile, g_scan_wgrad_w
 extern int g_scan_gconv_mfma;                                                           // gconv.hip
 extern int g_scan_dynconv_generic;                                                      // dynconv.hip
 extern int g_scan_dbscan_bf16x3;                                                        // dbscan.hip
-extern int g_scan_reduce_blocks;                                                        // pointwise.hip
+extern int g_scan_reduce_blocks;                                                        // losses.hip
 
 // one forward / data-gradient launch, validated
 struct ConvArgs {

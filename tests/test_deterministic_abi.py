@@ -73,6 +73,19 @@ def test_ordered_workspace_sizes_cover_the_launch_grids():
     assert L.scan_cka_bce_ordered_ws_floats(40000, 3) == 6 * 20
     assert L.scan_softmax_focal_ordered_ws_floats(40000) == 79  # 512 rows per workgroup iteration
     assert L.scan_softmax_focal_ordered_ws_floats(1) == 1
+    # the queries follow the knob: the cap itself, half of it for the "light" kernels, each clamped to one workgroup
+    for cap, focal, iou, bce, cka8, cka3 in ((2, 2, 2 * 1, 2 * 2, 16 * 2, 6 * 2), (0, 1, 2 * 1, 2 * 1, 16 * 1, 6 * 1)):
+        old = L.scan_tune(b"reduce_blocks", cap)
+        try:
+            assert L.scan_sigmoid_focal_loss_ordered_ws_floats(1 << 24, 8) == focal
+            assert L.scan_iou_loss_ordered_ws_floats(1 << 24) == iou
+            assert L.scan_bce_logits_ordered_ws_floats(320000) == bce
+            assert L.scan_cka_bce_ordered_ws_floats(40000, 8) == cka8  # the larger of the generic and the light float4 grid
+            assert L.scan_cka_bce_ordered_ws_floats(40000, 3) == cka3
+            assert L.scan_softmax_focal_ordered_ws_floats(40000) == 79  # the knob does not reach this kernel's grid
+        finally:
+            L.scan_tune(b"reduce_blocks", old)
+    assert L.scan_tune_get(b"reduce_blocks") == 2048
     d = _lib.PyramidDesc()
     d.n_levels, d.n_images = 2, 2
     d.h[0], d.w[0], d.h[1], d.w[1] = 64, 96, 7, 5

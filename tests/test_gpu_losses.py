@@ -1,4 +1,4 @@
-"""GPU tests of the five loss families of scan_amd/csrc/pointwise.hip -- sigmoid focal, IoU, BCE-with-logits, CKA class-weighted
+"""GPU tests of the five loss families of scan_amd/csrc/losses.hip -- sigmoid focal, IoU, BCE-with-logits, CKA class-weighted
 BCE, softmax focal -- on every dispatch path and numeric edge, each against a float64 torch-CPU computation of the reference's
 formula: the value AND every gradient element, with the atomic and the ordered (scan_tune "deterministic") reductions.
 
