@@ -910,6 +910,26 @@ int scan_deform_sample_backward(const float* x, const scan_pyramid_t* d, int32_t
 int scan_deform_dx_gather(const float* dcols, const int64_t* perm, const int64_t* seg_start, const float* wgts, int64_t M, int32_t C,
                           int32_t Cs, float* dx, void* stream);
 
+/* ---- centre-aware alignment of the EPM baseline (discriminator/fcos_head_discriminator_CA.py:56-124) ----
+ * :61-69 for every row of a pyramid in one launch:
+ *   atten[m] = sigmoid(weight * sigmoid(max_{c < C} cls[m * Cs + c]) * sigmoid(ctr[m * ctr_stride]))
+ * (sigmoid increases, so the maximum of the class probabilities is the probability of the largest logit).  cls: rows of pitch
+ * Cs >= C of which only the first C columns are read -- the padding columns of the conv that wrote them may hold anything.
+ * sigmoid(x) = 1 / (1 + expf(-x)) with IEEE division; no reduction across rows: the same bits on every run. */
+int scan_center_aware_map(const float* cls, int32_t Cs, int32_t C, const float* ctr, int64_t ctr_stride, float weight, int64_t M,
+                          float* atten, void* stream);
+/* :93 (atten_map * feature in front of the gradient-reversal layer) and layer.py:6-24 (its backward) for all levels of a pyramid
+ * in one launch:  y[m][c] = fl(fl(s[l(m)] * a[m]) * x[m][c]) for c < C, l(m) = the level of row m; a == NULL: the factor is
+ * s[l(m)] itself (one rounding in all).  s: HOST array of d->n_levels floats.  The forward runs with s = 1 (fl(1 * a) = a: the
+ * product a * x rounded once), the backward with s[l] = -lambda_l on the gradient rows.  x, y: row pitches ldx, ldy >= C in
+ * floats; C, ldx, ldy multiples of 4, x and y 16-byte aligned; columns >= C of y are left untouched. */
+int scan_row_scale_levels(const float* x, int32_t ldx, const float* a, const float* s, const scan_pyramid_t* d, int32_t C, float* y,
+                          int32_t ldy, void* stream);
+/* the same with x given level by level: x_levels is a HOST array of d->n_levels device pointers to each level's first row (the
+ * gradient tensors of a per-level split are separate allocations); a NULL level writes zeros into that level's rows of y. */
+int scan_row_scale_levels_ptrs(const float* const* x_levels, int32_t ldx, const float* a, const float* s, const scan_pyramid_t* d,
+                               int32_t C, float* y, int32_t ldy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -257,6 +257,10 @@ SIGNATURES = {
     "scan_deform_sample_backward": (ctypes.c_int, [c_vp, _PD, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp,
                                                    c_i32, c_vp, c_vp, c_vp]),
     "scan_deform_dx_gather": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp]),
+    "scan_center_aware_map": (ctypes.c_int, [c_vp, c_i32, c_i32, c_vp, c_i64, c_f32, c_i64, c_vp, c_vp]),
+    "scan_row_scale_levels": (ctypes.c_int, [c_vp, c_i32, c_vp, ctypes.POINTER(c_f32), _PD, c_i32, c_vp, c_i32, c_vp]),
+    "scan_row_scale_levels_ptrs": (ctypes.c_int, [ctypes.POINTER(c_vp), c_i32, c_vp, ctypes.POINTER(c_f32), _PD, c_i32, c_vp, c_i32,
+                                                  c_vp]),
 }
 
 _lib = None

@@ -83,6 +83,20 @@ ATSS_DEFAULTS = {
 }
 
 
+# The global-alignment (GA) and centre-aware (CA) discriminators of the EPM baseline (the reference's configs/epm/*.yaml) with the
+# reference's defaults (defaults.py:356-411).  Kept OUT of DEFAULTS for the same reason as ATSS_DEFAULTS; epm_settings(cfg) reads a
+# cfg's MODEL.ADV block over these.
+EPM_ADV_DEFAULTS = {
+    "USE_DIS_GLOBAL": False, "USE_DIS_CENTER_AWARE": False, "CENTER_AWARE_WEIGHT": 20, "CENTER_AWARE_TYPE": "ca_feature",
+    "GA_DIS_LAMBDA": 0.01, "CA_DIS_LAMBDA": 0.1, "USE_DIS_OUT": False,
+    **{"USE_DIS_%s" % l: False for l in ("P3", "P4", "P5", "P6", "P7")},
+    **{"DIS_%s_NUM_CONVS" % l: 4 for l in ("P3", "P4", "P5", "P6", "P7")},
+    **{"CA_DIS_%s_NUM_CONVS" % l: 4 for l in ("P3", "P4", "P5", "P6", "P7")},
+    **{"GRL_WEIGHT_%s" % l: 0.1 for l in ("P3", "P4", "P5", "P6", "P7")},
+    **{"CA_GRL_WEIGHT_%s" % l: 0.1 for l in ("P3", "P4", "P5", "P6", "P7")},
+}
+
+
 class Cfg(dict):
     """Nested dict with attribute access (what the path needs of yacs.config.CfgNode)."""
 
@@ -291,3 +305,66 @@ def atss_settings(cfg):
         topk=int(A.TOPK), reg_loss_weight=float(A.REG_LOSS_WEIGHT), prior_prob=float(A.PRIOR_PROB),
         inference_th=float(A.INFERENCE_TH), pre_nms_top_n=int(A.PRE_NMS_TOP_N), nms_th=float(A.NMS_TH),
         detections_per_img=int(cfg.TEST.DETECTIONS_PER_IMG))
+
+
+def epm_settings(cfg):
+    """Flat view for epm.build_model / epm.EPMTrainer: the EPM baseline of the reference's configs/epm/*.yaml -- the plain FCOS
+    head (MODEL.FCOS) or the ATSS head (MODEL.ATSS_ON, atss_settings) without a middle head, one GA discriminator per switched-on
+    level, optionally a CA one beside it.  Raises, naming the key, on everything that is not built."""
+    M, H, F = cfg.MODEL, cfg.MODEL.MIDDLE_HEAD, cfg.MODEL.FCOS
+    A = Cfg(EPM_ADV_DEFAULTS)
+    A._merge(M.ADV)
+    if H.CONDGRAPH_ON:
+        raise ValueError("MODEL.MIDDLE_HEAD.CONDGRAPH_ON True: the EPM step runs without a middle head (config.settings builds "
+                         "the SCAN step); GA / CA discriminators beside the middle head are not built")
+    if A.USE_DIS_CON:
+        raise ValueError("MODEL.ADV.USE_DIS_CON True: GA / CA discriminators beside the CKA ones are not built")
+    if A.USE_DIS_OUT:
+        raise ValueError("MODEL.ADV.USE_DIS_OUT True is not built (only USE_DIS_GLOBAL and USE_DIS_CENTER_AWARE)")
+    if not (A.USE_DIS_GLOBAL or A.USE_DIS_CENTER_AWARE):
+        raise ValueError("MODEL.ADV.USE_DIS_GLOBAL and USE_DIS_CENTER_AWARE are both False: no discriminator to train against")
+    if A.GRL_APPLIED_DOMAIN != "both":
+        raise ValueError("MODEL.ADV.GRL_APPLIED_DOMAIN %r is not built (only 'both')" % (A.GRL_APPLIED_DOMAIN,))
+    if A.PATCH_STRIDE is not None:
+        raise ValueError("MODEL.ADV.PATCH_STRIDE %r is not built (only None)" % (A.PATCH_STRIDE,))
+    if A.CENTER_AWARE_TYPE not in ("ca_feature", "ca_loss"):
+        raise ValueError("MODEL.ADV.CENTER_AWARE_TYPE %r is not built ('ca_feature' or 'ca_loss')" % (A.CENTER_AWARE_TYPE,))
+    if not any(A["USE_DIS_%s" % l] for l in LEVELS):
+        raise ValueError("MODEL.ADV.USE_DIS_P3..P7 are all False: no level to align")
+    for l in LEVELS:
+        for key in ("DIS_%s_NUM_CONVS" % l, "CA_DIS_%s_NUM_CONVS" % l):
+            if int(A[key]) < 0:
+                raise ValueError("MODEL.ADV.%s %r: a tower has 0 or more convs" % (key, A[key]))
+    if M.RETINANET.USE_C5:
+        raise ValueError("MODEL.RETINANET.USE_C5 True is not built (the pyramid's P6 reads P5)")
+    if str(cfg.TEST.MODE) != "common":
+        raise ValueError("TEST.MODE %r: without a middle head there are no act maps to score with (only 'common')" % (cfg.TEST.MODE,))
+    if M.get("ATSS_ON", False):
+        rpn, head = "atss", atss_settings(cfg)
+    elif M.get("FCOS_ON", False):
+        if int(F.NUM_CONVS_CLS) != int(F.NUM_CONVS_REG):
+            raise ValueError("MODEL.FCOS.NUM_CONVS_CLS != NUM_CONVS_REG is not built")
+        if not 2 <= int(F.NUM_CLASSES) <= 32:
+            raise ValueError("MODEL.FCOS.NUM_CLASSES %r (background included): 2..32 are built" % (F.NUM_CLASSES,))
+        rpn = "fcos"
+        head = dict(
+            num_classes=int(F.NUM_CLASSES), test_mode="common", reg_ctr_on=bool(F.REG_CTR_ON), num_convs_cls=int(F.NUM_CONVS_CLS),
+            num_convs_reg=int(F.NUM_CONVS_REG), prior_prob=float(F.PRIOR_PROB), loss_gamma=float(F.LOSS_GAMMA),
+            loss_alpha=float(F.LOSS_ALPHA), fpn_strides=tuple(F.FPN_STRIDES), inference_th=float(F.INFERENCE_TH),
+            pre_nms_top_n=int(F.PRE_NMS_TOP_N), nms_th=float(F.NMS_TH), detections_per_img=int(cfg.TEST.DETECTIONS_PER_IMG))
+    else:
+        raise ValueError("MODEL.ATSS_ON and MODEL.FCOS_ON are False: only those two heads are built")
+    return dict(
+        rpn=rpn, head=head, num_classes=head["num_classes"], conv_body=str(M.BACKBONE.CONV_BODY),
+        use_dis_global=bool(A.USE_DIS_GLOBAL), use_dis_center_aware=bool(A.USE_DIS_CENTER_AWARE),
+        center_aware_weight=float(A.CENTER_AWARE_WEIGHT), center_aware_type=str(A.CENTER_AWARE_TYPE),
+        ga_dis_lambda=float(A.GA_DIS_LAMBDA), ca_dis_lambda=float(A.CA_DIS_LAMBDA),
+        use_dis={l: bool(A["USE_DIS_%s" % l]) for l in LEVELS},
+        dis_num_convs={l: int(A["DIS_%s_NUM_CONVS" % l]) for l in LEVELS},
+        ca_dis_num_convs={l: int(A["CA_DIS_%s_NUM_CONVS" % l]) for l in LEVELS},
+        grl_weight={l: float(A["GRL_WEIGHT_%s" % l]) for l in LEVELS},
+        ca_grl_weight={l: float(A["CA_GRL_WEIGHT_%s" % l]) for l in LEVELS},
+        size_divisibility=int(cfg.DATALOADER.SIZE_DIVISIBILITY), ims_per_batch=int(cfg.SOLVER.IMS_PER_BATCH),
+        max_iter=int(cfg.SOLVER.MAX_ITER), test_ims_per_batch=int(cfg.TEST.IMS_PER_BATCH),
+        solver={k: solver_group(cfg, k) for k in ("backbone", "fcos", "dis")},
+    )

@@ -11,6 +11,10 @@ classes read the same x, so the 8 first convs are ONE implicit GEMM with 8*128 o
 over cat(x, act[1:]) (the per-class act channel enters through a block-diagonal weight
 slice), and the 8 second convs are ONE skinny conv 1024 -> 8 with a block-diagonal weight.
 The class-weighted BCE of all classes is one wavefront-reduction kernel.
+
+Beside it the two discriminators of the EPM baseline (the reference's configs/epm/*.yaml): FCOSDiscriminator (global
+alignment, fcos_head_discriminator.py:11-74) and FCOSDiscriminator_CA (centre-aware, fcos_head_discriminator_CA.py:7-124),
+on the same towers; the centre-aware map and its row scaling are csrc/center_aware.hip.
 """
 import torch
 from torch import nn
@@ -19,6 +23,106 @@ from .. import ops
 from ..layers import GradientReversal
 from .backbone import conv_holder
 from .fcos import make_tower, run_tower
+
+
+def _check_epm_keywords(name, grl_applied_domain, patch_stride=None, center_aware_type=None):
+    """the EPM discriminators are built for the setting of the reference's configs/epm/*.yaml; anything else names its key"""
+    if grl_applied_domain != "both":
+        raise ValueError("%s: grl_applied_domain %r is not built (MODEL.ADV.GRL_APPLIED_DOMAIN: only 'both')"
+                         % (name, grl_applied_domain))
+    if patch_stride is not None:
+        raise ValueError("%s: patch_stride %r is not built (MODEL.ADV.PATCH_STRIDE: only None)" % (name, patch_stride))
+    if center_aware_type is not None and center_aware_type not in ("ca_feature", "ca_loss"):
+        raise ValueError("%s: center_aware_type %r is not built (MODEL.ADV.CENTER_AWARE_TYPE: 'ca_feature' or 'ca_loss')"
+                         % (name, center_aware_type))
+
+
+class FCOSDiscriminator(nn.Module):
+    """Global-alignment (GA) discriminator of the EPM baseline on one pyramid level (reference discriminator/
+    fcos_head_discriminator.py:11-74): GRL -> num_convs x [conv3x3, GroupNorm(32), ReLU] -> conv3x3 256 -> 1 -> mean BCE against
+    the domain label.  Parameter names are the reference's (dis_tower.{0,1,3,4,...}, cls_logits)."""
+
+    def __init__(self, num_convs=2, in_channels=256, grad_reverse_lambda=-1.0, grl_applied_domain="both", patch_stride=None):
+        super().__init__()
+        _check_epm_keywords(type(self).__name__, grl_applied_domain, patch_stride)
+        if num_convs < 0 or in_channels != 256:
+            raise ValueError("%s: num_convs %r >= 0 on 256 input channels is what is built (in_channels %r)"
+                             % (type(self).__name__, num_convs, in_channels))
+        self.num_convs = num_convs
+        self.in_channels = in_channels
+        self.dis_tower = make_tower(num_convs, in_channels)
+        self.cls_logits = conv_holder(in_channels, 1, 3)
+        for modules in (self.dis_tower, self.cls_logits):  # reference :44-48
+            for m in modules.modules():
+                if isinstance(m, nn.Conv2d):
+                    nn.init.normal_(m.weight, std=0.01)
+                    nn.init.constant_(m.bias, 0)
+        self.grad_reverse = GradientReversal(grad_reverse_lambda)
+        self.grl_applied_domain = grl_applied_domain
+
+    def _logits(self, feature, shape):
+        """[M_l] domain logits; the 256 -> 1 conv is the skinny dense conv the FCOS head's centerness uses"""
+        x = run_tower(self.dis_tower, feature, shape, self.num_convs)
+        return ops.conv2d(x, self.cls_logits.weight, self.cls_logits.bias, shape, 3, 1)[:, 0]
+
+    def forward(self, feature, target, domain="source", shape=None):
+        """feature [M_l, 256] rows of ONE level; shape = that level's PyramidShape."""
+        assert target in (0, 1, 0.1, 0.9) and domain in ("source", "target")
+        return ops.bce_with_logits_const_mean(self._logits(self.grad_reverse(feature), shape), target)
+
+    def forward_pair(self, feature, shape, n_src, grl_applied=False):
+        """source frames [0, n_src) and target frames [n_src, N) of one level in ONE pass through the tower; the source loss
+        (label 1.0) is taken on the first n_src images' rows, the target loss (label 0.0) on the rest.  Same values and gradients
+        as forward(.., 1.0, 'source') + forward(.., 0.0, 'target') (reference trainer.py:316-318, 359-362).  grl_applied: the
+        caller already put the feature behind this module's GRL (ops.split_levels_grl)."""
+        if not grl_applied:
+            feature = self.grad_reverse(feature)
+        (h, w) = shape.sizes[0]
+        ls, lt = ops.split_rows2(self._logits(feature, shape), n_src * h * w)
+        return ops.bce_with_logits_const_mean(ls, 1.0), ops.bce_with_logits_const_mean(lt, 0.0)
+
+
+class FCOSDiscriminator_CA(FCOSDiscriminator):
+    """Centre-aware (CA) discriminator of the EPM baseline on one level (reference discriminator/
+    fcos_head_discriminator_CA.py:7-124).  The map atten = sigmoid(w * max_c sigmoid(cls) * sigmoid(ctr)) of the head's detached
+    outputs multiplies the feature in front of the GRL ('ca_feature') or weights the per-location BCE ('ca_loss')."""
+
+    def __init__(self, num_convs=2, in_channels=256, grad_reverse_lambda=-1.0, center_aware_weight=0.0,
+                 center_aware_type="ca_loss", grl_applied_domain="both"):
+        _check_epm_keywords(type(self).__name__, grl_applied_domain, None, center_aware_type)
+        super().__init__(num_convs, in_channels, grad_reverse_lambda, grl_applied_domain)
+        self.center_aware_weight = center_aware_weight
+        self.center_aware_type = center_aware_type
+
+    def atten_map(self, score_map):
+        """score_map {"box_cls": [M_l, C] rows, "centerness": [M_l] or [M_l, 1]} of this level -> atten [M_l], no gradient"""
+        cls = score_map["box_cls"]
+        return ops.center_aware_map(cls, score_map["centerness"], cls.shape[1], self.center_aware_weight)
+
+    def _input(self, feature, atten, shape):
+        """the feature behind this module's GRL: attention-scaled for 'ca_feature' (reference :93), as it is for 'ca_loss'"""
+        if self.center_aware_type == "ca_feature":
+            return ops.center_aware_split_levels_grl(feature, atten, shape, [self.grad_reverse.lambda_])[0]
+        return self.grad_reverse(feature)
+
+    def _loss(self, logits, atten, target):
+        return ops.bce_with_logits_const_mean(logits, target, atten if self.center_aware_type == "ca_loss" else None)
+
+    def forward(self, feature, target, score_map=None, domain="source", shape=None):
+        assert target in (0, 1, 0.1, 0.9) and domain in ("source", "target")
+        atten = self.atten_map(score_map)
+        return self._loss(self._logits(self._input(feature, atten, shape), shape), atten, target)
+
+    def forward_pair(self, feature, atten, shape, n_src, grl_applied=False):
+        """FCOSDiscriminator.forward_pair with this level's map atten [M_l] (ops.center_aware_map, or atten_map).  grl_applied:
+        the caller already formed this module's input (ops.center_aware_split_levels_grl with the map for 'ca_feature',
+        without it for 'ca_loss')."""
+        if not grl_applied:
+            feature = self._input(feature, atten, shape)
+        (h, w) = shape.sizes[0]
+        m = n_src * h * w
+        ls, lt = ops.split_rows2(self._logits(feature, shape), m)
+        return self._loss(ls, atten[:m], 1.0), self._loss(lt, atten[m:], 0.0)
 
 
 class FCOSDiscriminator_con(nn.Module):

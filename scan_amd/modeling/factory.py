@@ -22,7 +22,7 @@ import torch
 
 from .. import config, ops
 from ..structures import BoxList, to_image_list
-from . import fcos as fcos_mod
+from . import discriminator, fcos as fcos_mod
 from .atss import ATSSModule
 from .backbone import VGG16FPN
 from .condgraph import GRAPHModule
@@ -185,6 +185,9 @@ def build_rpn(cfg, in_channels):
         return _channels_last_(ATSSModuleNCHW(cfg=config.atss_settings(cfg)))
     if not cfg.MODEL.get("FCOS_ON", False):
         raise ValueError("MODEL.ATSS_ON and MODEL.FCOS_ON are False: only those two heads are built (no RPN / RetinaNet)")
+    if not cfg.MODEL.MIDDLE_HEAD.CONDGRAPH_ON:  # the EPM baseline: the plain head, centerness where MODEL.FCOS.REG_CTR_ON puts it
+        h = config.epm_settings(cfg)["head"]
+        return _channels_last_(FCOSModuleNCHW(h["num_classes"], h["test_mode"], h))
     s = config.settings(cfg)
     return _channels_last_(FCOSModuleNCHW(s["num_classes"], s["test_mode"], s))
 
@@ -206,6 +209,34 @@ class FCOSDiscriminatorNCHW(FCOSDiscriminator_con):
 FCOSDiscriminator_con = FCOSDiscriminatorNCHW
 
 
+class FCOSDiscriminatorGANCHW(discriminator.FCOSDiscriminator):
+    """FCOSDiscriminator.forward of the reference (discriminator/fcos_head_discriminator.py:57-74) on ONE level."""
+
+    def forward(self, feature, target, domain="source", shape=None):
+        """feature [N, 256, h, w] (or, with ``shape``, the engine's rows of one level)"""
+        if shape is not None:
+            return super().forward(feature, target, domain=domain, shape=shape)
+        frows, shape = _level_rows(feature)
+        return super().forward(frows, target, domain=domain, shape=shape)
+
+
+class FCOSDiscriminatorCANCHW(discriminator.FCOSDiscriminator_CA):
+    """FCOSDiscriminator_CA.forward of the reference (discriminator/fcos_head_discriminator_CA.py:56-124) on ONE level."""
+
+    def forward(self, feature, target, score_map=None, domain="source", shape=None):
+        """feature [N, 256, h, w], score_map {"box_cls": [N, C, h, w], "centerness": [N, 1, h, w]} of that level"""
+        if shape is not None:
+            return super().forward(feature, target, score_map, domain=domain, shape=shape)
+        frows, shape = _level_rows(feature)
+        maps = {"box_cls": _level_rows(score_map["box_cls"])[0], "centerness": _level_rows(score_map["centerness"])[0]}
+        return super().forward(frows, target, maps, domain=domain, shape=shape)
+
+
+# the names a reference script constructs the EPM discriminators by (tools/train_net_da.py:100-220): same keyword arguments
+FCOSDiscriminator = FCOSDiscriminatorGANCHW
+FCOSDiscriminator_CA = FCOSDiscriminatorCANCHW
+
+
 def _level_rows(t):
     """one [N, C, h, w] level -> ([N*h*w, C] rows, its PyramidShape): a view when the level is dense channels_last"""
     n, c, h, w = t.shape
@@ -217,10 +248,29 @@ def _level_rows(t):
 
 def build_discriminators(cfg):
     """{"dis_P7_CON": ..., ..., "dis_P3_CON": ...} for the levels MODEL.ADV.USE_DIS_<level>_CON switches on, with the level's
-    CON_NUM_SHARED_CONV_<level> tower convs and GRL_WEIGHT_<level> (reference tools/train_net_da.py:223-274)."""
+    CON_NUM_SHARED_CONV_<level> tower convs and GRL_WEIGHT_<level> (reference tools/train_net_da.py:223-274).  Without
+    USE_DIS_CON: the EPM baseline's {"dis_P7": ..., "dis_P3": ..., "dis_P7_CA": ..., "dis_P3_CA": ...} for the levels
+    MODEL.ADV.USE_DIS_<level> switches on -- the GA discriminators when USE_DIS_GLOBAL, then the CA ones when
+    USE_DIS_CENTER_AWARE (:69-131); nothing when neither is set."""
     A = cfg.MODEL.ADV
     if not A.USE_DIS_CON:
-        return {}
+        if not (A.get("USE_DIS_GLOBAL", False) or A.get("USE_DIS_CENTER_AWARE", False)):
+            return {}
+        s = config.epm_settings(cfg)
+        out = {}
+        used = [lvl for lvl in DIS_ORDER if s["use_dis"][lvl]]
+        if s["use_dis_global"]:
+            for lvl in used:
+                out["dis_%s" % lvl] = _channels_last_(FCOSDiscriminatorGANCHW(
+                    patch_stride=A.PATCH_STRIDE, num_convs=s["dis_num_convs"][lvl], grad_reverse_lambda=s["grl_weight"][lvl],
+                    grl_applied_domain=str(A.GRL_APPLIED_DOMAIN)))
+        if s["use_dis_center_aware"]:
+            for lvl in used:
+                out["dis_%s_CA" % lvl] = _channels_last_(FCOSDiscriminatorCANCHW(
+                    num_convs=s["ca_dis_num_convs"][lvl], grad_reverse_lambda=s["ca_grl_weight"][lvl],
+                    center_aware_weight=s["center_aware_weight"], center_aware_type=s["center_aware_type"],
+                    grl_applied_domain=str(A.GRL_APPLIED_DOMAIN)))
+        return out
     s = config.settings(cfg)
     out = {}
     for lvl in DIS_ORDER:
@@ -233,10 +283,13 @@ def build_discriminators(cfg):
 
 
 def build_model(cfg, device="cuda"):
-    """the reference's MODEL dict (tools/train_net_da.py:43-48,223-274) out of the factories above, moved to ``device``"""
+    """the reference's MODEL dict (tools/train_net_da.py:43-48,223-274) out of the factories above, moved to ``device``; without
+    MODEL.MIDDLE_HEAD.CONDGRAPH_ON there is no "middle_head" entry (:43-48)"""
     backbone = build_backbone(cfg)
-    model = {"backbone": backbone, "middle_head": build_middle_head(cfg, backbone.out_channels),
-             "fcos": build_rpn(cfg, backbone.out_channels)}
+    model = {"backbone": backbone}
+    if cfg.MODEL.MIDDLE_HEAD.CONDGRAPH_ON:
+        model["middle_head"] = build_middle_head(cfg, backbone.out_channels)
+    model["fcos"] = build_rpn(cfg, backbone.out_channels)
     model.update(build_discriminators(cfg))
     for m in model.values():
         m.to(device)

@@ -272,8 +272,11 @@ class FCOSHead(nn.Module):
     """reference fcos.py:13-114 with REG_CTR_ON True."""
     exp_reg = True  # bbox_reg = exp(scale * bbox_pred); the ATSS head (modeling/atss.py) regresses plain deltas
 
-    def __init__(self, num_classes=9, num_convs=4, prior_prob=0.01, use_dcn_in_tower=False):
+    def __init__(self, num_classes=9, num_convs=4, prior_prob=0.01, use_dcn_in_tower=False, reg_ctr_on=True):
+        """reg_ctr_on False (the reference's default, what its configs/epm/*.yaml run with): the centerness conv reads the
+        class tower (fcos.py:107-111)"""
         super().__init__()
+        self.reg_ctr_on = bool(reg_ctr_on)
         self.num_fg = num_classes - 1
         self.num_convs = num_convs
         self.cls_tower = make_tower(num_convs, dcn_last=use_dcn_in_tower)
@@ -290,6 +293,8 @@ class FCOSHead(nn.Module):
 
     def forward(self, rows, shape, need_cls=True):
         """-> logits [M,C] (or None), bbox_reg [M,4] = exp(scale_l * bbox_pred), centerness [M]."""
+        if not self.reg_ctr_on:
+            return self._forward_cls_ctr(rows, shape)
         logits = None
         if need_cls:
             ct = run_tower(self.cls_tower, rows, shape, self.num_convs)
@@ -303,6 +308,19 @@ class FCOSHead(nn.Module):
                                 for l in range(shape.n_levels)], 0)
         bbox_reg = out[:, :4] * scale_rows[:, None]
         return logits, torch.exp(bbox_reg) if self.exp_reg else bbox_reg, out[:, 4]
+
+    def _forward_cls_ctr(self, rows, shape):
+        """REG_CTR_ON False: cls_logits (C) and centerness (1) read the class tower -- one skinny conv with C + 1 outputs --
+        and bbox_pred alone reads the box tower"""
+        ct = run_tower(self.cls_tower, rows, shape, self.num_convs)
+        w = torch.cat([self.cls_logits.weight, self.centerness.weight], 0)
+        b = torch.cat([self.cls_logits.bias, self.centerness.bias], 0)
+        out = ops.conv2d(ct, w, b, shape, 3, 1)
+        rt = run_tower(self.bbox_tower, rows, shape, self.num_convs)
+        scale_rows = torch.cat([self.scales[l].scale.expand(shape.row_off[l + 1] - shape.row_off[l])
+                                for l in range(shape.n_levels)], 0)
+        bbox_reg = ops.conv2d(rt, self.bbox_pred.weight, self.bbox_pred.bias, shape, 3, 1)[:, :4] * scale_rows[:, None]
+        return out[:, :self.num_fg], torch.exp(bbox_reg) if self.exp_reg else bbox_reg, out[:, self.num_fg]
 
 
 class FCOSLossComputation:
@@ -522,7 +540,7 @@ class FCOSModule(nn.Module):
         if c.get("num_convs_cls", 4) != c.get("num_convs_reg", 4):
             raise ValueError("MODEL.FCOS.NUM_CONVS_CLS != NUM_CONVS_REG is not built")
         self.head = FCOSHead(num_classes, c.get("num_convs_cls", 4), c.get("prior_prob", 0.01),
-                             use_dcn_in_tower=bool(c.get("dcn_in_tower", False)))
+                             use_dcn_in_tower=bool(c.get("dcn_in_tower", False)), reg_ctr_on=bool(c.get("reg_ctr_on", True)))
         self.loss_evaluator = FCOSLossComputation(c.get("loss_gamma", 2.0), c.get("loss_alpha", 0.25))
         # reference rpn/fcos/inference.py:197-217 make_fcos_postprocessor
         self.box_selector_test = FCOSPostProcessor(

@@ -771,6 +771,78 @@ def split_levels_grl(rows, shape, lams):
     return _SplitLevelsGRL.apply(rows, shape, lams)
 
 
+# ----------------------------------------------------------------------------- centre-aware alignment (EPM baseline)
+def center_aware_map(cls_rows, ctr, C, weight):
+    """atten [M] = sigmoid(weight * max_c sigmoid(cls_rows[m, c]) * sigmoid(ctr[m])) (reference discriminator/
+    fcos_head_discriminator_CA.py:61-69) for the whole pyramid in one launch.  cls_rows: the head's class-logit rows, [M, >= C]
+    with unit column stride -- the column slice the head returns is taken as it is, its row pitch is the conv's padded width and
+    only the first C columns are read; ctr: [M] with any stride (a column of the head's bbox / centerness conv).  No gradient:
+    the reference detaches the score maps (engine/trainer.py:320-322)."""
+    cls_rows, ctr = cls_rows.detach(), ctr.detach()
+    if not (cls_rows.is_cuda and ctr.is_cuda):
+        raise RuntimeError("scan_amd ops run only on the GPU (HIP) -- got %s / %s tensors; no CPU fallback" % (cls_rows.device, ctr.device))
+    if cls_rows.dtype != torch.float32 or ctr.dtype != torch.float32 or cls_rows.dim() != 2:
+        raise RuntimeError("center_aware_map: fp32 [M, Cs] class rows and fp32 [M] centerness")
+    M = cls_rows.shape[0]
+    if ctr.dim() == 2 and ctr.shape[1] == 1:
+        ctr = ctr[:, 0]
+    if not 1 <= C <= cls_rows.shape[1] or ctr.dim() != 1 or ctr.shape[0] != M:
+        raise RuntimeError("center_aware_map: C=%d of %d columns, %s centerness for %d rows" % (C, cls_rows.shape[1], tuple(ctr.shape), M))
+    if M > 1 and (cls_rows.stride(1) != 1 or cls_rows.stride(0) < cls_rows.shape[1]):
+        cls_rows = cls_rows.contiguous()
+    cs = cls_rows.stride(0) if M > 1 else max(cls_rows.shape[1], 1)
+    atten = torch.empty((M,), dtype=torch.float32, device=cls_rows.device)
+    call("scan_center_aware_map", _ptr(cls_rows), cs, C, _ptr(ctr), max(ctr.stride(0), 1), float(weight), M, _ptr(atten), _stream())
+    return atten
+
+
+def _row_scale_levels(x_levels, ldx, atten, scales, shape, C, out):
+    """out[m, :C] = (scales[l(m)] * atten[m]) * x[m, :C]; x_levels: one matrix, or one tensor (or None: zeros) per level"""
+    s = (ctypes.c_float * shape.n_levels)(*scales)
+    if isinstance(x_levels, torch.Tensor):
+        call("scan_row_scale_levels", _ptr(x_levels), ldx, _ptr(atten), s, shape.ref(), C, _ptr(out), out.stride(0), _stream())
+    else:
+        ptrs = (ctypes.c_void_p * shape.n_levels)(*[t.data_ptr() if t is not None else None for t in x_levels])
+        call("scan_row_scale_levels_ptrs", ptrs, ldx, _ptr(atten), s, shape.ref(), C, _ptr(out), out.stride(0), _stream())
+    return out
+
+
+class _CenterAwareSplitLevelsGRL(torch.autograd.Function):
+    """rows [M, C] -> the five level views of atten[:, None] * rows, each behind a gradient-reversal layer of its own strength
+    (reference fcos_head_discriminator_CA.py:93: grad_reverse(atten_map * feature)).  One launch forward; the backward scales the
+    five level gradients by -lambda_l * atten[m] straight into their row ranges of one [M, C] matrix, in one launch too.
+    atten = None: split_levels_grl's values (the 'ca_loss' form keeps the feature as it is) with that one-launch backward."""
+
+    @staticmethod
+    def forward(ctx, rows, atten, shape, lams):
+        _chk(rows, atten)
+        M, C = rows.shape
+        if M != shape.rows or C % 4 or (atten is not None and atten.shape != (M,)):
+            raise RuntimeError("center_aware_split_levels_grl: rows %s, atten %s for %d pyramid rows (columns: a multiple of 4)"
+                               % (tuple(rows.shape), None if atten is None else tuple(atten.shape), shape.rows))
+        if len(lams) != shape.n_levels:
+            raise RuntimeError("center_aware_split_levels_grl: %d strengths for %d levels" % (len(lams), shape.n_levels))
+        ctx.cfg = (shape, tuple(float(v) for v in lams), C)
+        ctx.save_for_backward(atten)
+        y = rows if atten is None else _row_scale_levels(rows, C, atten, [1.0] * shape.n_levels, shape, C, torch.empty_like(rows))
+        return tuple(y[shape.row_off[l]:shape.row_off[l + 1]] for l in range(shape.n_levels))
+
+    @staticmethod
+    def backward(ctx, *grads):
+        shape, lams, C = ctx.cfg
+        atten, = ctx.saved_tensors
+        ref = next(g for g in grads if g is not None)
+        grads = [g if g is None or g.is_contiguous() else g.contiguous() for g in grads]
+        out = ref.new_empty((shape.rows, C))
+        _row_scale_levels(grads, C, atten, [-v for v in lams], shape, C, out)
+        return out, None, None, None
+
+
+def center_aware_split_levels_grl(feats, atten, shape, lams):
+    """the level views of atten[:, None] * feats behind grad_reverse(., lams[l]); atten from center_aware_map (detached)"""
+    return _CenterAwareSplitLevelsGRL.apply(feats, atten, shape, lams)
+
+
 class _TakeImages(torch.autograd.Function):
     """rows of images [i0, i1) of every level, as the pyramid of those images (level-major order is kept)."""
 
@@ -1394,6 +1466,35 @@ class _BceLogitsMean(torch.autograd.Function):
 
 def bce_with_logits_mean(logits, targets):
     return _BceLogitsMean.apply(logits.contiguous(), targets.contiguous())
+
+
+class _BceLogitsConstMean(torch.autograd.Function):
+    """mean_m w[m] * bce(logits[m], t) against ONE constant label t, w optional (None: 1) and without gradient: the domain loss of
+    the EPM discriminators (reference fcos_head_discriminator.py:71-72; _CA.py:86-88 with w = the centre-aware map).  The divisor
+    is M, not sum(w).  No label tensor is built: the kernels take the constant."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight):
+        _chk(logits, weight)
+        M = logits.numel()
+        out = logits.new_zeros((2,))
+        _call_reduction("scan_bce_logits", "_forward", logits, (M,), _ptr(logits), None, target, _ptr(weight), 1, M, _ptr(out))
+        ctx.save_for_backward(logits, weight)
+        ctx.target = target
+        return out[0] / M
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, weight = ctx.saved_tensors
+        M = logits.numel()
+        gn = (g / M).reshape(1).contiguous()
+        d = torch.empty_like(logits)
+        call("scan_bce_logits_backward", _ptr(logits), None, ctx.target, _ptr(weight), 1, M, _ptr(gn), _ptr(d), _stream())
+        return d, None, None
+
+
+def bce_with_logits_const_mean(logits, target, weight=None):
+    return _BceLogitsConstMean.apply(logits.contiguous(), float(target), None if weight is None else weight.detach().contiguous())
 
 
 def _cka_forward_loss(logits, act, M, cf, target, out):

@@ -172,6 +172,32 @@ def discriminator_state_dict(level, num_classes=9):
 LEVEL_NAMES = ("P3", "P4", "P5", "P6", "P7")
 
 
+def epm_discriminator_state_dict(name, num_convs=4):
+    """FCOSDiscriminator / FCOSDiscriminator_CA of the EPM baseline (reference discriminator/fcos_head_discriminator.py:11-55,
+    fcos_head_discriminator_CA.py:7-54: the same parameters); name: the model key ("dis_P3", "dis_P3_CA"), which seeds it."""
+    tag = "epm_" + name
+    t = {}
+    _tower(t, tag + ".dis_tower", num_convs)
+    _conv(t, tag + ".cls_logits", 1, 256, 3, 1.0)
+    return {k[len(tag) + 1:]: v for k, v in t.items()}
+
+
+def epm_state_dicts(num_classes=9, adv=("ga",), conv_body="VGG-16-FPN-RETINANET", dis_num_convs=4, ca_dis_num_convs=4):
+    """backbone, head and the GA (/ CA) discriminators of epm.build_model; *_num_convs: one count or {level: count}"""
+    out = {
+        "backbone": backbone_state_dict() if conv_body.startswith("VGG") else
+        resnet_backbone_state_dict(conv_body[:-len("-FPN-RETINANET")]),
+        "fcos": fcos_state_dict(num_classes),
+    }
+    count = lambda n, lvl: n[lvl] if isinstance(n, dict) else n
+    for lvl in LEVEL_NAMES:
+        if "ga" in adv:
+            out["dis_%s" % lvl] = epm_discriminator_state_dict("dis_%s" % lvl, count(dis_num_convs, lvl))
+        if "ca" in adv:
+            out["dis_%s_CA" % lvl] = epm_discriminator_state_dict("dis_%s_CA" % lvl, count(ca_dis_num_convs, lvl))
+    return out
+
+
 def all_state_dicts(num_classes=9, conv_body="VGG-16-FPN-RETINANET"):
     out = {
         "backbone": backbone_state_dict() if conv_body.startswith("VGG") else
