@@ -772,6 +772,15 @@ int scan_cka_stack_weights(const scan_cka_branch_t* branches, int32_t Cf, int32_
 int scan_cka_unstack_grads(const scan_cka_branch_t* grads, int32_t Cf, int32_t C, int32_t H, int64_t s1o, int64_t s1c,
                            int64_t s1k, int64_t s2c, int64_t s2k, int32_t Cs1, int32_t Cs2, const float* dw1,
                            const float* db1, const float* dw2, const float* db2, int32_t accumulate, void* stream);
+/* Split form for the class branches whose act term runs inside the grouped conv (scan_gconv3x3_to1_act_* below): wmain
+ * [Cf*H][9][C] = the C feature columns of every w0, e [Cf][9][H] = its act-map column, b1 / w2 / b2 as above.  unstack: dwmain
+ * and de into the per-class w0 gradients (a null gradient leaves its elements alone). */
+int scan_cka_stack_weights_split(const scan_cka_branch_t* branches, int32_t Cf, int32_t C, int32_t H, int64_t s1o, int64_t s1c,
+                                 int64_t s1k, int64_t s2c, int64_t s2k, int32_t Cs2, float* wmain, float* e, float* b1,
+                                 float* w2, float* b2, void* stream);
+int scan_cka_unstack_grads_split(const scan_cka_branch_t* grads, int32_t Cf, int32_t C, int32_t H, int64_t s1o, int64_t s1c,
+                                 int64_t s1k, int64_t s2c, int64_t s2k, int32_t Cs2, const float* dwmain, const float* de,
+                                 const float* db1, const float* dw2, const float* db2, int32_t accumulate, void* stream);
 
 /* ---- the class branches' second convolution: G groups of 128 channels -> one output channel per group ----
  * replaces `classifier_cls_c[2]` = nn.Conv2d(128, 1, 3, padding=1) applied per foreground class
@@ -808,6 +817,30 @@ int scan_gconv3x3_to1_any_wgrad(const float* x, const float* dy, int32_t Ns, con
 int scan_gconv3x3_to1_any_backward(const float* x, const float* dy, int32_t Ns, const scan_pyramid_t* d, int32_t G, int32_t Cg,
                                    const float* w, int32_t relu_mask, float* dx, float* dw, int32_t accumulate, float* ws,
                                    void* stream);
+/* The same conv with the class branches' act-map term formed in registers (G = 1, 2, 4, 8): x = h_main [M][G*128], the first
+ * conv on the feature channels alone, stored BEFORE its ReLU; a = act map rows [M][lda], class g in column a_col0 + g;
+ * E [G][9][128] = the act column of each class's first-conv weight.  The kernels read
+ *   hv[q][g*128 + i] = relu(x[q][g*128 + i] + sum_t E[g][t][i] * a[nb(q, t)][a_col0 + g])     (zero outside the image)
+ * where the entry points above read x: forward y = conv(hv), backward dx = (hv > 0) * dgrad (the gradient of x AND of the
+ * act term) and dw from hv.  act_grads is the act term's own backward, one pass over dh (= that dx):
+ *   dE[g][t][i] = sum_q dh[q][g*128 + i] * a[nb(q, t)][a_col0 + g]     (fixed-order sums; added to dE when accumulate != 0)
+ *   da[q][da_col0 + g] = sum_t sum_i E[g][t][i] * dh[nb(q, -t)][g*128 + i]     (every other column of da [M][ldda] := 0)
+ * Workspace of each: scan_gconv3x3_to1_act_ws_floats floats. */
+int64_t scan_gconv3x3_to1_act_ws_floats(const scan_pyramid_t* d, int32_t G, int32_t Cg);
+int scan_gconv3x3_to1_act_forward(const float* x, const scan_pyramid_t* d, int32_t G, int32_t Cg, const float* w,
+                                  const float* bias, const float* a, int32_t lda, int32_t a_col0, const float* E, float* y,
+                                  int32_t Ns, float* ws, void* stream);
+int scan_gconv3x3_to1_act_backward(const float* x, const float* dy, int32_t Ns, const scan_pyramid_t* d, int32_t G, int32_t Cg,
+                                   const float* w, const float* a, int32_t lda, int32_t a_col0, const float* E, float* dx,
+                                   float* dw, int32_t accumulate, float* ws, void* stream);
+int scan_gconv3x3_to1_act_grads(const float* dh, const scan_pyramid_t* d, int32_t G, int32_t Cg, const float* a, int32_t lda,
+                                int32_t a_col0, const float* E, float* da, int32_t ldda, int32_t da_col0, float* dE,
+                                int32_t accumulate, float* ws, void* stream);
+/* act_backward and act_grads in one pass over x (dx is used while it is in registers and never read back); same results */
+int scan_gconv3x3_to1_act_backward_all(const float* x, const float* dy, int32_t Ns, const scan_pyramid_t* d, int32_t G,
+                                       int32_t Cg, const float* w, const float* a, int32_t lda, int32_t a_col0, const float* E,
+                                       float* dx, float* dw, float* da, int32_t ldda, int32_t da_col0, float* dE,
+                                       int32_t accumulate, float* ws, void* stream);
 /* forward that also leaves the ReLU mask of x as bits (relu_bits: M * G * 4 uint32; bit 4 j + e of word
  * [(row * G + g) * 4 + q] = x[row][g * 128 + 16 j + 4 q + e] > 0), and the backward that masks dx with them instead of
  * re-reading x for the mask. */

@@ -225,6 +225,19 @@ SIGNATURES = {
     "scan_gconv3x3_to1_forward_bits": (ctypes.c_int, [c_vp, _PD, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "scan_gconv3x3_to1_backward_bits": (ctypes.c_int, [c_vp, c_vp, c_i32, _PD, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32,
                                                        c_vp, c_vp]),
+    "scan_cka_stack_weights_split": (ctypes.c_int, [ctypes.POINTER(CkaBranch), c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_i64,
+                                                    c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "scan_cka_unstack_grads_split": (ctypes.c_int, [ctypes.POINTER(CkaBranch), c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_i64,
+                                                    c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
+    "scan_gconv3x3_to1_act_ws_floats": (c_i64, [_PD, c_i32, c_i32]),
+    "scan_gconv3x3_to1_act_forward": (ctypes.c_int, [c_vp, _PD, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32,
+                                                     c_vp, c_vp]),
+    "scan_gconv3x3_to1_act_backward": (ctypes.c_int, [c_vp, c_vp, c_i32, _PD, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp,
+                                                      c_vp, c_i32, c_vp, c_vp]),
+    "scan_gconv3x3_to1_act_backward_all": (ctypes.c_int, [c_vp, c_vp, c_i32, _PD, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp,
+                                                          c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp]),
+    "scan_gconv3x3_to1_act_grads": (ctypes.c_int, [c_vp, _PD, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp,
+                                                   c_i32, c_vp, c_vp]),
     "scan_resize_bilinear_u8": (ctypes.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp,
                                                c_i32, c_vp]),
     # ordered (bit-reproducible) forms of the reductions, scan_tune "deterministic": the twin's arguments + ws before stream

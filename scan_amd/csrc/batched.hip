@@ -244,11 +244,13 @@ struct CkaPtrs {
 __global__ __launch_bounds__(256) void cka_stack_kernel(CkaPtrs P, int Cf, int C, int H, int64_t s1o, int64_t s1c,
                                                         int64_t s1k, int64_t s2c, int64_t s2k, int Cs1, int Cs2,
                                                         float* __restrict__ w1, float* __restrict__ b1,
-                                                        float* __restrict__ w2, float* __restrict__ b2) {
+                                                        float* __restrict__ w2, float* __restrict__ b2,
+                                                        float* __restrict__ e) {
   const int64_t n1 = (int64_t)Cf * H * 9 * Cs1;   // w1 [Cf*H][9][Cs1]
   const int64_t n2 = (int64_t)Cf * 9 * Cs2;       // w2 [Cf][9][Cs2], Cs2 >= Cf*H
   const int64_t nb = (int64_t)Cf * H + Cf;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n1 + n2 + nb;
+  const int64_t ne = e != nullptr ? (int64_t)Cf * 9 * H : 0;  // split form: e [Cf][9][H], the act column of every w0
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n1 + n2 + nb + ne;
        i += (int64_t)gridDim.x * blockDim.x) {
     if (i < n1) {
       const int col = (int)(i % Cs1);
@@ -258,7 +260,7 @@ __global__ __launch_bounds__(256) void cka_stack_kernel(CkaPtrs P, int Cf, int C
       const int c = row / H, o = row - c * H;
       float v = 0.f;
       if (col < C) v = P.b[c].w0[o * s1o + col * s1c + k * s1k];
-      else if (col == C + c) v = P.b[c].w0[o * s1o + C * s1c + k * s1k];
+      else if (e == nullptr && col == C + c) v = P.b[c].w0[o * s1o + C * s1c + k * s1k];
       w1[i] = v;
     } else if (i < n1 + n2) {
       const int64_t q = i - n1;
@@ -269,10 +271,17 @@ __global__ __launch_bounds__(256) void cka_stack_kernel(CkaPtrs P, int Cf, int C
       float v = 0.f;
       if (col >= c * H && col < (c + 1) * H) v = P.b[c].w2[(col - c * H) * s2c + k * s2k];
       w2[q] = v;
-    } else {
+    } else if (i < n1 + n2 + nb) {
       const int q = (int)(i - n1 - n2);
       if (q < Cf * H) b1[q] = P.b[q / H].b0[q % H];
       else b2[q - Cf * H] = P.b[q - Cf * H].b2[0];
+    } else {
+      const int64_t q = i - n1 - n2 - nb;
+      const int o = (int)(q % H);
+      const int64_t r = q / H;
+      const int k = (int)(r % 9);
+      const int c = (int)(r / 9);
+      e[q] = P.b[c].w0[o * s1o + C * s1c + k * s1k];
     }
   }
 }
@@ -281,7 +290,7 @@ __global__ __launch_bounds__(256) void cka_unstack_kernel(CkaPtrs G, int Cf, int
                                                           int64_t s1k, int64_t s2c, int64_t s2k, int Cs1, int Cs2,
                                                           const float* __restrict__ dw1, const float* __restrict__ db1,
                                                           const float* __restrict__ dw2, const float* __restrict__ db2,
-                                                          int accumulate) {
+                                                          const float* __restrict__ de, int accumulate) {
   const int64_t n1 = (int64_t)Cf * H * 9 * (C + 1);  // one element of every w0 gradient
   const int64_t n2 = (int64_t)Cf * 9 * H;
   const int64_t nb = (int64_t)Cf * H + Cf;
@@ -293,7 +302,13 @@ __global__ __launch_bounds__(256) void cka_unstack_kernel(CkaPtrs G, int Cf, int
       const int k = (int)(r % 9);
       const int row = (int)(r / 9);
       const int c = row / H, o = row - c * H;
-      if (dw1 != nullptr) {
+      if (Cs1 == C && col == C) {  // split form (dw1 has no act columns): the act column's gradient comes as de [Cf][9][H]
+        if (de != nullptr) {
+          float* dst = const_cast<float*>(G.b[c].w0) + o * s1o + col * s1c + k * s1k;
+          const float v = de[((int64_t)c * 9 + k) * H + o];
+          *dst = accumulate ? *dst + v : v;
+        }
+      } else if (dw1 != nullptr) {
         const float v = dw1[((int64_t)row * 9 + k) * Cs1 + (col < C ? col : C + c)];
         float* dst = const_cast<float*>(G.b[c].w0) + o * s1o + col * s1c + k * s1k;
         *dst = accumulate ? *dst + v : v;
@@ -324,9 +339,12 @@ __global__ __launch_bounds__(256) void cka_unstack_kernel(CkaPtrs G, int Cf, int
   }
 }
 
-static int cka_check(const scan_cka_branch_t* br, int Cf, int C, int H, int Cs1, int Cs2, const char* who) {
+// split: the act columns live in a tensor of their own (w1 holds the C main columns only)
+static int cka_check(const scan_cka_branch_t* br, int Cf, int C, int H, int Cs1, int Cs2, const char* who,
+                     bool split = false) {
   SCAN_CHECK_ARG(br && Cf >= 1 && Cf <= SCAN_CKA_MAX_CLASSES, "%s: Cf=%d out of 1..%d", who, Cf, SCAN_CKA_MAX_CLASSES);
-  SCAN_CHECK_ARG(C > 0 && H > 0 && Cs1 >= C + Cf && Cs2 >= Cf * H, "%s: C=%d H=%d Cs1=%d Cs2=%d", who, C, H, Cs1, Cs2);
+  SCAN_CHECK_ARG(C > 0 && H > 0 && Cs1 >= C + (split ? 0 : Cf) && Cs2 >= Cf * H, "%s: C=%d H=%d Cs1=%d Cs2=%d", who, C, H,
+                 Cs1, Cs2);
   for (int c = 0; c < Cf; ++c)
     SCAN_CHECK_ARG(br[c].w0 && br[c].b0 && br[c].w2 && br[c].b2, "%s: null pointer in branch %d", who, c);
   return 0;
@@ -341,8 +359,24 @@ extern "C" int scan_cka_stack_weights(const scan_cka_branch_t* branches, int32_t
   for (int c = 0; c < Cf; ++c) P.b[c] = branches[c];
   const int64_t n = (int64_t)Cf * H * 9 * Cs1 + (int64_t)Cf * 9 * Cs2 + (int64_t)Cf * H + Cf;
   hipLaunchKernelGGL(cka_stack_kernel, dim3(grid_for(n, 256)), dim3(256), 0, as_stream(stream), P, Cf, C, H, s1o, s1c,
-                     s1k, s2c, s2k, Cs1, Cs2, w1, b1, w2, b2);
+                     s1k, s2c, s2k, Cs1, Cs2, w1, b1, w2, b2, (float*)nullptr);
   SCAN_LAUNCH_CHECK("cka_stack_weights");
+  return 0;
+}
+
+// Split form: wmain [Cf*H][9][C] (the C feature columns of every w0), e [Cf][9][H] (its act column), b1, w2, b2 as above --
+// the weights of the class branches whose act term runs inside the grouped conv (scan_gconv3x3_to1_act_*).
+extern "C" int scan_cka_stack_weights_split(const scan_cka_branch_t* branches, int32_t Cf, int32_t C, int32_t H, int64_t s1o,
+                                            int64_t s1c, int64_t s1k, int64_t s2c, int64_t s2k, int32_t Cs2, float* wmain,
+                                            float* e, float* b1, float* w2, float* b2, void* stream) {
+  if (cka_check(branches, Cf, C, H, C, Cs2, "cka_stack_weights_split", true)) return -1;
+  SCAN_CHECK_ARG(wmain && e && b1 && w2 && b2, "cka_stack_weights_split: null output");
+  CkaPtrs P;
+  for (int c = 0; c < Cf; ++c) P.b[c] = branches[c];
+  const int64_t n = (int64_t)Cf * H * 9 * C + (int64_t)Cf * 9 * Cs2 + (int64_t)Cf * H + Cf + (int64_t)Cf * 9 * H;
+  hipLaunchKernelGGL(cka_stack_kernel, dim3(grid_for(n, 256)), dim3(256), 0, as_stream(stream), P, Cf, C, H, s1o, s1c,
+                     s1k, s2c, s2k, C, Cs2, wmain, b1, w2, b2, e);
+  SCAN_LAUNCH_CHECK("cka_stack_weights_split");
   return 0;
 }
 
@@ -355,7 +389,22 @@ extern "C" int scan_cka_unstack_grads(const scan_cka_branch_t* grads, int32_t Cf
   for (int c = 0; c < Cf; ++c) G.b[c] = grads[c];
   const int64_t n = (int64_t)Cf * H * 9 * (C + 1) + (int64_t)Cf * 9 * H + (int64_t)Cf * H + Cf;
   hipLaunchKernelGGL(cka_unstack_kernel, dim3(grid_for(n, 256)), dim3(256), 0, as_stream(stream), G, Cf, C, H, s1o, s1c,
-                     s1k, s2c, s2k, Cs1, Cs2, dw1, db1, dw2, db2, accumulate);
+                     s1k, s2c, s2k, Cs1, Cs2, dw1, db1, dw2, db2, (const float*)nullptr, accumulate);
   SCAN_LAUNCH_CHECK("cka_unstack_grads");
+  return 0;
+}
+
+// Split form: dwmain [Cf*H][9][C] and de [Cf][9][H] into the per-class w0 gradients (a null one leaves its elements alone)
+extern "C" int scan_cka_unstack_grads_split(const scan_cka_branch_t* grads, int32_t Cf, int32_t C, int32_t H, int64_t s1o,
+                                            int64_t s1c, int64_t s1k, int64_t s2c, int64_t s2k, int32_t Cs2,
+                                            const float* dwmain, const float* de, const float* db1, const float* dw2,
+                                            const float* db2, int32_t accumulate, void* stream) {
+  if (cka_check(grads, Cf, C, H, C, Cs2, "cka_unstack_grads_split", true)) return -1;
+  CkaPtrs G;
+  for (int c = 0; c < Cf; ++c) G.b[c] = grads[c];
+  const int64_t n = (int64_t)Cf * H * 9 * (C + 1) + (int64_t)Cf * 9 * H + (int64_t)Cf * H + Cf;
+  hipLaunchKernelGGL(cka_unstack_kernel, dim3(grid_for(n, 256)), dim3(256), 0, as_stream(stream), G, Cf, C, H, s1o, s1c,
+                     s1k, s2c, s2k, C, Cs2, dwmain, db1, dw2, db2, de, accumulate);
+  SCAN_LAUNCH_CHECK("cka_unstack_grads_split");
   return 0;
 }

@@ -733,3 +733,426 @@ extern "C" int scan_gconv3x3_to1_any_backward(const float* x, const float* dy, i
   return gconv_backward(x, dy, Ns, d, G, Cg, w, relu_mask, nullptr, dx, dw, accumulate, ws, as_stream(stream),
                         "gconv3x3_to1_any_backward", true);
 }
+
+// ---- class branches with the act-map channel taken out of the first conv (G = 1, 2, 4, 8) ---------------------------------
+// The first conv of class c reads cat(x, act[c + 1]); its act channel reaches only that class's 128 hidden channels, so
+// the dense conv runs on x alone (h_main = conv3x3(x; Wmain) + b1, stored before the ReLU) and the kernels below add
+//   hact[q][g * 128 + i] = sum_t E[g][t][i] * a[nb(q, t)][g]        (E [G][9][128] = the act column of each class's weight,
+//                                                                   a = act[:, a_col0 + g], zero outside the image)
+// in registers wherever the kernels above read x:  hv = relu(h_main + hact)  feeds the tap products (forward), the mask
+// (hv > 0) and the dw accumulation (backward).  Both directions add the nine terms in the tap order t = 0..8, so the
+// backward's mask is bit for bit the forward's ReLU.  The act term's own gradients, dE[g][t][i] = sum_q dh[q][g * 128 + i] *
+// a[nb(q, t)][g] in per-workgroup slabs summed in a fixed order and da[q][g] = sum_t <E[g][t], dh[nb(q, -t)][g * 128 ..]> as
+// tap sums + the gather, come from dh while the backward kernel holds it in registers (gconv_bwd_act_kernel<.., true>:
+// 0.16 ms of the training step faster than re-reading dh) or from one more pass over dh (gconv_act_grads_kernel).  No atomics.
+
+// the nine values src[nb(q, SIGN * off(t)) * ld + g] of one (pixel, group), zero outside the image.  uniform (one pixel per
+// workgroup iteration, q wave-uniform): lanes 0..17 fetch the 9 x 2 values of the wave's two groups with one load and every
+// lane picks its own by v_readlane, as in gconv_bwd_kernel.
+template <int SIGN>
+__device__ __forceinline__ void tap_values(const scan_pyramid_t& d, int64_t q, const RowCoord& rc,
+                                           const float* __restrict__ src, int ld, int g, bool uniform, float (&v)[9]) {
+  if (uniform) {
+    const int g0 = 2 * (int)(threadIdx.x >> 6);
+    const int l = threadIdx.x & 63;
+    const int tl = l % 9, gl = l / 9;
+    const int64_t pl = l < 18 ? neighbour_row(d, q, rc, SIGN * (tl / 3 - 1), SIGN * (tl % 3 - 1)) : -1;
+    const float val = pl >= 0 ? src[pl * ld + g0 + gl] : 0.f;
+    const int vb = __builtin_bit_cast(int, val);
+    const bool hi = (l & 32) != 0;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      const float lo_v = __builtin_bit_cast(float, __builtin_amdgcn_readlane(vb, t));
+      const float hi_v = __builtin_bit_cast(float, __builtin_amdgcn_readlane(vb, 9 + t));
+      v[t] = hi ? hi_v : lo_v;
+    }
+  } else {
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      const int64_t p = neighbour_row(d, q, rc, SIGN * (t / 3 - 1), SIGN * (t % 3 - 1));
+      v[t] = p >= 0 ? src[p * ld + g] : 0.f;
+    }
+  }
+}
+
+// relu(h + sum_t ev[t] * av[t]), t ascending
+__device__ __forceinline__ float4 act_hidden(float4 h, const float4 (&ev)[9], const float (&av)[9]) {
+#pragma unroll
+  for (int t = 0; t < 9; ++t) {
+    h.x = __fmaf_rn(av[t], ev[t].x, h.x);
+    h.y = __fmaf_rn(av[t], ev[t].y, h.y);
+    h.z = __fmaf_rn(av[t], ev[t].z, h.z);
+    h.w = __fmaf_rn(av[t], ev[t].w, h.w);
+  }
+  h.x = h.x > 0.f ? h.x : 0.f;
+  h.y = h.y > 0.f ? h.y : 0.f;
+  h.z = h.z > 0.f ? h.z : 0.f;
+  h.w = h.w > 0.f ? h.w : 0.f;
+  return h;
+}
+
+__device__ __forceinline__ int64_t uniform_row(int64_t q) {
+  return ((int64_t)__builtin_amdgcn_readfirstlane((int)(q >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)q);
+}
+
+// UNI: G = 8, one pixel per workgroup iteration (slots == 1): the pixel row is wave-uniform
+#define GC_UNROLL_A 2  // pixels in flight per thread of the act backward kernels (nine more weight quads in registers)
+
+template <bool UNI>
+__global__ __launch_bounds__(256) void gconv_taps_act_kernel(const float* __restrict__ x, scan_pyramid_t d, int G, int GC,
+                                                             const float* __restrict__ w, const float* __restrict__ a,
+                                                             int lda, const float* __restrict__ E, float* __restrict__ T) {
+  const int64_t M = d.row_off[d.n_levels];
+  const int quads = GC >> 2, slots = 256 / quads;
+  const int cq = threadIdx.x % quads, slot = threadIdx.x / quads;
+  const int g = cq >> 5, l32 = cq & 31;
+  float4 wv[9], ev[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t) {
+    wv[t] = *reinterpret_cast<const float4*>(w + ((int64_t)g * 9 + t) * GC + 4 * cq);
+    ev[t] = *reinterpret_cast<const float4*>(E + ((int64_t)g * 9 + t) * GC_G + 4 * l32);
+  }
+  const int64_t stride = (int64_t)gridDim.x * slots;
+  for (int64_t q0 = (int64_t)blockIdx.x * slots + slot; q0 < M; q0 += GC_UNROLL_F * stride) {
+    float4 h[GC_UNROLL_F];
+#pragma unroll
+    for (int u = 0; u < GC_UNROLL_F; ++u) {
+      const int64_t q = q0 + u * stride;
+      h[u] = q < M ? *reinterpret_cast<const float4*>(x + q * GC + 4 * cq) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int u = 0; u < GC_UNROLL_F; ++u) {
+      int64_t q = q0 + u * stride;
+      if (UNI) q = uniform_row(q);
+      if (q >= M) continue;
+      float av[9];  // fetched per pixel right before use: nine registers, not nine per pixel in flight
+      tap_values<1>(d, q, decode_row(d, q), a, lda, g, UNI, av);
+      const float4 hv = act_hidden(h[u], ev, av);
+      float mine = 0.f;
+#pragma unroll
+      for (int t = 0; t < 9; ++t) {
+        float s = __fmaf_rn(hv.x, wv[t].x, __fmaf_rn(hv.y, wv[t].y, __fmaf_rn(hv.z, wv[t].z, hv.w * wv[t].w)));
+        s = half_wave_sum_hi(s);
+        if (l32 == 16 + t) mine = s;
+      }
+      if (l32 >= 16 && l32 < 25) T[(q * G + g) * 9 + (l32 - 16)] = mine;
+    }
+  }
+}
+
+// per-workgroup partials acc[t] (one float4 per thread and tap) -> slab[block][t][GC], pixel slots added in slot order
+__device__ __forceinline__ void slab_store(const float4 (&acc)[9], float* __restrict__ red, float* __restrict__ slab, int GC,
+                                           int quads, int slots, int cq, int slot) {
+  float* out = slab + (int64_t)blockIdx.x * 9 * GC;
+  if (slots == 1) {
+#pragma unroll
+    for (int t = 0; t < 9; ++t) *reinterpret_cast<float4*>(out + (int64_t)t * GC + 4 * cq) = acc[t];
+    return;
+  }
+#pragma unroll
+  for (int t = 0; t < 9; ++t) *reinterpret_cast<float4*>(red + (t * 256 + threadIdx.x) * 4) = acc[t];
+  __syncthreads();
+  if (slot == 0) {
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      float4 s = acc[t];
+      for (int k = 1; k < slots; ++k) {
+        const float4 v = *reinterpret_cast<const float4*>(red + (t * 256 + k * quads + cq) * 4);
+        s.x += v.x;
+        s.y += v.y;
+        s.z += v.z;
+        s.w += v.w;
+      }
+      *reinterpret_cast<float4*>(out + (int64_t)t * GC + 4 * cq) = s;
+    }
+  }
+}
+
+// gconv_bwd_kernel<true, true> on hv = relu(x + hact): dx = (hv > 0) * sum_t dy_t * w[t], dw partials of hv
+// FUSE: the act term's own gradients in the same pass, from dx while it is in registers (no second read of dh): the dE
+// partials accE[t] += a[nb(q, t)] * dx[q] into slab_e and the tap sums of da into T, as gconv_act_grads_kernel forms them
+template <bool UNI, bool FUSE>
+__global__ __launch_bounds__(256, (UNI && !FUSE) ? 3 : 2) void gconv_bwd_act_kernel(
+    const float* __restrict__ x, const float* __restrict__ dy, int Ns, scan_pyramid_t d, int G, int GC,
+    const float* __restrict__ w, const float* __restrict__ a, int lda, const float* __restrict__ E, float* __restrict__ dx,
+    float* __restrict__ slab, float* __restrict__ T, float* __restrict__ slab_e) {
+  __shared__ float red[9 * 1024];
+  const int64_t M = d.row_off[d.n_levels];
+  const int quads = GC >> 2, slots = 256 / quads;
+  const int cq = threadIdx.x % quads, slot = threadIdx.x / quads;
+  const int g = cq >> 5, l32 = cq & 31;
+  float4 wv[9], ev[9], acc[9], acc_e[9];  // dead without FUSE
+#pragma unroll
+  for (int t = 0; t < 9; ++t) {
+    wv[t] = *reinterpret_cast<const float4*>(w + ((int64_t)g * 9 + t) * GC + 4 * cq);
+    ev[t] = *reinterpret_cast<const float4*>(E + ((int64_t)g * 9 + t) * GC_G + 4 * l32);
+    acc[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (FUSE) acc_e[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  // rows dealt round-robin in groups of UN * slots, as in gconv_bwd_kernel
+  for (int64_t q0 = (int64_t)blockIdx.x * GC_UNROLL_A * slots + slot; q0 < M;
+       q0 += (int64_t)gridDim.x * GC_UNROLL_A * slots) {
+    float4 h[GC_UNROLL_A];
+#pragma unroll
+    for (int u = 0; u < GC_UNROLL_A; ++u) {
+      const int64_t q = q0 + u * slots;
+      h[u] = q < M ? *reinterpret_cast<const float4*>(x + q * GC + 4 * cq) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int u = 0; u < GC_UNROLL_A; ++u) {
+      int64_t q = q0 + u * slots;
+      if (UNI) q = uniform_row(q);
+      if (q >= M) continue;
+      // the tap values of one pixel at a time, right before use: 9 + 9 registers, not 18 per pixel in flight
+      const RowCoord rc = decode_row(d, q);
+      float av[9], gy[9];
+      tap_values<1>(d, q, rc, a, lda, g, UNI, av);
+      const float4 hv = act_hidden(h[u], ev, av);
+      tap_values<-1>(d, q, rc, dy, Ns, g, UNI, gy);  // x[q] feeds y[q - off(t)]
+      float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int t = 0; t < 9; ++t) {
+        acc[t].x = __fmaf_rn(gy[t], hv.x, acc[t].x);
+        acc[t].y = __fmaf_rn(gy[t], hv.y, acc[t].y);
+        acc[t].z = __fmaf_rn(gy[t], hv.z, acc[t].z);
+        acc[t].w = __fmaf_rn(gy[t], hv.w, acc[t].w);
+        o.x = __fmaf_rn(gy[t], wv[t].x, o.x);
+        o.y = __fmaf_rn(gy[t], wv[t].y, o.y);
+        o.z = __fmaf_rn(gy[t], wv[t].z, o.z);
+        o.w = __fmaf_rn(gy[t], wv[t].w, o.w);
+      }
+      o.x = hv.x > 0.f ? o.x : 0.f;
+      o.y = hv.y > 0.f ? o.y : 0.f;
+      o.z = hv.z > 0.f ? o.z : 0.f;
+      o.w = hv.w > 0.f ? o.w : 0.f;
+      *reinterpret_cast<float4*>(dx + q * GC + 4 * cq) = o;
+      if (FUSE) {
+        float mine = 0.f;
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+          acc_e[t].x = __fmaf_rn(av[t], o.x, acc_e[t].x);
+          acc_e[t].y = __fmaf_rn(av[t], o.y, acc_e[t].y);
+          acc_e[t].z = __fmaf_rn(av[t], o.z, acc_e[t].z);
+          acc_e[t].w = __fmaf_rn(av[t], o.w, acc_e[t].w);
+          float s = __fmaf_rn(o.x, ev[8 - t].x, __fmaf_rn(o.y, ev[8 - t].y, __fmaf_rn(o.z, ev[8 - t].z, o.w * ev[8 - t].w)));
+          s = half_wave_sum_hi(s);
+          if (l32 == 16 + t) mine = s;
+        }
+        if (l32 >= 16 && l32 < 25) T[(q * G + g) * 9 + (l32 - 16)] = mine;
+      }
+    }
+  }
+  slab_store(acc, red, slab, GC, quads, slots, cq, slot);
+  if (FUSE) {
+    __syncthreads();  // the LDS staging of the first store is read by then
+    slab_store(acc_e, red, slab_e, GC, quads, slots, cq, slot);
+  }
+}
+
+// one pass over dh: the dE partials (acc[t] += a[nb(q, t)] * dh[q]) and the tap sums of da,
+// T[q][g][t] = <dh[q][g * 128 ..], E[g][8 - t]>, so that da[p][g] = sum_t T[nb(p, t)][g][t] (the forward gather)
+template <bool UNI>
+__global__ __launch_bounds__(256) void gconv_act_grads_kernel(const float* __restrict__ dh, scan_pyramid_t d, int G, int GC,
+                                                              const float* __restrict__ a, int lda,
+                                                              const float* __restrict__ E, float* __restrict__ T,
+                                                              float* __restrict__ slab) {
+  __shared__ float red[9 * 1024];
+  const int64_t M = d.row_off[d.n_levels];
+  const int quads = GC >> 2, slots = 256 / quads;
+  const int cq = threadIdx.x % quads, slot = threadIdx.x / quads;
+  const int g = cq >> 5, l32 = cq & 31;
+  float4 ev[9], acc[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t) {
+    ev[t] = *reinterpret_cast<const float4*>(E + ((int64_t)g * 9 + t) * GC_G + 4 * l32);
+    acc[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  for (int64_t q0 = (int64_t)blockIdx.x * GC_UNROLL_A * slots + slot; q0 < M;
+       q0 += (int64_t)gridDim.x * GC_UNROLL_A * slots) {
+    float4 h[GC_UNROLL_A];
+#pragma unroll
+    for (int u = 0; u < GC_UNROLL_A; ++u) {
+      const int64_t q = q0 + u * slots;
+      h[u] = q < M ? *reinterpret_cast<const float4*>(dh + q * GC + 4 * cq) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int u = 0; u < GC_UNROLL_A; ++u) {
+      int64_t q = q0 + u * slots;
+      if (UNI) q = uniform_row(q);
+      if (q >= M) continue;
+      float av[9];
+      tap_values<1>(d, q, decode_row(d, q), a, lda, g, UNI, av);
+      float mine = 0.f;
+#pragma unroll
+      for (int t = 0; t < 9; ++t) {
+        acc[t].x = __fmaf_rn(av[t], h[u].x, acc[t].x);
+        acc[t].y = __fmaf_rn(av[t], h[u].y, acc[t].y);
+        acc[t].z = __fmaf_rn(av[t], h[u].z, acc[t].z);
+        acc[t].w = __fmaf_rn(av[t], h[u].w, acc[t].w);
+        float s = __fmaf_rn(h[u].x, ev[8 - t].x,
+                            __fmaf_rn(h[u].y, ev[8 - t].y, __fmaf_rn(h[u].z, ev[8 - t].z, h[u].w * ev[8 - t].w)));
+        s = half_wave_sum_hi(s);
+        if (l32 == 16 + t) mine = s;
+      }
+      if (l32 >= 16 && l32 < 25) T[(q * G + g) * 9 + (l32 - 16)] = mine;
+    }
+  }
+  slab_store(acc, red, slab, GC, quads, slots, cq, slot);
+}
+
+// the gather into columns col0 .. col0 + G of y [M][ldy]; every other column of the row is written as zero
+__global__ __launch_bounds__(256) void gconv_gather_cols_kernel(const float* __restrict__ T, scan_pyramid_t d, int G,
+                                                                float* __restrict__ y, int ldy, int col0) {
+  const int64_t M = d.row_off[d.n_levels];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < M * ldy; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t p = i / ldy;
+    const int g = (int)(i - p * ldy) - col0;
+    float acc = 0.f;
+    if (g >= 0 && g < G) {
+      const RowCoord rc = decode_row(d, p);
+#pragma unroll
+      for (int t = 0; t < 9; ++t) {
+        const int64_t q = neighbour_row(d, p, rc, t / 3 - 1, t % 3 - 1);
+        if (q >= 0) acc += T[(q * G + g) * 9 + t];
+      }
+    }
+    y[i] = acc;
+  }
+}
+
+// partial [parts][t][GC] -> dE[g][t][128]
+__global__ __launch_bounds__(256) void gconv_act_reduce_kernel(const float* __restrict__ partial, int parts, int GC,
+                                                               float* __restrict__ dE, int accumulate) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;  // over 9 * GC
+  if (i >= 9 * GC) return;
+  const int t = i / GC, c = i - t * GC;
+  float s = 0.f;
+  for (int b = 0; b < parts; ++b) s += partial[(int64_t)b * 9 * GC + i];
+  float* dst = dE + ((int64_t)(c / GC_G) * 9 + t) * GC_G + c % GC_G;
+  *dst = accumulate ? *dst + s : s;
+}
+
+static int gconv_act_check(const scan_pyramid_t* d, int G, int Cg, const float* a, int lda, int a_col0, const float* E,
+                           const char* who) {
+  if (gconv_check(d, G, Cg, who)) return -1;
+  SCAN_CHECK_ARG(a && E && a_col0 >= 0 && lda >= a_col0 + G, "%s: bad act map (lda=%d, first column %d, G=%d)", who, lda,
+                 a_col0, G);
+  return 0;
+}
+
+// workgroups of the slab kernels (the grid rule of gconv_backward)
+static int gconv_slab_blocks(int64_t M) {
+  int64_t rpb = (M + GC_MAX_BLOCKS - 1) / GC_MAX_BLOCKS;
+  if (rpb < 16) rpb = 16;  // small levels: fewer, fuller workgroups
+  return (int)((M + rpb - 1) / rpb);
+}
+
+static int gconv_slab_reduce(float* slab, int blocks, int GC, float** partial, hipStream_t st) {
+  const int n = 9 * GC, per = (blocks + GC_PARTS - 1) / GC_PARTS, parts = (blocks + per - 1) / per;
+  *partial = slab + (int64_t)GC_MAX_BLOCKS * n;
+  hipLaunchKernelGGL(gconv_slab_partial_kernel, dim3((n + 255) / 256, parts), dim3(256), 0, st, slab, blocks, n, per,
+                     *partial);
+  return parts;
+}
+
+// scan_gconv3x3_to1_act_backward_all keeps the tap sums and two slabs at once; the others need less
+extern "C" int64_t scan_gconv3x3_to1_act_ws_floats(const scan_pyramid_t* d, int32_t G, int32_t Cg) {
+  if (!d) return -1;
+  const int64_t M = d->row_off[d->n_levels];
+  return M * G * 9 + 2 * (int64_t)(GC_MAX_BLOCKS + GC_PARTS) * 9 * G * Cg;
+}
+
+extern "C" int scan_gconv3x3_to1_act_forward(const float* x, const scan_pyramid_t* d, int32_t G, int32_t Cg, const float* w,
+                                             const float* bias, const float* a, int32_t lda, int32_t a_col0, const float* E,
+                                             float* y, int32_t Ns, float* ws, void* stream) {
+  if (gconv_act_check(d, G, Cg, a, lda, a_col0, E, "gconv3x3_to1_act_forward")) return -1;
+  SCAN_CHECK_ARG(x && w && y && ws && Ns >= G, "gconv3x3_to1_act_forward: bad arguments (Ns=%d)", Ns);
+  const int64_t M = d->row_off[d->n_levels];
+  if (M == 0) return 0;
+  const int GC = G * Cg, slots = 256 / (GC / 4);
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL((G == 8 ? gconv_taps_act_kernel<true> : gconv_taps_act_kernel<false>), dim3(grid_for((M + slots - 1) / slots, 1)), dim3(256), 0, st, x, *d, G, GC, w,
+                     a + a_col0, lda, E, ws);
+  SCAN_LAUNCH_CHECK("gconv_taps_act");
+  hipLaunchKernelGGL(gconv_gather_kernel, dim3(grid_for(M * Ns, 256)), dim3(256), 0, st, ws, *d, G, bias, y, Ns);
+  SCAN_LAUNCH_CHECK("gconv_gather");
+  return 0;
+}
+
+extern "C" int scan_gconv3x3_to1_act_backward(const float* x, const float* dy, int32_t Ns, const scan_pyramid_t* d, int32_t G,
+                                              int32_t Cg, const float* w, const float* a, int32_t lda, int32_t a_col0,
+                                              const float* E, float* dx, float* dw, int32_t accumulate, float* ws,
+                                              void* stream) {
+  if (gconv_act_check(d, G, Cg, a, lda, a_col0, E, "gconv3x3_to1_act_backward")) return -1;
+  SCAN_CHECK_ARG(x && dy && w && dx && dw && ws && Ns >= G, "gconv3x3_to1_act_backward: bad arguments (Ns=%d)", Ns);
+  const int64_t M = d->row_off[d->n_levels];
+  if (M == 0) return 0;
+  const int GC = G * Cg, blocks = gconv_slab_blocks(M);
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL((G == 8 ? gconv_bwd_act_kernel<true, false> : gconv_bwd_act_kernel<false, false>), dim3(blocks), dim3(256),
+                     0, st, x, dy, Ns, *d, G, GC, w, a + a_col0, lda, E, dx, ws, (float*)nullptr, (float*)nullptr);
+  SCAN_LAUNCH_CHECK("gconv_bwd_act");
+  float* partial;
+  const int parts = gconv_slab_reduce(ws, blocks, GC, &partial, st);
+  SCAN_LAUNCH_CHECK("gconv_slab_partial");
+  hipLaunchKernelGGL(gconv_wgrad_reduce_kernel, dim3((9 * GC + 255) / 256), dim3(256), 0, st, partial, parts, G, GC, dw,
+                     accumulate);
+  SCAN_LAUNCH_CHECK("gconv_wgrad_reduce");
+  return 0;
+}
+
+extern "C" int scan_gconv3x3_to1_act_grads(const float* dh, const scan_pyramid_t* d, int32_t G, int32_t Cg, const float* a,
+                                           int32_t lda, int32_t a_col0, const float* E, float* da, int32_t ldda,
+                                           int32_t da_col0, float* dE, int32_t accumulate, float* ws, void* stream) {
+  if (gconv_act_check(d, G, Cg, a, lda, a_col0, E, "gconv3x3_to1_act_grads")) return -1;
+  SCAN_CHECK_ARG(dh && da && dE && ws && da_col0 >= 0 && ldda >= da_col0 + G,
+                 "gconv3x3_to1_act_grads: bad arguments (ldda=%d, first column %d)", ldda, da_col0);
+  const int64_t M = d->row_off[d->n_levels];
+  if (M == 0) return 0;
+  const int GC = G * Cg, blocks = gconv_slab_blocks(M);
+  hipStream_t st = as_stream(stream);
+  float* slab = ws + M * G * 9;
+  hipLaunchKernelGGL((G == 8 ? gconv_act_grads_kernel<true> : gconv_act_grads_kernel<false>), dim3(blocks), dim3(256), 0, st, dh, *d, G, GC, a + a_col0, lda, E, ws, slab);
+  SCAN_LAUNCH_CHECK("gconv_act_grads");
+  hipLaunchKernelGGL(gconv_gather_cols_kernel, dim3(grid_for(M * ldda, 256)), dim3(256), 0, st, ws, *d, G, da, ldda, da_col0);
+  SCAN_LAUNCH_CHECK("gconv_gather_cols");
+  float* partial;
+  const int parts = gconv_slab_reduce(slab, blocks, GC, &partial, st);
+  SCAN_LAUNCH_CHECK("gconv_slab_partial");
+  hipLaunchKernelGGL(gconv_act_reduce_kernel, dim3((9 * GC + 255) / 256), dim3(256), 0, st, partial, parts, GC, dE, accumulate);
+  SCAN_LAUNCH_CHECK("gconv_act_reduce");
+  return 0;
+}
+
+// scan_gconv3x3_to1_act_backward and scan_gconv3x3_to1_act_grads in ONE pass over x: dh is never read back
+extern "C" int scan_gconv3x3_to1_act_backward_all(const float* x, const float* dy, int32_t Ns, const scan_pyramid_t* d,
+                                                  int32_t G, int32_t Cg, const float* w, const float* a, int32_t lda,
+                                                  int32_t a_col0, const float* E, float* dx, float* dw, float* da, int32_t ldda,
+                                                  int32_t da_col0, float* dE, int32_t accumulate, float* ws, void* stream) {
+  if (gconv_act_check(d, G, Cg, a, lda, a_col0, E, "gconv3x3_to1_act_backward_all")) return -1;
+  SCAN_CHECK_ARG(x && dy && w && dx && dw && ws && Ns >= G, "gconv3x3_to1_act_backward_all: bad arguments (Ns=%d)", Ns);
+  SCAN_CHECK_ARG(da && dE && da_col0 >= 0 && ldda >= da_col0 + G,
+                 "gconv3x3_to1_act_backward_all: bad arguments (ldda=%d, first column %d)", ldda, da_col0);
+  const int64_t M = d->row_off[d->n_levels];
+  if (M == 0) return 0;
+  const int GC = G * Cg, blocks = gconv_slab_blocks(M);
+  hipStream_t st = as_stream(stream);
+  float* slab = ws + M * G * 9;
+  float* slab_e = slab + (int64_t)(GC_MAX_BLOCKS + GC_PARTS) * 9 * GC;
+  hipLaunchKernelGGL((G == 8 ? gconv_bwd_act_kernel<true, true> : gconv_bwd_act_kernel<false, true>), dim3(blocks), dim3(256), 0,
+                     st, x, dy, Ns, *d, G, GC, w, a + a_col0, lda, E, dx, slab, ws, slab_e);
+  SCAN_LAUNCH_CHECK("gconv_bwd_act");
+  hipLaunchKernelGGL(gconv_gather_cols_kernel, dim3(grid_for(M * ldda, 256)), dim3(256), 0, st, ws, *d, G, da, ldda, da_col0);
+  SCAN_LAUNCH_CHECK("gconv_gather_cols");
+  float* partial;
+  int parts = gconv_slab_reduce(slab, blocks, GC, &partial, st);
+  SCAN_LAUNCH_CHECK("gconv_slab_partial");
+  hipLaunchKernelGGL(gconv_wgrad_reduce_kernel, dim3((9 * GC + 255) / 256), dim3(256), 0, st, partial, parts, G, GC, dw,
+                     accumulate);
+  SCAN_LAUNCH_CHECK("gconv_wgrad_reduce");
+  parts = gconv_slab_reduce(slab_e, blocks, GC, &partial, st);
+  SCAN_LAUNCH_CHECK("gconv_slab_partial");
+  hipLaunchKernelGGL(gconv_act_reduce_kernel, dim3((9 * GC + 255) / 256), dim3(256), 0, st, partial, parts, GC, dE, accumulate);
+  SCAN_LAUNCH_CHECK("gconv_act_reduce");
+  return 0;
+}

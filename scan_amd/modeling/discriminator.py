@@ -10,7 +10,8 @@ foreground class c, cat(x, act[c+1]) -> conv3x3 257->128 -> ReLU -> conv3x3 128-
 classes read the same x, so the 8 first convs are ONE implicit GEMM with 8*128 output channels
 over cat(x, act[1:]) (the per-class act channel enters through a block-diagonal weight
 slice), and the 8 second convs are ONE skinny conv 1024 -> 8 with a block-diagonal weight.
-The class-weighted BCE of all classes is one wavefront-reduction kernel.
+The class-weighted BCE of all classes is one wavefront-reduction kernel.  With ops.CLS_SPLIT (default) the first GEMM runs on
+the 256 feature channels alone and each class's act channel is added in registers by the kernel of the second conv.
 
 Beside it the two discriminators of the EPM baseline (the reference's configs/epm/*.yaml): FCOSDiscriminator (global
 alignment, fcos_head_discriminator.py:11-74) and FCOSDiscriminator_CA (centre-aware, fcos_head_discriminator_CA.py:7-124),
@@ -166,6 +167,15 @@ class FCOSDiscriminator_con(nn.Module):
         if not grl_applied:  # the caller already put both inputs behind this module's GRL (ops.split_levels_grl)
             feature = self.grad_reverse(feature)
             act_maps = self.grad_reverse(act_maps)
+        blocks = [getattr(self, "classifier_cls_%d" % c) for c in range(Cf)]
+        if ops.CLS_SPLIT and ops.BATCHED and ops.GROUPED_CLS and ops.cls_split_supported(Cf):
+            # the first convs as ONE dense conv on the 256 feature channels (no cat, no pad columns); each class's act-map
+            # channel -- 72 multiply-adds per pixel and class -- is added in registers by the grouped conv that reads h.
+            # h is stored before its ReLU (the grouped conv applies it to h + act term and masks dh by it).
+            x = run_tower(self.dis_tower, feature, shape, self.num_convs)
+            wm, e, b1, w2, b2 = ops.cka_stacked_weights_split([(b[0], b[2]) for b in blocks], self.in_channels, 128)
+            h = ops.conv2d(x, wm, b1, shape, 3, 1)
+            return ops.gconv3x3_to1_act(h, w2, b2, act_maps, e, shape, Cf, 1)[:, :Cf], act_maps
         # cat([x, act[1:]], 1) (reference :104-118) without copying x: the tower's last GroupNorm writes into the first
         # 256 columns of the [M, pad4(256 + Cf)] class-branch input, only the Cf act columns are copied behind them, and
         # the backward hands the GroupNorm its column slice of the conv's data gradient in place
@@ -179,7 +189,6 @@ class FCOSDiscriminator_con(nn.Module):
             xcat = torch.cat([x, act_maps[:, 1:]], 1)  # [M, 256 + Cf]; 264 is a multiple of 4
             if cs1 != xcat.shape[1]:
                 xcat = torch.nn.functional.pad(xcat, (0, cs1 - xcat.shape[1]))
-        blocks = [getattr(self, "classifier_cls_%d" % c) for c in range(Cf)]
         if ops.BATCHED and Cf <= ops.CKA_STACK_MAX:  # the one-launch stacking takes 16 branches; more: the torch spelling
             w1, b1, w2, b2 = ops.cka_stacked_weights([(b[0], b[2]) for b in blocks], self.in_channels, 128,
                                                      xcat.shape[1])

@@ -1896,6 +1896,159 @@ def gconv3x3_to1(x, w, bias, shape, G, mask_dx=False):
     return _GroupedConvTo1.apply(x, w, bias, shape, int(G), bool(mask_dx))
 
 
+# SCAN_CLS_SPLIT=0: the class branches' first conv as one dense conv over cat(x, act[1:]) with a block-diagonal act weight
+# (264 input channels for 8 classes), for A/B.  On (default): the dense conv runs on the 256 feature channels alone and
+# the per-class act-map channel -- nine multiply-adds per hidden element -- is formed in registers by the grouped conv
+# that reads the hidden map (gconv3x3_to1_act, csrc/gconv.hip).  Same values up to the summation order.
+CLS_SPLIT = os.environ.get("SCAN_CLS_SPLIT", "1") != "0"
+
+
+# SCAN_CLS_SPLIT_FUSED=0: the act term's gradients (d act, dE) in a pass of their own over dh (scan_gconv3x3_to1_act_grads)
+# instead of inside the kernel that produces dh, for A/B.  Same sums in the same per-workgroup slab order.
+CLS_SPLIT_FUSED = os.environ.get("SCAN_CLS_SPLIT_FUSED", "1") != "0"
+
+
+def cls_split_supported(G):
+    """the act-term kernels exist for the lane-mapped class counts on the fp32 FMA gconv path"""
+    return G in (1, 2, 4, 8) and query("scan_tune_get", b"gconv_mfma") == 0
+
+
+class _CkaStackedWeightsSplit(torch.autograd.Function):
+    """_CkaStackedWeights for the split class branches: (wmain [Cf*H, C, 3, 3] channels-last, e [Cf, 9, H], b1, w2, b2) in one
+    launch; the backward scatters dwmain and de into the per-class conv0.weight gradients in one launch (straight into the
+    flat gradient buffers when the parameters have them)."""
+
+    @staticmethod
+    def forward(ctx, C, H, *params):
+        cf = len(params) // 4
+        w0s, b0s, w2s, b2s = params[0::4], params[1::4], params[2::4], params[3::4]
+        for t in params:
+            if not t.is_cuda or t.dtype != torch.float32:
+                raise RuntimeError("scan_amd ops run only on fp32 GPU (HIP) tensors -- got %s %s; no CPU fallback"
+                                   % (t.device, t.dtype))
+        w0, w2 = w0s[0], w2s[0]
+        assert tuple(w0.shape) == (H, C + 1, 3, 3) and tuple(w2.shape) == (1, H, 3, 3), (w0.shape, w2.shape)
+        for a, b in zip(w0s, w2s):
+            if a.stride() != w0.stride() or b.stride() != w2.stride() or a.shape != w0.shape or b.shape != w2.shape:
+                raise RuntimeError("cka_stacked_weights_split: the class branches must share one memory layout")
+        if w0.stride(2) != 3 * w0.stride(3) or w2.stride(2) != 3 * w2.stride(3):
+            raise RuntimeError("cka_stacked_weights_split: the 3x3 taps of a weight must be evenly strided")
+        strides = (w0.stride(0), w0.stride(1), w0.stride(3), w2.stride(1), w2.stride(3))
+        cs2 = cf * H
+        dev = w0.device
+        wm = torch.empty((cf * H, 9, C), device=dev)
+        e = torch.empty((cf, 9, H), device=dev)
+        b1 = torch.empty((cf * H,), device=dev)
+        w2o = torch.empty((cf, 9, cs2), device=dev)
+        b2 = torch.empty((cf,), device=dev)
+        arr = (_lib.CkaBranch * cf)()
+        for a, p0, q0, p2, q2 in zip(arr, w0s, b0s, w2s, b2s):
+            a.w0, a.b0, a.w2, a.b2 = p0.data_ptr(), q0.data_ptr(), p2.data_ptr(), q2.data_ptr()
+        call("scan_cka_stack_weights_split", arr, cf, C, H, *strides, cs2, _ptr(wm), _ptr(e), _ptr(b1), _ptr(w2o), _ptr(b2),
+             _stream())
+        ctx.cfg = (cf, C, H, cs2, strides)
+        ctx.params = params  # parameters (leaf tensors), needed for their .grad buffers; not graph intermediates
+        return (wm.view(cf * H, 3, 3, C).permute(0, 3, 1, 2), e, b1, w2o.view(cf, 3, 3, cs2).permute(0, 3, 1, 2), b2)
+
+    @staticmethod
+    def backward(ctx, dwm, de, db1, dw2, db2):
+        cf, C, H, cs2, strides = ctx.cfg
+        params = ctx.params
+
+        def ohwi(g):
+            return None if g is None else g.permute(0, 2, 3, 1).contiguous()
+
+        dwm, dw2 = ohwi(dwm), ohwi(dw2)
+        de, db1, db2 = (None if g is None else g.contiguous() for g in (de, db1, db2))
+        direct = all(getattr(p, "_scan_flat", False) and p.grad is not None and p.grad.stride() == p.stride()
+                     for p in params)
+        tgt = [p.grad for p in params] if direct else [torch.zeros_like(p) for p in params]
+        arr = (_lib.CkaBranch * cf)()
+        for c, a in enumerate(arr):
+            a.w0, a.b0, a.w2, a.b2 = (t.data_ptr() for t in tgt[4 * c:4 * c + 4])
+        call("scan_cka_unstack_grads_split", arr, cf, C, H, *strides, cs2, _ptr(dwm), _ptr(de), _ptr(db1), _ptr(dw2),
+             _ptr(db2), 1, _stream())
+        return (None, None) + (tuple(None for _ in params) if direct else tuple(tgt))
+
+
+def cka_stacked_weights_split(branches, C, H):
+    """branches: the Cf (conv0, conv2) module pairs.  Returns (wmain [Cf*H, C, 3, 3], e [Cf, 9, H], b1, w2 [Cf, Cf*H, 3, 3],
+    b2): conv0.weight[:, :C] of the classes stacked, conv0.weight[:, C] as e[c][ky * 3 + kx][o], and the second conv as in
+    cka_stacked_weights."""
+    params = []
+    for c0, c2 in branches:
+        params += [c0.weight, c0.bias, c2.weight, c2.bias]
+    return _CkaStackedWeightsSplit.apply(int(C), int(H), *params)
+
+
+class _GroupedConvTo1Act(torch.autograd.Function):
+    """_GroupedConvTo1 on relu(h + hact) with the class branches' act term hact formed inside the kernels: h [M, G*128] is
+    the first conv on the feature channels, stored before its ReLU; act [M, K] holds class g in column col0 + g; e [G, 9, 128]
+    is each class's act-column weight.  One node: the backward returns dh (the gradient of h, already masked by the ReLU),
+    dw, db, d act and de."""
+
+    @staticmethod
+    def forward(ctx, h, w, bias, act, e, shape, G, col0):
+        _chk(h, bias, act, e)
+        gc = G * 128
+        assert h.shape == (shape.rows, gc) and tuple(w.shape) == (G, gc, 3, 3) and w.permute(0, 2, 3, 1).is_contiguous()
+        assert act.shape[0] == shape.rows and act.shape[1] >= col0 + G and act.is_contiguous(), (act.shape, col0, G)
+        assert tuple(e.shape) == (G, 9, 128) and e.is_contiguous() and h.is_contiguous()
+        if not cls_split_supported(G):
+            raise RuntimeError("gconv3x3_to1_act: G=%d on the fp32 FMA kernels only (G in 1, 2, 4, 8; gconv_mfma = 0)" % G)
+        ns = pad4(G)
+        y = h.new_empty((shape.rows, ns))
+        ws = h.new_empty((query("scan_gconv3x3_to1_act_ws_floats", shape.ref(), G, 128),))
+        call("scan_gconv3x3_to1_act_forward", _ptr(h), shape.ref(), G, 128, _ptr(w), _ptr(bias), _ptr(act), act.shape[1], col0,
+             _ptr(e), _ptr(y), ns, _ptr(ws), _stream())
+        ctx.save_for_backward(h, w, act, e)
+        ctx.cfg = (shape, G, ns, col0, bias is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        h, w, act, e = ctx.saved_tensors
+        shape, G, ns, col0, has_bias = ctx.cfg
+        dy = dy.contiguous()
+        st = _stream()
+        K = act.shape[1]
+        ws = h.new_empty((query("scan_gconv3x3_to1_act_ws_floats", shape.ref(), G, 128),))
+        dwp = h.new_zeros((G, 9, G * 128))  # off-diagonal blocks: exact zeros (they meet a zero in the adjoint)
+        dh = torch.empty_like(h)
+        want_act = ctx.needs_input_grad[3] or ctx.needs_input_grad[4]
+        fused = CLS_SPLIT_FUSED and want_act
+        if fused:  # d act and de from dh while it is in registers: no second pass over dh
+            dact, de = torch.empty_like(act), torch.empty_like(e)
+            call("scan_gconv3x3_to1_act_backward_all", _ptr(h), _ptr(dy), ns, shape.ref(), G, 128, _ptr(w), _ptr(act), K, col0,
+                 _ptr(e), _ptr(dh), _ptr(dwp), _ptr(dact), K, col0, _ptr(de), 0, _ptr(ws), st)
+        else:
+            call("scan_gconv3x3_to1_act_backward", _ptr(h), _ptr(dy), ns, shape.ref(), G, 128, _ptr(w), _ptr(act), K, col0,
+                 _ptr(e), _ptr(dh), _ptr(dwp), 0, _ptr(ws), st)
+        dw = dwp.view(G, 3, 3, G * 128).permute(0, 3, 1, 2) if ctx.needs_input_grad[1] else None
+        db = None
+        if not fused:
+            dact = de = None
+        if has_bias and ctx.needs_input_grad[2]:
+            M = dy.shape[0]
+            cws = h.new_empty((query("scan_colsum_ws_floats", M, G),))
+            db = h.new_empty((G,))
+            call("scan_colsum", _ptr(dy), M, G, ns, _ptr(db), 0, _ptr(cws), st)
+        if want_act and not fused:
+            dact = torch.empty_like(act)
+            de = torch.empty_like(e)
+            call("scan_gconv3x3_to1_act_grads", _ptr(dh), shape.ref(), G, 128, _ptr(act), K, col0, _ptr(e), _ptr(dact), K, col0,
+                 _ptr(de), 0, _ptr(ws), st)
+        dact = dact if ctx.needs_input_grad[3] else None
+        de = de if ctx.needs_input_grad[4] else None
+        return (dh if ctx.needs_input_grad[0] else None), dw, db, dact, de, None, None, None
+
+
+def gconv3x3_to1_act(h, w, bias, act, e, shape, G, col0=1):
+    """y[:, g] = conv3x3(relu(h + hact)[:, g*128:(g+1)*128], w[g, g*128:(g+1)*128]) + bias[g] -> [M, pad4(G)], with
+    hact[p, g*128 + i] = sum_t e[g, t, i] * act[nb(p, t), col0 + g] (zero outside the image)."""
+    return _GroupedConvTo1Act.apply(h, w, bias, act.contiguous(), e, shape, int(G), int(col0))
+
+
 # ----------------------------------------------------------------------------- optimizer
 # SCAN_COND_RNN=0: the conditioned-kernel generator (paradigm -> 2-layer tanh RNN -> (T, 1) conv) runs as the torch loop it is
 # written as in modeling/condgraph.py (T x 2 x (2 linear + add + tanh), ~120 launches with its backward) instead of the

@@ -30,6 +30,7 @@ SHAPES = [
     ("conv1_2 64->64 @1024x2048, 4 frames", 4, [(1024, 2048)], 64, 64),
     ("conv2_1 64->128 @512x1024, 4 frames", 4, [(512, 1024)], 64, 128),
     ("dis P3 264->1024, 4 frames", 4, [(128, 256)], 264, 1024),
+    ("dis P3 256->1024, 4 frames (CLS_SPLIT)", 4, [(128, 256)], 256, 1024),  # the act channels left to the grouped conv
     ("head_out 268->256 pyramid, 4 frames", 4, [(128, 256), (64, 128), (32, 64), (16, 32), (8, 16)], 268, 256),
 ]
 
