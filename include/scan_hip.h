@@ -218,7 +218,8 @@ int scan_softmax_focal_forward_ordered(const float* logits, const int64_t* label
                                        float* loss_sum, float* ws, void* stream);
 
 /* ---- y = alpha * x  (GradientReversalFunction: forward alpha = 1 copy, backward alpha = -lambda;
- *      discriminator/layer.py:6-24) ---- */
+ *      discriminator/layer.py:6-24).  x and y are flat fp32 ranges with any 4-byte alignment (a level's rows of an [M, 9]
+ *      matrix); y == x is allowed.  Both 16-byte aligned: the float4 kernel; otherwise one float per lane, the same bits. ---- */
 int scan_scale(const float* x, float alpha, float* y, int64_t n, void* stream);
 /* dst[r][c] = src[r][c] for c < ncols, zeros for ncols <= c < ncols + ztail; row pitches ld_src / ld_dst in floats (callers
  * offset the pointers to the first column).  Replaces the torch-tier spellings of F.pad(act_maps, (0, 3)) in front of head_out's
@@ -510,7 +511,8 @@ int scan_weight_transpose(const float* w, int32_t Cout, int32_t T, int32_t Cin_s
 int64_t scan_colsum_ws_floats(int64_t M, int32_t C);
 int scan_colsum(const float* dy, int64_t M, int32_t C, int32_t ld, float* db, int32_t accumulate, float* ws,
                 void* stream);
-/* out = dy * (y > 0)   (ReLU backward; y is the ReLU output; out may alias dy) */
+/* out = dy * (y > 0)   (ReLU backward; y is the ReLU output; out may alias dy).  Any 4-byte alignment: the float4 kernel when
+ * all three pointers are 16-byte aligned, otherwise one float per lane, the same bits. */
 int scan_relu_backward(const float* dy, const float* y, float* out, int64_t n, void* stream);
 
 /* ---- GroupNorm(32 groups) + ReLU on a pyramid (replaces nn.GroupNorm(32,C)+nn.ReLU in the towers,
@@ -669,7 +671,8 @@ int scan_atss_giou_backward(const scan_pyramid_t* d, const int32_t* strides, con
 /* ---- FPN top-down join on NHWC rows (reference backbone/fpn.py:62-75: inner = lateral + F.interpolate(top,
  *      scale_factor=2, mode="nearest")).  lat / y [N, 2h, 2w, C], coarse [N, h, w, C], C % 4 == 0.  Backward:
  *      d_lateral is the incoming gradient itself, d_coarse its 2x2 window sums (scan_downsample2x_sum: g [N, 2h, 2w, C]
- *      -> d [N, h, w, C]). ---- */
+ *      -> d [N, h, w, C]).  Every pointer 16-byte aligned (float4 rows); a misaligned one is an argument error naming it,
+ *      nothing is launched. ---- */
 int scan_upsample2x_add(const float* lat, const float* coarse, int32_t N, int32_t h, int32_t w, int32_t C, float* y,
                         void* stream);
 int scan_downsample2x_sum(const float* g, int32_t N, int32_t h, int32_t w, int32_t C, float* d, void* stream);
@@ -678,7 +681,8 @@ int scan_downsample2x_sum(const float* g, int32_t N, int32_t h, int32_t w, int32
  *      backbone/mmdetection/vgg.py:33).  x [N,H,W,C], y [N,H/2,W/2,C]; H, W even, C % 4 == 0.
  *      backward routes the gradient to the first maximum of each window (F.max_pool2d's rule);
  *      relu_mask != 0 additionally zeroes it where that maximum is <= 0 (x is a ReLU output whose own
- *      backward was left to its consumers, see scan_conv3x3_bf16x3's mask). ---- */
+ *      backward was left to its consumers, see scan_conv3x3_bf16x3's mask).  Every pointer 16-byte aligned; a misaligned
+ *      one is an argument error, nothing is launched. ---- */
 int scan_maxpool2x2_forward(const float* x, int32_t N, int32_t H, int32_t W, int32_t C, float* y, void* stream);
 int scan_maxpool2x2_backward(const float* x, const float* y, const float* dy, int32_t N, int32_t H, int32_t W,
                              int32_t C, float* dx, int32_t relu_mask, void* stream);
@@ -687,7 +691,9 @@ int scan_maxpool2x2_backward(const float* x, const float* y, const float* dy, in
  *      (:335; forward only -- the stem is frozen for FREEZE_CONV_BODY_AT >= 1), y [N,(H-1)/2+1,(W-1)/2+1,C], C % 4 == 0;
  *      and the residual join y = max(a + b, 0) (:312-313; backward = scan_relu_backward(dy, y) to both branches).
  *      FrozenBatchNorm2d (layers/batch_norm.py:5-24) is an affine per channel and is folded into the conv weights /
- *      bias by the host side. ---- */
+ *      bias by the host side.  The pool's x and y must be 16-byte aligned (an argument error otherwise); add_relu takes flat
+ *      ranges with any 4-byte alignment: the float4 kernel when a, b and y are 16-byte aligned, otherwise one float per lane,
+ *      the same bits. ---- */
 int scan_maxpool3x3s2_forward(const float* x, int32_t N, int32_t H, int32_t W, int32_t C, float* y, void* stream);
 int scan_add_relu(const float* a, const float* b, float* y, int64_t n, void* stream);
 

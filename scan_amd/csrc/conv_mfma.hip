@@ -412,6 +412,12 @@ __global__ void relu_bwd_kernel(const float* dy, const float* __restrict__ y, fl
     for (int64_t i = n4 << 2; i < n; ++i) out[i] = y[i] > 0.f ? dy[i] : 0.f;
 }
 
+// the same select, one float per lane: for pointers that are not 16-byte aligned
+__global__ void relu_bwd_scalar_kernel(const float* dy, const float* __restrict__ y, float* out, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    out[i] = y[i] > 0.f ? dy[i] : 0.f;
+}
+
 // ------------------------------------------------------------------------------------------ C ABI
 static int check_pyr(const scan_pyramid_t* d, const char* who) {
   SCAN_CHECK_ARG(d != nullptr, "%s: null pyramid", who);
@@ -610,7 +616,10 @@ extern "C" int scan_weight_transpose(const float* w, int32_t Cout, int32_t T, in
 extern "C" int scan_relu_backward(const float* dy, const float* y, float* out, int64_t n, void* stream) {
   SCAN_CHECK_ARG(dy && y && out && n >= 0, "relu_backward: bad arguments");
   if (n == 0) return 0;
-  hipLaunchKernelGGL(relu_bwd_kernel, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, as_stream(stream), dy, y, out, n);
+  if (((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(out)) & 15) == 0)
+    hipLaunchKernelGGL(relu_bwd_kernel, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, as_stream(stream), dy, y, out, n);
+  else
+    hipLaunchKernelGGL(relu_bwd_scalar_kernel, dim3(grid_for(n, 256)), dim3(256), 0, as_stream(stream), dy, y, out, n);
   SCAN_LAUNCH_CHECK("relu_bwd");
   return 0;
 }

@@ -7,6 +7,11 @@
 #include "common.h"
 #include <algorithm>
 
+// The float4 kernels below need 16-byte aligned pointers.  The flat ones (scale, add_relu) are handed row ranges of matrices
+// with any column count and pick a scalar kernel when a pointer is not; the NHWC ones take fresh allocations with C % 4 == 0
+// and reject anything else.
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 // ------------------------------------------------------------------ y = alpha * x (GRL)
 __global__ __launch_bounds__(256) void scale_kernel(const float* __restrict__ x, float alpha, float* __restrict__ y,
                                                     int64_t n) {
@@ -19,11 +24,21 @@ __global__ __launch_bounds__(256) void scale_kernel(const float* __restrict__ x,
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) y[(n4 << 2) + threadIdx.x] = alpha * x[(n4 << 2) + threadIdx.x];
 }
 
+// the same multiply, one float per lane: for pointers that are not 16-byte aligned (a level's rows of an [M, 9] matrix)
+__global__ __launch_bounds__(256) void scale_scalar_kernel(const float* __restrict__ x, float alpha, float* __restrict__ y,
+                                                           int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    y[i] = alpha * x[i];
+}
+
 extern "C" int scan_scale(const float* x, float alpha, float* y, int64_t n, void* stream) {
   SCAN_CHECK_ARG(n >= 0, "scale: bad n");
   if (n == 0) return 0;
   SCAN_CHECK_ARG(x && y, "scale: null pointer");
-  hipLaunchKernelGGL(scale_kernel, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, as_stream(stream), x, alpha, y, n);
+  if (aligned16(x) && aligned16(y))
+    hipLaunchKernelGGL(scale_kernel, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, as_stream(stream), x, alpha, y, n);
+  else
+    hipLaunchKernelGGL(scale_scalar_kernel, dim3(grid_for(n, 256)), dim3(256), 0, as_stream(stream), x, alpha, y, n);
   SCAN_LAUNCH_CHECK("scale");
   return 0;
 }
@@ -128,6 +143,7 @@ extern "C" int scan_maxpool2x2_forward(const float* x, int32_t N, int32_t H, int
                                        void* stream) {
   SCAN_CHECK_ARG(x && y && N > 0 && H > 0 && W > 0 && C > 0, "maxpool2x2_forward: bad arguments");
   SCAN_CHECK_ARG((H & 1) == 0 && (W & 1) == 0 && (C & 3) == 0, "maxpool2x2_forward: H, W must be even and C %% 4 == 0");
+  SCAN_CHECK_ARG(aligned16(x) && aligned16(y), "maxpool2x2_forward: x and y must be 16-byte aligned");
   const int64_t total = (int64_t)N * (H / 2) * (W / 2) * (C / 4);
   hipLaunchKernelGGL(maxpool2_fwd_kernel, dim3(grid_for(total, 256)), dim3(256), 0, as_stream(stream), x, N, H, W, C, y);
   SCAN_LAUNCH_CHECK("maxpool2_fwd");
@@ -138,6 +154,8 @@ extern "C" int scan_maxpool2x2_backward(const float* x, const float* y, const fl
                                         int32_t W, int32_t C, float* dx, int32_t relu_mask, void* stream) {
   SCAN_CHECK_ARG(x && y && dy && dx && N > 0 && H > 0 && W > 0 && C > 0, "maxpool2x2_backward: bad arguments");
   SCAN_CHECK_ARG((H & 1) == 0 && (W & 1) == 0 && (C & 3) == 0, "maxpool2x2_backward: H, W must be even and C %% 4 == 0");
+  SCAN_CHECK_ARG(aligned16(x) && aligned16(y) && aligned16(dy) && aligned16(dx),
+                 "maxpool2x2_backward: x, y, dy and dx must be 16-byte aligned");
   const int64_t total = (int64_t)N * (H / 2) * (W / 2) * (C / 4);
   hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(grid_for(total, 256)), dim3(256), 0, as_stream(stream), x, y, dy, N, H, W,
                      C, dx, relu_mask);
@@ -183,6 +201,7 @@ extern "C" int scan_maxpool3x3s2_forward(const float* x, int32_t N, int32_t H, i
                                          void* stream) {
   SCAN_CHECK_ARG(x && y && N > 0 && H > 0 && W > 0 && C > 0 && (C & 3) == 0,
                  "maxpool3x3s2_forward: bad arguments (C %% 4 == 0 required)");
+  SCAN_CHECK_ARG(aligned16(x) && aligned16(y), "maxpool3x3s2_forward: x and y must be 16-byte aligned");
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
   const int64_t total = (int64_t)N * Ho * Wo * (C / 4);
   hipLaunchKernelGGL(maxpool3s2_fwd_kernel, dim3(grid_for(total, 256)), dim3(256), 0, as_stream(stream), x, N, H, W, C,
@@ -209,10 +228,19 @@ __global__ __launch_bounds__(256) void add_relu_kernel(const float* __restrict__
     for (int64_t i = n4 << 2; i < n; ++i) y[i] = fmaxf(a[i] + b[i], 0.f);
 }
 
+__global__ __launch_bounds__(256) void add_relu_scalar_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                              float* __restrict__ y, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    y[i] = fmaxf(a[i] + b[i], 0.f);
+}
+
 extern "C" int scan_add_relu(const float* a, const float* b, float* y, int64_t n, void* stream) {
   SCAN_CHECK_ARG(a && b && y && n >= 0, "add_relu: bad arguments");
   if (n == 0) return 0;
-  hipLaunchKernelGGL(add_relu_kernel, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, as_stream(stream), a, b, y, n);
+  if (aligned16(a) && aligned16(b) && aligned16(y))
+    hipLaunchKernelGGL(add_relu_kernel, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, as_stream(stream), a, b, y, n);
+  else  // a pointer that is not 16-byte aligned: the same add and max, one float per lane
+    hipLaunchKernelGGL(add_relu_scalar_kernel, dim3(grid_for(n, 256)), dim3(256), 0, as_stream(stream), a, b, y, n);
   SCAN_LAUNCH_CHECK("add_relu");
   return 0;
 }
@@ -260,6 +288,7 @@ extern "C" int scan_upsample2x_add(const float* lat, const float* coarse, int32_
                                    float* y, void* stream) {
   SCAN_CHECK_ARG(lat && coarse && y && N >= 1 && h >= 1 && w >= 1 && C >= 4 && C % 4 == 0,
                  "upsample2x_add: bad arguments (C=%d must be a multiple of 4)", C);
+  SCAN_CHECK_ARG(aligned16(lat) && aligned16(coarse) && aligned16(y), "upsample2x_add: lat, coarse and y must be 16-byte aligned");
   const int64_t n4 = (int64_t)N * 4 * h * w * (C / 4);
   hipLaunchKernelGGL(upsample2x_add_kernel, dim3(grid_for(n4, 256)), dim3(256), 0, as_stream(stream), lat, coarse, N, h, w,
                      C / 4, y);
@@ -270,6 +299,7 @@ extern "C" int scan_upsample2x_add(const float* lat, const float* coarse, int32_
 extern "C" int scan_downsample2x_sum(const float* g, int32_t N, int32_t h, int32_t w, int32_t C, float* d, void* stream) {
   SCAN_CHECK_ARG(g && d && N >= 1 && h >= 1 && w >= 1 && C >= 4 && C % 4 == 0,
                  "downsample2x_sum: bad arguments (C=%d must be a multiple of 4)", C);
+  SCAN_CHECK_ARG(aligned16(g) && aligned16(d), "downsample2x_sum: g and d must be 16-byte aligned");
   const int64_t n4 = (int64_t)N * h * w * (C / 4);
   hipLaunchKernelGGL(downsample2x_sum_kernel, dim3(grid_for(n4, 256)), dim3(256), 0, as_stream(stream), g, N, h, w, C / 4, d);
   SCAN_LAUNCH_CHECK("downsample2x_sum");
