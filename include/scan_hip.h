@@ -814,6 +814,14 @@ int scan_gconv3x3_to1_backward(const float* x, const float* dy, int32_t Ns, cons
  * of the entry points above, every other G generic ones (one 32-lane half-wave per (pixel, group), plain fp32 FMA,
  * deterministic weight gradient).  Workspace: scan_gconv3x3_to1_ws_floats. */
 int32_t scan_gconv3x3_to1_max_groups(void);
+/* What (G, Cg) would get right now: 0 for everything the entry points refuse, else a set of the bits below.  Reads the
+ * "gconv_mfma" knob, writes nothing. */
+#define SCAN_GCONV_RUNS 1        /* the _any_ entry points take it */
+#define SCAN_GCONV_LANE_MAPPED 2 /* G = 1, 2, 4, 8: the entry points without "any", the _bits and the _act_ ones take it too */
+#define SCAN_GCONV_BITS 4        /* lane-mapped and gconv_mfma = 1: forward / backward run the matrix-core kernels, which the
+                                    bit mask of _forward_bits / _backward_bits serves */
+#define SCAN_GCONV_ACT 8         /* lane-mapped and gconv_mfma = 0: the act-term kernels continue the fp32 FMA path */
+int32_t scan_gconv3x3_to1_caps(int32_t G, int32_t Cg);
 int scan_gconv3x3_to1_any_forward(const float* x, const scan_pyramid_t* d, int32_t G, int32_t Cg, const float* w,
                                   const float* bias, float* y, int32_t Ns, float* ws, void* stream);
 int scan_gconv3x3_to1_any_dgrad(const float* dy, int32_t Ns, const scan_pyramid_t* d, int32_t G, int32_t Cg, const float* w,

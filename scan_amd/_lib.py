@@ -212,6 +212,7 @@ SIGNATURES = {
                                               c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
     "scan_gconv3x3_to1_ws_floats": (c_i64, [_PD, c_i32, c_i32]),
     "scan_gconv3x3_to1_max_groups": (c_i32, []),
+    "scan_gconv3x3_to1_caps": (c_i32, [c_i32, c_i32]),
     "scan_gconv3x3_to1_any_forward": (ctypes.c_int, [c_vp, _PD, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "scan_gconv3x3_to1_any_dgrad": (ctypes.c_int, [c_vp, c_i32, _PD, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "scan_gconv3x3_to1_any_wgrad": (ctypes.c_int, [c_vp, c_vp, c_i32, _PD, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp]),

@@ -1820,6 +1820,9 @@ def cka_stacked_weights(branches, C, H, cs1):
     return _CkaStackedWeights.apply(int(C), int(H), int(cs1), *params)
 
 
+GCONV_BITS, GCONV_ACT = 4, 8  # SCAN_GCONV_BITS / _ACT of scan_gconv3x3_to1_caps: what the library runs for a G right now
+
+
 class _GroupedConvTo1(torch.autograd.Function):
     """conv3x3 [M, G*128] -> [M, Ns >= G], one output channel per group of 128 (the class branches' second conv);
     w = the stacked weight [G, G*128, 3, 3] (channels-last) whose diagonal blocks are the per-class weights.
@@ -1835,15 +1838,13 @@ class _GroupedConvTo1(torch.autograd.Function):
         y = x.new_empty((shape.rows, ns))
         ws = x.new_empty((query("scan_gconv3x3_to1_ws_floats", shape.ref(), G, 128),))
         bits = None
-        mfma = query("scan_tune_get", b"gconv_mfma")  # read-only: no write to the launch-selection state
-        # the matrix-core / bit-mask kernels exist for G = 1, 2, 4, 8 only
-        any_ = "" if G in (1, 2, 4, 8) else "any_"  # the scan_gconv3x3_to1_any_* entry points take every G up to gconv_max_groups()
-        if mfma == 1 and not any_ and mask_dx and torch.is_grad_enabled() and x.requires_grad:
+        # the bit mask serves the matrix-core kernels: only where the library would run those
+        if query("scan_gconv3x3_to1_caps", G, 128) & GCONV_BITS and mask_dx and torch.is_grad_enabled() and x.requires_grad:
             bits = torch.empty((shape.rows * G * 4,), dtype=torch.int32, device=x.device)
             call("scan_gconv3x3_to1_forward_bits", _ptr(x), shape.ref(), G, 128, _ptr(w), _ptr(bias), _ptr(y), ns,
                  _ptr(ws), _ptr(bits), _stream())
         else:
-            call("scan_gconv3x3_to1_%sforward" % any_, _ptr(x), shape.ref(), G, 128, _ptr(w), _ptr(bias), _ptr(y), ns, _ptr(ws),
+            call("scan_gconv3x3_to1_any_forward", _ptr(x), shape.ref(), G, 128, _ptr(w), _ptr(bias), _ptr(y), ns, _ptr(ws),
                  _stream())
         ctx.save_for_backward(x, w, bits)
         ctx.cfg = (shape, G, ns, mask_dx, bias is not None)
@@ -1853,7 +1854,6 @@ class _GroupedConvTo1(torch.autograd.Function):
     def backward(ctx, dy):
         x, w, bits = ctx.saved_tensors
         shape, G, ns, mask_dx, has_bias = ctx.cfg
-        any_ = "" if G in (1, 2, 4, 8) else "any_"
         dy = dy.contiguous()
         st = _stream()
         dx = dw = db = dwp = None
@@ -1867,13 +1867,13 @@ class _GroupedConvTo1(torch.autograd.Function):
             call("scan_gconv3x3_to1_backward_bits", _ptr(x), _ptr(dy), ns, shape.ref(), G, 128, _ptr(w), _ptr(bits),
                  _ptr(dx), _ptr(dwp), 0, _ptr(ws), st)
         elif dx is not None and dwp is not None:
-            call("scan_gconv3x3_to1_%sbackward" % any_, _ptr(x), _ptr(dy), ns, shape.ref(), G, 128, _ptr(w), int(mask_dx), _ptr(dx),
+            call("scan_gconv3x3_to1_any_backward", _ptr(x), _ptr(dy), ns, shape.ref(), G, 128, _ptr(w), int(mask_dx), _ptr(dx),
                  _ptr(dwp), 0, _ptr(ws), st)
         elif dx is not None:
-            call("scan_gconv3x3_to1_%sdgrad" % any_, _ptr(dy), ns, shape.ref(), G, 128, _ptr(w), _ptr(x if mask_dx else None),
+            call("scan_gconv3x3_to1_any_dgrad", _ptr(dy), ns, shape.ref(), G, 128, _ptr(w), _ptr(x if mask_dx else None),
                  _ptr(dx), st)
         elif dwp is not None:
-            call("scan_gconv3x3_to1_%swgrad" % any_, _ptr(x), _ptr(dy), ns, shape.ref(), G, 128, _ptr(dwp), 0, _ptr(ws), st)
+            call("scan_gconv3x3_to1_any_wgrad", _ptr(x), _ptr(dy), ns, shape.ref(), G, 128, _ptr(dwp), 0, _ptr(ws), st)
         if has_bias and ctx.needs_input_grad[2]:
             M = dy.shape[0]
             cws = x.new_empty((query("scan_colsum_ws_floats", M, G),))
@@ -1910,7 +1910,7 @@ CLS_SPLIT_FUSED = os.environ.get("SCAN_CLS_SPLIT_FUSED", "1") != "0"
 
 def cls_split_supported(G):
     """the act-term kernels exist for the lane-mapped class counts on the fp32 FMA gconv path"""
-    return G in (1, 2, 4, 8) and query("scan_tune_get", b"gconv_mfma") == 0
+    return bool(query("scan_gconv3x3_to1_caps", int(G), 128) & GCONV_ACT)
 
 
 class _CkaStackedWeightsSplit(torch.autograd.Function):

@@ -42,3 +42,31 @@ def test_class_count_limits_are_declared_and_exported():
     for K in (1, 33):
         with pytest.raises(RuntimeError, match=r"only K in 2\.\.32 is built \(got %d\)" % K):
             _lib.call("scan_dynconv_softmax_forward", None, None, 10, 256, K, None, None, None)
+
+
+def test_gconv_caps_follow_the_group_count_and_the_knob():
+    """scan_gconv3x3_to1_caps: 0 for what the entry points refuse, else runnable (1) | lane-mapped (2, G in 1, 2, 4, 8) |
+    bit-mask forward / backward taken now (4, lane-mapped and gconv_mfma = 1) | act-term kernels available now (8,
+    lane-mapped and gconv_mfma = 0); the knob is read and left alone"""
+    hdr = open(os.path.join(ROOT, "include", "scan_hip.h")).read()
+    assert re.search(r"int32_t\s+scan_gconv3x3_to1_caps\(int32_t G, int32_t Cg\);", hdr)
+    for name, bit in (("RUNS", 1), ("LANE_MAPPED", 2), ("BITS", 4), ("ACT", 8)):
+        assert re.search(r"#define\s+SCAN_GCONV_%s\s+%d\b" % (name, bit), hdr), name
+    from scan_amd import _lib, ops
+    assert (ops.GCONV_BITS, ops.GCONV_ACT) == (4, 8)
+    gmax = _lib.query("scan_gconv3x3_to1_max_groups")
+    old = _lib.query("scan_tune_get", b"gconv_mfma")
+    try:
+        for knob in (0, 1):
+            _lib.query("scan_tune", b"gconv_mfma", knob)
+            for G in range(0, 33):
+                want = 0
+                if 1 <= G <= gmax:
+                    want = 1 | ((2 | (4 if knob == 1 else 8)) if G in (1, 2, 4, 8) else 0)
+                assert _lib.query("scan_gconv3x3_to1_caps", G, 128) == want, (knob, G)
+                assert bool(_lib.query("scan_gconv3x3_to1_caps", G, 128) & 1) == (1 <= G <= gmax)
+                assert ops.cls_split_supported(G) == (G in (1, 2, 4, 8) and knob == 0)
+            assert _lib.query("scan_gconv3x3_to1_caps", 2, 64) == 0
+            assert _lib.query("scan_tune_get", b"gconv_mfma") == knob
+    finally:
+        _lib.query("scan_tune", b"gconv_mfma", old)

@@ -46,3 +46,14 @@ def test_new_entry_points_are_declared_and_exported():
                  "scan_gconv3x3_to1_act_forward", "scan_gconv3x3_to1_act_backward", "scan_gconv3x3_to1_act_grads",
                  "scan_gconv3x3_to1_act_backward_all"):
         assert name + "(" in hdr and name in _lib.SIGNATURES and hasattr(L, name), name
+
+
+def test_gconv_workspace_sizes():
+    """tap sums [M][G][9]; a slab = 1024 partials + 32 run sums of 9 * G * 128.  The plain entry points use one or the other,
+    scan_gconv3x3_to1_act_backward_all the tap sums and two slabs at once."""
+    slab = 1056 * 9 * 128
+    for shape in (ops.PyramidShape(2, [(17, 17)]), ops.PyramidShape(2, [(5, 7), (3, 4)]), ROWS):
+        M = shape.rows
+        for G in (1, 8, 31):
+            assert _lib.query("scan_gconv3x3_to1_ws_floats", shape.ref(), G, 128) == max(9 * M * G, slab * G), (M, G)
+            assert _lib.query("scan_gconv3x3_to1_act_ws_floats", shape.ref(), G, 128) == 9 * M * G + 2 * slab * G, (M, G)
