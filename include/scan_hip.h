@@ -242,7 +242,8 @@ int scan_dynconv_softmax_forward(const float* feat, const float* kernels, int64_
                                  float* logits, float* probs, void* stream);
 /* d_logits_in [M,K] or NULL (grad arriving at the logits, e.g. from the act loss), d_probs [M,K] or NULL.
  * Writes d_feat [M,C] (overwrites) and d_kernels [K,C] (overwrites; uses ws of size >= grid*K*C floats,
- * see scan_dynconv_ws_floats). */
+ * see scan_dynconv_ws_floats).  M == 0 is legal in both directions: the forward launches nothing, the backward only clears
+ * d_kernels (the other pointers are not looked at). */
 int64_t scan_dynconv_ws_floats(int64_t M, int32_t C, int32_t K);
 int scan_dynconv_softmax_backward(const float* feat, const float* kernels, const float* probs,
                                   const float* d_logits_in, const float* d_probs, int64_t M, int32_t C,

@@ -344,7 +344,15 @@ extern "C" int scan_dynconv_softmax_backward(const float* feat, const float* ker
                                              int32_t K, float* d_feat, float* d_kernels, float* ws, void* stream) {
   SCAN_CHECK_ARG(C == DC_C, "dynconv_softmax_backward: only C=256 is built (got %d)", C);
   SCAN_CHECK_ARG(K >= 2 && K <= DC_KMAX, "dynconv_softmax_backward: only K in 2..%d is built (got %d)", DC_KMAX, K);
-  SCAN_CHECK_ARG(M > 0, "dynconv_softmax_backward: M must be positive");
+  SCAN_CHECK_ARG(M >= 0, "dynconv_softmax_backward: bad M");
+  if (M == 0) {  // as the forward: no rows, no launch; the sum over no rows is zero
+    SCAN_CHECK_ARG(d_kernels, "dynconv_softmax_backward: null pointer (d_kernels [K,256])");
+    if (hipMemsetAsync(d_kernels, 0, sizeof(float) * K * C, as_stream(stream)) != hipSuccess) {
+      scan_set_error("dynconv_softmax_backward: memset failed");
+      return -2;
+    }
+    return 0;
+  }
   SCAN_CHECK_ARG(feat && kernels && probs && d_feat && d_kernels && ws, "dynconv_softmax_backward: null pointer");
   const int nb = dc_bwd_blocks(M);
   hipStream_t st = as_stream(stream);
