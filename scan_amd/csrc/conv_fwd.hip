@@ -92,6 +92,14 @@ __device__ __forceinline__ void mma_pieces(const bf16x8 (&w)[NP], const bf16x8 (
       for (int tm = 0; tm < TM; ++tm) acc[tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[i], p[s - i][tm], acc[tm], 0, 0, 0);
 }
 
+// GroupNorm sums of a pixel's four stored channels: every element enters both sums as a double (a square rounded to fp32
+// costs the variance a relative (mean / std)^2 * 2^-24), the same for every instance
+__device__ __forceinline__ void gn_sums_add(const float4 o, double& ds, double& dq) {
+  const double o0 = (double)o.x, o1 = (double)o.y, o2 = (double)o.z, o3 = (double)o.w;
+  ds += (o0 + o1) + (o2 + o3);
+  dq += (o0 * o0 + o1 * o1) + (o2 * o2 + o3 * o3);
+}
+
 // NP: pieces per operand; BN: output channels per workgroup; TH: tile rows (tile = TH x 16 pixels); NT: threads; KS: 3 or 1.
 // KS = 1 also serves the stride-2 1x1 convs through MAP (0: same pyramid; 1: source = 2 * output, forward of a stride-2
 // conv; 2: source = output / 2 on even coordinates, zero elsewhere: its data gradient).
@@ -717,8 +725,7 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
               o.w = (mk[tm][e].w > 0.f) ? o.w : 0.f;
             }
             *reinterpret_cast<float4*>(dst + (rowbase + (int64_t)y * W + xw + e) * Ns + o4) = o;
-            ds += (double)((o.x + o.y) + (o.z + o.w));
-            dq += (double)((o.x * o.x + o.y * o.y) + (o.z * o.z + o.w * o.w));
+            if (gn_ws != nullptr) gn_sums_add(o, ds, dq);
           }
         }
       }
@@ -773,7 +780,7 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
                     : make_float4(0.f, 0.f, 0.f, 0.f);
       }
     }
-    double ds = 0.0, dq = 0.0;  // fp32 over a pixel's four channels, fp64 from there on: the same for every instance
+    double ds = 0.0, dq = 0.0;  // fp64 from the element on (gn_sums_add): the same for every instance
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm) {
       const int y = ty0 + ewm * TM + tm;
@@ -793,8 +800,7 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
           o.w = (mk[tm].w > 0.f) ? o.w : 0.f;
         }
         *reinterpret_cast<float4*>(dst + (rowbase + (int64_t)y * W + x) * Ns + o4) = o;
-        ds += (double)((o.x + o.y) + (o.z + o.w));
-        dq += (double)((o.x * o.x + o.y * o.y) + (o.z * o.z + o.w * o.w));
+        if (gn_ws != nullptr) gn_sums_add(o, ds, dq);
       }
     }
     if (gn_ws != nullptr) {

@@ -249,7 +249,7 @@ __global__ __launch_bounds__(NT, NT == 512 ? 2 : 3) void conv3x3_bf16x3_kernel(
   for (int tn = 0; tn < TN; ++tn) {
     const int o = n0 + wn * 32 * TN + tn * 32 + lr;
     const float bv = (bias != nullptr && o < Nout) ? bias[o] : 0.f;
-    float gs = 0.f, gq = 0.f;
+    double gs = 0.0, gq = 0.0;  // every element enters both GroupNorm sums as a double (see gn_sums_add, conv_fwd.hip)
     if (relu & 2) {
       // fused 2x2 / stride-2 max-pool (frozen VGG stages, single-level pyramid): a window's four pixels are the
       // registers r, r+1 (x, x+1) and r+8, r+9 (next row) of ONE lane, so the pooled tensor is written directly and
@@ -294,15 +294,17 @@ __global__ __launch_bounds__(NT, NT == 512 ? 2 : 3) void conv3x3_bf16x3_kernel(
           if (relu & 1) v = fmaxf(v, 0.f);
           if (mask != nullptr) v = (mk[r] > 0.f) ? v : 0.f;
           dst[m * Ns + o] = v;
-          gs += v;
-          gq += v * v;
+          if (gn_ws != nullptr) {
+            gs += (double)v;
+            gq += (double)v * (double)v;
+          }
         }
       }
     }
     if (gn_ws != nullptr) {
       // GroupNorm(32) statistics of the 256-channel output this conv feeds: sum / sum of squares per (level, image,
       // group of 8 channels = 8 adjacent lanes, both lane halves), one fp64 atomic pair per group and wave
-      double ds = (double)gs, dq = (double)gq;
+      double ds = gs, dq = gq;
 #pragma unroll
       for (int sh = 1; sh <= 4; sh <<= 1) {
         ds += __shfl_xor(ds, sh, 64);

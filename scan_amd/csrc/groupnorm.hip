@@ -70,8 +70,11 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__
                                   : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      s += (double)((v[u].x + v[u].y) + (v[u].z + v[u].w));
-      q += (double)((v[u].x * v[u].x + v[u].y * v[u].y) + (v[u].z * v[u].z + v[u].w * v[u].w));
+      // every element is widened before it is added or squared: a square rounded to fp32 costs the variance a relative
+      // (mean / std)^2 * 2^-24, and overflows from |x| = 1.8e19
+      const double x0 = (double)v[u].x, x1 = (double)v[u].y, x2 = (double)v[u].z, x3 = (double)v[u].w;
+      s += (x0 + x1) + (x2 + x3);
+      q += (x0 * x0 + x1 * x1) + (x2 * x2 + x3 * x3);
     }
   }
   // 8 channels per group = 2 adjacent lanes

@@ -175,8 +175,9 @@ def test_conv3x3_groupnorm_sums_clear_then_accumulate(device, pieces):
         print("sums: pass %d, largest difference %.3e, smallest bound %.3e" % (passes, float(diff.max()),
                                                                                  float(_sums_bound(y, d, passes).min())))
         assert bool((diff <= _sums_bound(y, d, passes)).all())
-    # and they are the sums: (level 0, image 0) holds twice one pass over its 240 pixels.  The epilogue adds the four channels a
-    # lane holds (and their squares) in fp32 before it widens: three roundings of 2^-24 on sums of at most sum |addend|
+    # and they are the sums: (level 0, image 0) holds twice one pass over its 240 pixels.  A coarse bar, three roundings of
+    # 2^-24 on sums of at most sum |addend|: the epilogue widens every element before it adds or squares it, and
+    # tests/test_gpu_groupnorm_parity.py holds these sums to 2^-53 bars
     blk = y[:240].double().reshape(240, 32, 8)
     once = torch.stack([blk.sum((0, 2)), (blk * blk).sum((0, 2))], 1)
     mag = torch.stack([blk.abs().sum((0, 2)), (blk * blk).sum((0, 2))], 1)

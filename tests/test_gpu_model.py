@@ -29,10 +29,17 @@ def _digest(g):
     return [flat.sum().item(), flat.abs().sum().item()] + flat[idx].tolist()
 
 
-def _check_all_gradient_digests(gold, model, mode, rt, tag, allow=()):
+def _check_all_gradient_digests(gold, model, mode, rt, tag, allow=(), one_relu=None):
     """EVERY parameter-gradient digest the fixture holds (sum and abs-sum, error relative to the abs-sum) within
     ``rt``; the two smallest discriminator levels get twice the bar in bf16x3 mode (a handful of rows: one ReLU
-    decision flipped by the operand split moves their digests by ~1e-3).  Prints the six worst entries."""
+    decision flipped by the operand split moves their digests by ~1e-3).  Prints the six worst entries.
+
+    one_relu: {(mode, module): rows} names a module on a level of so few rows, in a fixture known to hold a GroupNorm output
+    within rounding of zero there, that ONE ReLU decision shows in its sampled gradient elements: the reference and the kernels
+    reach that output through different roundings, and which side of zero it falls on is neither's error.  Such an element is
+    a sum over ``rows`` pixel terms of which the decision adds or drops one; terms of one size t that do not line up sum to
+    t sqrt(rows) = mean |grad|, so one term is mean |grad| / sqrt(rows).  That much is granted there, once, on top of the
+    sampled bar and relative to mean |grad| only; the digest bars stay as they are."""
     worst, errs, samp = (0.0, None), [], (0.0, None)
     for mk, m in model.items():
         for name, p in m.named_parameters():
@@ -53,9 +60,10 @@ def _check_all_gradient_digests(gold, model, mode, rt, tag, allow=()):
             # is a sum of thousands of cancelling terms, so the bar is relative to the element AND to the mean magnitude
             mean_abs = ref[1] / max(1, p.numel())
             st = SAMPLED_BAR if mode != "bf16x3" else (0.5 if mk in ("dis_P6_CON", "dis_P7_CON") else 0.2)  # fp32 and bf16x6: one bar everywhere
+            flip = 1.0 / (one_relu or {}).get((mode, mk), float("inf")) ** 0.5
             for a, b in zip(mine[2:], ref[2:]):
                 samp = max(samp, (abs(a - b) / (abs(b) + mean_abs + 1e-30), mk + "/" + name))
-                assert abs(a - b) <= st * abs(b) + st * mean_abs + 1e-7, (tag, mode, mk, name, a, b)
+                assert abs(a - b) <= st * abs(b) + (st + flip) * mean_abs + 1e-7, (tag, mode, mk, name, a, b)
     errs.sort(reverse=True)
     print("%s %s: %d gradient digests, worst errors (sum / abs-sum, relative to abs-sum): %s" % (
         tag, mode, len(errs), ", ".join("%.2e %s" % e for e in errs[:6])))
@@ -640,7 +648,10 @@ def test_step_other_sizes_match_reference(device, gold_dir, name, paired):
             mine = _digest(p.grad)
             assert abs(mine[1] - ref[1]) <= 5e-3 * ref[1], (mode, mk, name_, mine[1], ref[1])
         if H * W >= 512 * 1024:  # real level sizes (cfg1: 100x200 ... 7x13): EVERY digest of the fixture, the step_mid bars
-            _check_all_gradient_digests(gold, model, mode, 2e-3 if mode != "bf16x3" else 3e-3, name)
+            # cfg1 in "fp32" mode: the second GroupNorm of the 7x13 discriminator tower has an output at -2.7e-7 before the
+            # ReLU (float64 on the kernels' own input, rounding bar 1.3e-7) that the reference's gradient has unmasked
+            _check_all_gradient_digests(gold, model, mode, 2e-3 if mode != "bf16x3" else 3e-3, name,
+                                        one_relu={("fp32", "dis_P7_CON"): 2 * N * 7 * 13} if name == "step_cfg1_800x1600" else None)
 
 
 @pytest.mark.parametrize("name,ft", [("step_s2c_128x256", False), ("step_s2c_ft_256x512", True)])
