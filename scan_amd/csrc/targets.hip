@@ -8,7 +8,9 @@
 // The torch spelling of the same plan (modeling/fcos.py: assign_targets, source_node_index, centerness_targets -- pinned
 // against the reference's label maps and node lists) took ~115 launches and a dozen host round trips (nonzero) per
 // iteration; here the host reads five counters once.  Integer / index work and single fp32 operations in the reference's
-// order: bit-identical to the torch spelling (tests/test_gpu_kernels.py::test_target_plan_kernels_equal_torch_plan).
+// order: bit-identical to the torch spelling (tests/test_gpu_kernels.py::test_target_plan_kernels_equal_torch_plan) and to
+// the host oracle of tests/targets_ref.py at ties, boundary equalities, zero positives, images without boxes and short
+// pyramids, with guarded outputs (tests/test_gpu_targets.py).
 #include "common.h"
 
 #define FCOS_INF 100000000.0f  // reference rpn/fcos/loss.py:22

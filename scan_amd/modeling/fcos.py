@@ -262,10 +262,15 @@ def assign_targets(locations, targets):
 
 
 def centerness_targets(reg):
-    """reference loss.py:128-133."""
+    """reference loss.py:128-133.  On the CPU the square root is taken in fp64 and rounded once, which is the correctly
+    rounded fp32 root: torch's vectorised fp32 sqrt there is not (about 0.6 % of uniform inputs end one ulp off, e.g.
+    sqrt(0.0098522175) = 0.09925833723... gives 0.099258333 where 0.099258341 is nearer), and this function is the
+    definition that csrc/targets.hip and tests/targets_ref.py are held to bit for bit.  The device's sqrt is correctly
+    rounded and stays as it was."""
     lr = reg[:, [0, 2]]
     tb = reg[:, [1, 3]]
-    return torch.sqrt((lr.min(-1)[0] / lr.max(-1)[0]) * (tb.min(-1)[0] / tb.max(-1)[0]))
+    ctr = (lr.min(-1)[0] / lr.max(-1)[0]) * (tb.min(-1)[0] / tb.max(-1)[0])
+    return torch.sqrt(ctr) if ctr.is_cuda or ctr.dtype != torch.float32 else torch.sqrt(ctr.double()).float()
 
 
 class FCOSHead(nn.Module):
