@@ -978,6 +978,54 @@ int scan_row_scale_levels(const float* x, int32_t ldx, const float* a, const flo
 int scan_row_scale_levels_ptrs(const float* const* x_levels, int32_t ldx, const float* a, const float* s, const scan_pyramid_t* d,
                                int32_t C, float* y, int32_t ldy, void* stream);
 
+/* ---- region pooling: ROIAlign, ROIPool and the FPN level mapper (csrc/vision.cpp:8-17, the two-stage half) ----
+ * x: pyramid rows [M, Cs] (Cs % 4 == 0, 16-byte aligned, only columns 0..C-1 are read).  rois: [K, 5] floats (image index,
+ * x1, y1, x2, y2); levels: K int32 level indices, or NULL: every ROI on level 0; scales: HOST array of d->n_levels spatial
+ * scales (copied into the kernel arguments).  Outputs are channel-last [K, PH, PW, Cs], padding columns written as zeros,
+ * every element written exactly once (they may be uninitialised); one launch covers all levels.  A single-level pyramid is
+ * the reference's plain operator.  Additions where the reference reads out of bounds: a ROI whose image index (truncated
+ * towards zero, as the reference's int conversion) is outside [0, n_images) or whose level is outside [0, n_levels) gives
+ * zeros, argmax -1 and no gradient; K == 0 returns without a launch (the gradients: zeros).
+ *
+ * ROIAlign, aligned = False semantics, with s the scale of the ROI's level, H x W its size.  Every fp32 operation is rounded
+ * on its own in the source's left-to-right order (what the reference's CPU build computes):
+ *   start = x1 * s, roi_w = max(x2 * s - x1 * s, 1), bin_w = roi_w / PW (likewise h)
+ *   g = sampling_ratio when > 0, otherwise ceil(roi_h / PH) and ceil(roi_w / PW) per axis (capped at 32768)
+ *   y = start_h + ph * bin_h + (iy + 0.5f) * bin_h / g_h;  y < -1 || y > H || x < -1 || x > W (or NaN): the sample is 0
+ *   y = max(y, 0), y_low = (int)y; y_low >= H - 1: y_low = y_high = H - 1, y = y_low; ly = y - y_low, hy = 1 - ly (same for x)
+ *   sample = hy hx v1 + hy lx v2 + ly hx v3 + ly lx v4;  out = (sum of the g_h g_w samples, iy outer, ix inner) / (g_h g_w) */
+/* modeling/poolers.py:31-42 (LevelMapper.__call__): levels[k] = clamp(floor(lvl0 + log2(sqrt(area) / s0 + eps)), k_min, k_max)
+ * - k_min in fp32, area = (x2 - x1 + 1) * (y2 - y1 + 1) of boxes[k * ld .. + 3] (ld = 4: a box matrix; rois + 1 with ld = 5: a
+ * ROI matrix).  k_min must be an integer.  A NaN (negative area) maps to level 0. */
+int scan_roi_levels(const float* boxes, int32_t ld, int64_t K, float k_min, float k_max, float s0, float lvl0, float eps,
+                    int32_t* levels, void* stream);
+/* csrc/cuda/ROIAlign_cuda.cu:15-122,257-299 and the per-level loop of modeling/poolers.py:116-119: y [K, PH, PW, Cs] */
+int scan_roi_align_forward(const float* x, const scan_pyramid_t* d, int32_t C, int32_t Cs, const float* rois, const int32_t* levels,
+                           const float* scales, int64_t K, int32_t PH, int32_t PW, int32_t sampling_ratio, float* y, void* stream);
+/* csrc/cuda/ROIAlign_cuda.cu:125-254,302-346: dx [M, Cs], every row written.  Each sample sends (dy * w_i) / count to its four
+ * cells; the sum is formed per destination row in a fixed order (ROI, ph, iy, y corner, pw, ix, x corner) without float
+ * atomics: the same bits on every run, for every sampling_ratio, no workspace and no host read. */
+int scan_roi_align_backward(const float* dy, const scan_pyramid_t* d, int32_t C, int32_t Cs, const float* rois,
+                            const int32_t* levels, const float* scales, int64_t K, int32_t PH, int32_t PW, int32_t sampling_ratio,
+                            float* dx, void* stream);
+/* ROIAlign_cuda.cu:99-112,22-57 made visible for tests: for every (ROI, bin) and iy, ix < gmax the position (y, x) as first
+ * formed [K, PH, PW, gmax, gmax, 2], the weights w1..w4 [.., 4] and the cells y * W + x of the level [.., 4] (-1 and weight 0:
+ * a dropped sample; iy >= g_h or ix >= g_w: position 0 too), and grid [K, 2] = (g_h, g_w), (0, 0) for a ROI outside. */
+int scan_roi_align_samples(const scan_pyramid_t* d, const float* rois, const int32_t* levels, const float* scales, int64_t K,
+                           int32_t PH, int32_t PW, int32_t sampling_ratio, int32_t gmax, int32_t* grid, float* pos, float* wgt,
+                           int32_t* cell, void* stream);
+/* csrc/cuda/ROIPool_cuda.cu:16-77,110-153: start = round(x1 * s) (half away from zero, clamped to +-2^29), roi_w = max(end -
+ * start + 1, 1) in integers, bin = roi_w / PW in fp32, wstart = floor(pw * bin) + start, wend = ceil((pw + 1) * bin) + start,
+ * both clipped to [0, W]; an empty bin gives 0 and argmax -1, otherwise the maximum from -FLT_MAX with a strict > in (h, w)
+ * scan order.  y [K, PH, PW, Cs]; argmax [K, PH, PW, Cs] int32 = h * W + w of the level per channel (padding columns -1),
+ * 16-byte aligned. */
+int scan_roi_pool_forward(const float* x, const scan_pyramid_t* d, int32_t C, int32_t Cs, const float* rois, const int32_t* levels,
+                          const float* scales, int64_t K, int32_t PH, int32_t PW, float* y, int32_t* argmax, void* stream);
+/* csrc/cuda/ROIPool_cuda.cu:79-108,156-202: dx [M, Cs] += dy at the argmax (-1: nothing), summed per destination row over the
+ * bins whose window contains it in ascending (ROI, ph, pw) order, without float atomics: the same bits on every run. */
+int scan_roi_pool_backward(const float* dy, const int32_t* argmax, const scan_pyramid_t* d, int32_t C, int32_t Cs, const float* rois,
+                           const int32_t* levels, const float* scales, int64_t K, int32_t PH, int32_t PW, float* dx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

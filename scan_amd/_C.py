@@ -7,9 +7,15 @@ error behaviour, backed by libscan_hip.so through the C ABI.
     sigmoid_focalloss_forward(logits[M,C], targets[M] int32, num_classes, gamma, alpha) -> losses[M,C]
     sigmoid_focalloss_backward(logits, targets, d_losses, num_classes, gamma, alpha) -> d_logits[M,C]
 
-roi_align_* / roi_pool_* belong to the two-stage heads no SCAN config uses
- and raise.
+    roi_align_forward(input[N,C,H,W], rois[K,5], scale, PH, PW, sampling_ratio) -> [K,C,PH,PW]  (CPU tensors: roi_align_host)
+    roi_align_backward(grad[K,C,PH,PW], rois, scale, PH, PW, N, C, H, W, sampling_ratio) -> [N,C,H,W]
+    roi_pool_forward(input, rois, scale, PH, PW) -> (output[K,C,PH,PW], argmax int32 [K,C,PH,PW])
+    roi_pool_backward(grad, input, rois, argmax, scale, PH, PW, N, C, H, W) -> [N,C,H,W]
+
+All eight functions of vision.cpp; the pooling ones run csrc/roi.hip.
 """
+import ctypes
+
 import torch
 
 from . import ops
@@ -105,8 +111,169 @@ def sigmoid_focalloss_backward(logits, targets, d_losses, num_classes, gamma, al
     return d_logits
 
 
-def _two_stage(*a, **k):
-    raise RuntimeError("roi_align/roi_pool are outside the SCAN hot path (RPN_ONLY configs); not built")
+# ----------------------------------------------------------------------------- region pooling
+# The four functions take the reference's positional arguments (csrc/ROIAlign.h:11-45, csrc/ROIPool.h:10-47) through *args: a
+# wrong count raises RuntimeError naming them, as every other failure of this module does (a plain signature would raise
+# TypeError).  NCHW is converted to the kernels' row matrix here (a view for channels_last inputs with C % 4 == 0, one
+# permuting copy otherwise) and the channel-last result back to contiguous NCHW; INTEGRATION.md prices both.
+def _take(who, names, args, kwargs):
+    if kwargs or len(args) != len(names):
+        raise RuntimeError("%s(%s): expected %d positional arguments, got %d%s"
+                           % (who, ", ".join(names), len(names), len(args), " and keyword arguments" if kwargs else ""))
+    return args
 
 
-roi_align_forward = roi_align_backward = roi_pool_forward = roi_pool_backward = _two_stage
+def _rows_in(t, who):
+    """NCHW fp32 -> (rows [N*H*W, Cs], PyramidShape, C)"""
+    if t.dim() != 4:
+        raise RuntimeError("%s: input must be [N, C, H, W]" % who)
+    rows, shape = ops.nchw_to_rows(t.float())
+    return rows, shape, t.shape[1]
+
+
+def _pooled_in(t, c, fill, who):
+    """[K, C, PH, PW] -> channel-last [K, PH, PW, Cs], padding columns = fill"""
+    if t.dim() != 4 or t.shape[1] != c:
+        raise RuntimeError("%s: expected a [K, %d, PH, PW] tensor, got %s" % (who, c, tuple(t.shape)))
+    t = t.permute(0, 2, 3, 1)
+    if c % 4:
+        t = torch.nn.functional.pad(t, (0, ops.pad4(c) - c), value=fill)
+    return t.contiguous()
+
+
+def _rois_in(rois, who):
+    if not rois.is_cuda:
+        raise RuntimeError("rois must be a CUDA tensor")  # ROIAlign_cuda.cu:264
+    if rois.dim() != 2 or rois.shape[1] != 5:
+        raise RuntimeError("%s: rois must be [K, 5]" % who)
+    return rois.float().contiguous()
+
+
+def _scale1(s):
+    return (ctypes.c_float * 1)(float(s))
+
+
+def roi_align_host(input, rois, spatial_scale, pooled_height, pooled_width, sampling_ratio):
+    """The reference's CPU dispatch (csrc/ROIAlign.h:24, csrc/cpu/ROIAlign_cpu.cpp:113-257) for host tensors, float or double:
+    positions, weights and cells in the tensors' own dtype, operation by operation in the source's order; per ROI the samples
+    of all bins are formed once for all channels.  An image index outside [0, N) gives zeros (the reference reads out of
+    bounds there)."""
+    if input.is_cuda or rois.is_cuda:
+        raise RuntimeError("input and rois must be CPU tensors")  # ROIAlign_cpu.cpp:227-228
+    if input.dtype not in (torch.float32, torch.float64) or rois.dtype != input.dtype:
+        raise RuntimeError("ROIAlign_forward: float or double input, rois of the same type")
+    N, C, H, W = input.shape
+    K, PH, PW = rois.shape[0], int(pooled_height), int(pooled_width)
+    out = torch.zeros((K, C, PH, PW), dtype=input.dtype)
+    x = input.contiguous()
+    T = input.dtype
+    scale = torch.tensor(spatial_scale, dtype=torch.float32).to(T)  # `const float spatial_scale`, then `const T&`
+
+    def axis(start, binsz, P, g, size):
+        """positions of the P * g samples of an axis -> live, low cell, high cell, l, h"""
+        p = torch.arange(P, dtype=T).repeat_interleave(g)
+        i = torch.arange(g, dtype=torch.float32).repeat(P)
+        y = start + p * binsz + (i + 0.5).to(T) * binsz / torch.tensor(float(g), dtype=T)
+        live = ~((y < -1.0) | (y > size))
+        y = torch.where((y <= 0) | ~live, torch.zeros_like(y), y)
+        lo = y.to(torch.int64).clamp(max=size - 1)  # dead samples are masked below
+        top = lo >= size - 1
+        hi = torch.where(top, lo, lo + 1)
+        y = torch.where(top, lo.to(T), y)
+        l = y - lo.to(T)
+        return live, lo, hi, l, 1.0 - l
+
+    for k in range(K):
+        r = rois[k]
+        n = int(r[0])
+        if not 0 <= n < N:
+            continue
+        sw, sh, ew, eh = r[1] * scale, r[2] * scale, r[3] * scale, r[4] * scale
+        one = torch.ones((), dtype=T)
+        rw, rh = torch.maximum(ew - sw, one), torch.maximum(eh - sh, one)
+        bh, bw = rh / PH, rw / PW
+        gh = sampling_ratio if sampling_ratio > 0 else int(torch.ceil(rh / PH))
+        gw = sampling_ratio if sampling_ratio > 0 else int(torch.ceil(rw / PW))
+        ly_, ylo, yhi, ly, hy = axis(sh, bh, PH, gh, H)
+        lx_, xlo, xhi, lx, hx = axis(sw, bw, PW, gw, W)
+        live = (ly_[:, None] & lx_[None, :]).to(T)
+        img = x[n]  # [C, H, W]
+        w1, w2, w3, w4 = hy[:, None] * hx[None, :], hy[:, None] * lx[None, :], ly[:, None] * hx[None, :], ly[:, None] * lx[None, :]
+        v1, v2 = img[:, ylo[:, None], xlo[None, :]], img[:, ylo[:, None], xhi[None, :]]
+        v3, v4 = img[:, yhi[:, None], xlo[None, :]], img[:, yhi[:, None], xhi[None, :]]
+        val = ((w1 * live) * v1 + (w2 * live) * v2 + (w3 * live) * v3 + (w4 * live) * v4).view(C, PH, gh, PW, gw)
+        acc = torch.zeros((C, PH, PW), dtype=T)
+        for iy in range(gh):
+            for ix in range(gw):
+                acc = acc + val[:, :, iy, :, ix]
+        out[k] = acc / torch.tensor(float(gh * gw), dtype=T)
+    return out
+
+
+def roi_align_forward(*args, **kwargs):
+    """roi_align_forward(input [N,C,H,W], rois [K,5], spatial_scale, pooled_height, pooled_width, sampling_ratio) ->
+    [K,C,PH,PW]   (csrc/ROIAlign.h:11-25; CPU tensors: roi_align_host)"""
+    input, rois, scale, ph, pw, sr = _take("roi_align_forward", ("input", "rois", "spatial_scale", "pooled_height",
+                                                                 "pooled_width", "sampling_ratio"), args, kwargs)
+    if not input.is_cuda:
+        return roi_align_host(input, rois, scale, ph, pw, sr)
+    rows, shape, c = _rows_in(input, "roi_align_forward")
+    rois = _rois_in(rois, "roi_align_forward")
+    y = torch.empty((rois.shape[0], int(ph), int(pw), rows.shape[1]), dtype=torch.float32, device=input.device)
+    call("scan_roi_align_forward", _ptr(rows), shape.ref(), c, rows.shape[1], _ptr(rois), None, _scale1(scale), rois.shape[0],
+         int(ph), int(pw), int(sr), _ptr(y), _stream())
+    return y[..., :c].permute(0, 3, 1, 2).contiguous().to(input.dtype)
+
+
+def roi_align_backward(*args, **kwargs):
+    """roi_align_backward(grad [K,C,PH,PW], rois, spatial_scale, pooled_height, pooled_width, batch_size, channels, height,
+    width, sampling_ratio) -> [N,C,H,W]   (csrc/ROIAlign.h:27-45)"""
+    grad, rois, scale, ph, pw, bs, ch, h, w, sr = _take(
+        "roi_align_backward", ("grad", "rois", "spatial_scale", "pooled_height", "pooled_width", "batch_size", "channels",
+                               "height", "width", "sampling_ratio"), args, kwargs)
+    if not grad.is_cuda:
+        raise RuntimeError("Not implemented on the CPU")  # csrc/ROIAlign.h:44
+    rois = _rois_in(rois, "roi_align_backward")
+    dy = _pooled_in(grad.float(), int(ch), 0.0, "roi_align_backward")
+    shape = ops.PyramidShape(int(bs), [(int(h), int(w))])
+    cs = dy.shape[-1]
+    dx = torch.empty((shape.rows, cs), dtype=torch.float32, device=grad.device)
+    call("scan_roi_align_backward", _ptr(dy), shape.ref(), int(ch), cs, _ptr(rois), None, _scale1(scale), rois.shape[0], int(ph),
+         int(pw), int(sr), _ptr(dx), _stream())
+    return dx.view(int(bs), int(h), int(w), cs)[..., :int(ch)].permute(0, 3, 1, 2).contiguous().to(grad.dtype)
+
+
+def roi_pool_forward(*args, **kwargs):
+    """roi_pool_forward(input [N,C,H,W], rois [K,5], spatial_scale, pooled_height, pooled_width) -> (output [K,C,PH,PW],
+    argmax int32 [K,C,PH,PW])   (csrc/ROIPool.h:10-25)"""
+    input, rois, scale, ph, pw = _take("roi_pool_forward", ("input", "rois", "spatial_scale", "pooled_height", "pooled_width"),
+                                       args, kwargs)
+    if not input.is_cuda:
+        raise RuntimeError("Not implemented on the CPU")  # csrc/ROIPool.h:24
+    rows, shape, c = _rows_in(input, "roi_pool_forward")
+    rois = _rois_in(rois, "roi_pool_forward")
+    y = torch.empty((rois.shape[0], int(ph), int(pw), rows.shape[1]), dtype=torch.float32, device=input.device)
+    argmax = torch.empty(y.shape, dtype=torch.int32, device=input.device)
+    call("scan_roi_pool_forward", _ptr(rows), shape.ref(), c, rows.shape[1], _ptr(rois), None, _scale1(scale), rois.shape[0],
+         int(ph), int(pw), _ptr(y), _ptr(argmax), _stream())
+    return (y[..., :c].permute(0, 3, 1, 2).contiguous().to(input.dtype), argmax[..., :c].permute(0, 3, 1, 2).contiguous())
+
+
+def roi_pool_backward(*args, **kwargs):
+    """roi_pool_backward(grad [K,C,PH,PW], input, rois, argmax, spatial_scale, pooled_height, pooled_width, batch_size, channels,
+    height, width) -> [N,C,H,W]   (csrc/ROIPool.h:27-47)"""
+    grad, input, rois, argmax, scale, ph, pw, bs, ch, h, w = _take(
+        "roi_pool_backward", ("grad", "input", "rois", "argmax", "spatial_scale", "pooled_height", "pooled_width", "batch_size",
+                              "channels", "height", "width"), args, kwargs)
+    if not grad.is_cuda:
+        raise RuntimeError("Not implemented on the CPU")  # csrc/ROIPool.h:46
+    rois = _rois_in(rois, "roi_pool_backward")
+    dy = _pooled_in(grad.float(), int(ch), 0.0, "roi_pool_backward")
+    am = _pooled_in(argmax.to(torch.int32), int(ch), -1, "roi_pool_backward")
+    shape = ops.PyramidShape(int(bs), [(int(h), int(w))])
+    cs = dy.shape[-1]
+    dx = torch.empty((shape.rows, cs), dtype=torch.float32, device=grad.device)
+    call("scan_roi_pool_backward", _ptr(dy), _ptr(am), shape.ref(), int(ch), cs, _ptr(rois), None, _scale1(scale), rois.shape[0],
+         int(ph), int(pw), _ptr(dx), _stream())
+    return dx.view(int(bs), int(h), int(w), cs)[..., :int(ch)].permute(0, 3, 1, 2).contiguous().to(grad.dtype)
+

@@ -275,6 +275,17 @@ SIGNATURES = {
     "scan_row_scale_levels": (ctypes.c_int, [c_vp, c_i32, c_vp, ctypes.POINTER(c_f32), _PD, c_i32, c_vp, c_i32, c_vp]),
     "scan_row_scale_levels_ptrs": (ctypes.c_int, [ctypes.POINTER(c_vp), c_i32, c_vp, ctypes.POINTER(c_f32), _PD, c_i32, c_vp, c_i32,
                                                   c_vp]),
+    "scan_roi_levels": (ctypes.c_int, [c_vp, c_i32, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp]),
+    "scan_roi_align_forward": (ctypes.c_int, [c_vp, _PD, c_i32, c_i32, c_vp, c_vp, ctypes.POINTER(c_f32), c_i64, c_i32, c_i32,
+                                              c_i32, c_vp, c_vp]),
+    "scan_roi_align_backward": (ctypes.c_int, [c_vp, _PD, c_i32, c_i32, c_vp, c_vp, ctypes.POINTER(c_f32), c_i64, c_i32, c_i32,
+                                               c_i32, c_vp, c_vp]),
+    "scan_roi_align_samples": (ctypes.c_int, [_PD, c_vp, c_vp, ctypes.POINTER(c_f32), c_i64, c_i32, c_i32, c_i32, c_i32, c_vp,
+                                              c_vp, c_vp, c_vp, c_vp]),
+    "scan_roi_pool_forward": (ctypes.c_int, [c_vp, _PD, c_i32, c_i32, c_vp, c_vp, ctypes.POINTER(c_f32), c_i64, c_i32, c_i32,
+                                             c_vp, c_vp, c_vp]),
+    "scan_roi_pool_backward": (ctypes.c_int, [c_vp, c_vp, _PD, c_i32, c_i32, c_vp, c_vp, ctypes.POINTER(c_f32), c_i64, c_i32,
+                                              c_i32, c_vp, c_vp]),
 }
 
 _lib = None

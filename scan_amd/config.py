@@ -83,6 +83,12 @@ ATSS_DEFAULTS = {
 }
 
 
+# Region poolers (modeling/poolers.make_pooler) with the reference's defaults for MODEL.<head_name> (defaults.py:214-216 for
+# ROI_BOX_HEAD; ROI_MASK_HEAD :231-233 and ROI_KEYPOINT_HEAD :249-251 carry the same three values).  Kept OUT of DEFAULTS for
+# the same reason as ATSS_DEFAULTS; pooler_settings(cfg, head_name) reads a cfg's MODEL[head_name] block over these.
+POOLER_DEFAULTS = {"POOLER_RESOLUTION": 14, "POOLER_SAMPLING_RATIO": 0, "POOLER_SCALES": (1.0 / 16,)}
+
+
 # The global-alignment (GA) and centre-aware (CA) discriminators of the EPM baseline (the reference's configs/epm/*.yaml) with the
 # reference's defaults (defaults.py:356-411).  Kept OUT of DEFAULTS for the same reason as ATSS_DEFAULTS; epm_settings(cfg) reads a
 # cfg's MODEL.ADV block over these.
@@ -272,6 +278,13 @@ def settings(cfg):
         val_iter=int(cfg.SOLVER.VAL_ITER), val_type=str(cfg.SOLVER.VAL_TYPE), adapt_val_on=bool(cfg.SOLVER.ADAPT_VAL_ON),
         solver={k: solver_group(cfg, k) for k in ("backbone", "fcos", "middle_head", "dis")},
     )
+
+
+def pooler_settings(cfg, head_name):
+    """(resolution, scales, sampling_ratio) of MODEL[head_name] over POOLER_DEFAULTS (reference modeling/poolers.py:124-127)"""
+    P = Cfg(POOLER_DEFAULTS)
+    P._merge({k: v for k, v in cfg.MODEL.get(head_name, {}).items() if k in POOLER_DEFAULTS})
+    return int(P.POOLER_RESOLUTION), tuple(float(s) for s in P.POOLER_SCALES), int(P.POOLER_SAMPLING_RATIO)
 
 
 def atss_settings(cfg):

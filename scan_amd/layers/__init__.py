@@ -7,7 +7,7 @@ from torch import nn
 from .. import _C as _C_ctypes, ops
 
 # ``_C``: the compiled pybind11 module a reference checkout imports as fcos_core._C (scan_amd/csrc/fcos_core_C.cpp, built by
-# __graft_entry__.build() into scan_amd/ext/fcos_core/); scan_amd/_C.py is the same four functions bound through ctypes
+# __graft_entry__.build() into scan_amd/ext/fcos_core/); scan_amd/_C.py is the same eight functions bound through ctypes
 # (kept for environments without a C++ toolchain -- both sit on the C ABI of libscan_hip.so, neither computes anything itself)
 try:
     from ..ext.fcos_core import _C
@@ -320,3 +320,53 @@ class DFConv2d(nn.Module):
         offset_mask = self.offset(x)
         split_point = self.offset_base_channels * 2
         return self.conv(x, offset_mask[:, :split_point, :, :], offset_mask[:, split_point:, :, :].sigmoid())
+
+
+# ----------------------------------------------------------------------------- region pooling (ROIAlign / ROIPool)
+# reference layers/roi_align.py:11-68 and layers/roi_pool.py:11-63 over _C.roi_align_* / _C.roi_pool_* (csrc/cuda/ROIAlign_cuda.cu,
+# csrc/cuda/ROIPool_cuda.cu): the same call signatures and __repr__ on NCHW tensors, contiguous NCHW [K, C, PH, PW] out.  The
+# arithmetic is ops.roi_align / ops.roi_pool on the row matrix of the input (csrc/roi.hip; a channels_last input with C % 4 == 0
+# IS that matrix), whose gradients are per-destination sums without float atomics.  GPU tensors only, as every op here;
+# _C.roi_align_forward mirrors the reference's CPU dispatch for host tensors.
+def _pair(v):
+    return tuple(v) if isinstance(v, (list, tuple)) else (v, v)
+
+
+def roi_align(input, roi, output_size, spatial_scale, sampling_ratio):
+    rows, shape, c = _to_rows(input)
+    y = ops.roi_align(rows, shape, roi, _pair(output_size), (spatial_scale,), sampling_ratio, c=c)
+    return y[..., :c].permute(0, 3, 1, 2).contiguous()
+
+
+class ROIAlign(nn.Module):
+    def __init__(self, output_size, spatial_scale, sampling_ratio):
+        super().__init__()
+        self.output_size = output_size
+        self.spatial_scale = spatial_scale
+        self.sampling_ratio = sampling_ratio
+
+    def forward(self, input, rois):
+        return roi_align(input, rois, self.output_size, self.spatial_scale, self.sampling_ratio)
+
+    def __repr__(self):
+        return "%s(output_size=%s, spatial_scale=%s, sampling_ratio=%s)" % (
+            self.__class__.__name__, self.output_size, self.spatial_scale, self.sampling_ratio)
+
+
+def roi_pool(input, roi, output_size, spatial_scale):
+    rows, shape, c = _to_rows(input)
+    y = ops.roi_pool(rows, shape, roi, _pair(output_size), (spatial_scale,), c=c)
+    return y[..., :c].permute(0, 3, 1, 2).contiguous()
+
+
+class ROIPool(nn.Module):
+    def __init__(self, output_size, spatial_scale):
+        super().__init__()
+        self.output_size = output_size
+        self.spatial_scale = spatial_scale
+
+    def forward(self, input, rois):
+        return roi_pool(input, rois, self.output_size, self.spatial_scale)
+
+    def __repr__(self):
+        return "%s(output_size=%s, spatial_scale=%s)" % (self.__class__.__name__, self.output_size, self.spatial_scale)

@@ -1000,6 +1000,142 @@ def unpack_levels(rows, shape, c=None, memory_format=torch.channels_last):
     return list(_UnpackLevels.apply(rows, shape, c, memory_format))
 
 
+# ----------------------------------------------------------------------------- region pooling (ROIAlign / ROIPool)
+def _roi_args(who, rows, shape, rois, output_size, scales, levels, c):
+    """the checks every pooling op shares; returns (rois, levels, (PH, PW), host scale array, C)"""
+    _chk(rows, rois, levels)
+    if rows.dtype != torch.float32 or rows.dim() != 2 or rows.shape[0] != shape.rows or rows.shape[1] % 4:
+        raise RuntimeError("%s: rows %s (%s) do not fit %r as an fp32 [M, Cs] matrix with Cs %% 4 == 0"
+                           % (who, tuple(rows.shape), rows.dtype, shape))
+    if rois.dtype != torch.float32 or rois.dim() != 2 or rois.shape[1] != 5:
+        raise RuntimeError("%s: rois must be an fp32 [K, 5] matrix (image index, x1, y1, x2, y2), got %s %s"
+                           % (who, tuple(rois.shape), rois.dtype))
+    ph, pw = (output_size, output_size) if isinstance(output_size, int) else (int(output_size[0]), int(output_size[1]))
+    if ph < 1 or pw < 1:
+        raise RuntimeError("%s: output_size %r must be >= 1 x 1" % (who, output_size))
+    scales = [float(s) for s in ((scales,) if isinstance(scales, (int, float)) else scales)]
+    if len(scales) != shape.n_levels:
+        raise RuntimeError("%s: %d scales for the %d levels of %r" % (who, len(scales), shape.n_levels, shape))
+    c = rows.shape[1] if c is None else int(c)
+    if not 1 <= c <= rows.shape[1]:
+        raise RuntimeError("%s: c=%d must be in [1, Cs=%d]" % (who, c, rows.shape[1]))
+    rois = rois.contiguous()
+    if levels is None and len(scales) > 1:
+        levels = roi_levels(rois, -torch.log2(torch.tensor(scales[0], dtype=torch.float32)).item(),
+                            -torch.log2(torch.tensor(scales[-1], dtype=torch.float32)).item())  # modeling/poolers.py:74-76
+    if levels is not None:
+        if levels.dtype != torch.int32 or levels.dim() != 1 or levels.shape[0] != rois.shape[0]:
+            raise RuntimeError("%s: levels must be int32 [K=%d], got %s %s" % (who, rois.shape[0], tuple(levels.shape), levels.dtype))
+        levels = levels.contiguous()
+    return rois, levels, (ph, pw), (ctypes.c_float * len(scales))(*scales), c
+
+
+def roi_levels(rois, k_min, k_max, canonical_scale=224, canonical_level=4, eps=1e-6):
+    """The reference's LevelMapper (modeling/poolers.py:11-42) on the device: rois [K, 5] (or boxes [K, 4], xyxy) -> int32 [K]
+    = clamp(floor(canonical_level + log2(sqrt(area) / canonical_scale + eps)), k_min, k_max) - k_min in fp32, with
+    area = (x2 - x1 + 1)(y2 - y1 + 1).  No host read."""
+    _chk(rois)
+    if rois.dtype != torch.float32 or rois.dim() != 2 or rois.shape[1] not in (4, 5):
+        raise RuntimeError("roi_levels: needs an fp32 [K, 5] ROI or [K, 4] box matrix, got %s %s" % (tuple(rois.shape), rois.dtype))
+    rois = rois.contiguous()
+    K, ld = rois.shape
+    levels = torch.empty((K,), dtype=torch.int32, device=rois.device)
+    call("scan_roi_levels", ctypes.c_void_p(rois.data_ptr() + 4 * (ld - 4)), ld, K, float(k_min), float(k_max),
+         float(canonical_scale), float(canonical_level), float(eps), _ptr(levels), _stream())
+    return levels
+
+
+class _RoiAlign(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, shape, rois, levels, sizes, scales, sr, c):
+        K, cs = rois.shape[0], x.shape[1]
+        y = x.new_empty((K, sizes[0], sizes[1], cs))
+        call("scan_roi_align_forward", _ptr(x), shape.ref(), c, cs, _ptr(rois), _ptr(levels), scales, K, sizes[0], sizes[1], sr,
+             _ptr(y), _stream())
+        ctx.save_for_backward(rois, levels)
+        ctx.cfg = (shape, sizes, scales, sr, c, cs)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        rois, levels = ctx.saved_tensors
+        shape, sizes, scales, sr, c, cs = ctx.cfg
+        dy = dy.contiguous()
+        dx = torch.empty((shape.rows, cs), dtype=torch.float32, device=dy.device)
+        call("scan_roi_align_backward", _ptr(dy), shape.ref(), c, cs, _ptr(rois), _ptr(levels), scales, rois.shape[0], sizes[0],
+             sizes[1], sr, _ptr(dx), _stream())
+        return dx, None, None, None, None, None, None, None
+
+
+def roi_align(rows, shape, rois, output_size, scales, sampling_ratio, levels=None, c=None):
+    """ROIAlign (reference csrc/cuda/ROIAlign_cuda.cu, aligned=False semantics; include/scan_hip.h has the definition) of pyramid
+    rows [M, Cs] for rois [K, 5] = (image, x1, y1, x2, y2): returns [K, PH, PW, Cs] channel-last, columns c..Cs-1 zeros.  One
+    launch for all levels: ``scales`` has one spatial scale per level, ``levels`` int32 [K] names each ROI's level (None: level
+    0 for a single scale, otherwise roi_levels, the reference's LevelMapper).  A ROI whose image or level is out of range gives
+    zeros and no gradient.  sampling_ratio <= 0: the adaptive grid ceil(roi / pooled) per ROI and axis.
+
+    Autograd to ``rows`` only.  The gradient is summed per destination row in a fixed order without float atomics
+    (csrc/roi.hip): bit-identical from run to run whether ``deterministic`` is on or off, for every sampling_ratio, and with
+    NO host read (0 device-to-host copies, the adaptive grid included)."""
+    rois, levels, sizes, sc, c = _roi_args("roi_align", rows, shape, rois, output_size, scales, levels, c)
+    return _RoiAlign.apply(rows, shape, rois, levels, sizes, sc, int(sampling_ratio), c)
+
+
+def roi_align_samples(shape, rois, output_size, scales, sampling_ratio, gmax, levels=None):
+    """what roi_align's kernels form per sample, for tests: (grid int32 [K, 2], pos [K, PH, PW, gmax, gmax, 2],
+    weights [..., 4], cells int32 [..., 4]) -- see scan_roi_align_samples"""
+    dummy = torch.empty((shape.rows, 4), dtype=torch.float32, device=rois.device)
+    rois, levels, (ph, pw), sc, _ = _roi_args("roi_align_samples", dummy, shape, rois, output_size, scales, levels, None)
+    K, dev = rois.shape[0], rois.device
+    grid = torch.zeros((K, 2), dtype=torch.int32, device=dev)
+    pos = torch.zeros((K, ph, pw, gmax, gmax, 2), dtype=torch.float32, device=dev)
+    wgt = torch.zeros((K, ph, pw, gmax, gmax, 4), dtype=torch.float32, device=dev)
+    cell = torch.zeros((K, ph, pw, gmax, gmax, 4), dtype=torch.int32, device=dev)
+    call("scan_roi_align_samples", shape.ref(), _ptr(rois), _ptr(levels), sc, K, ph, pw, int(sampling_ratio), int(gmax), _ptr(grid),
+         _ptr(pos), _ptr(wgt), _ptr(cell), _stream())
+    return grid, pos, wgt, cell
+
+
+class _RoiPool(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, shape, rois, levels, sizes, scales, c):
+        K, cs = rois.shape[0], x.shape[1]
+        y = x.new_empty((K, sizes[0], sizes[1], cs))
+        argmax = torch.empty((K, sizes[0], sizes[1], cs), dtype=torch.int32, device=x.device)
+        call("scan_roi_pool_forward", _ptr(x), shape.ref(), c, cs, _ptr(rois), _ptr(levels), scales, K, sizes[0], sizes[1],
+             _ptr(y), _ptr(argmax), _stream())
+        ctx.save_for_backward(rois, levels, argmax)
+        ctx.cfg = (shape, sizes, scales, c, cs)
+        ctx.mark_non_differentiable(argmax)
+        return y, argmax
+
+    @staticmethod
+    def backward(ctx, dy, _dargmax):
+        rois, levels, argmax = ctx.saved_tensors
+        shape, sizes, scales, c, cs = ctx.cfg
+        dx = roi_pool_backward(dy.contiguous(), argmax, shape, rois, sizes, scales, levels, c)
+        return dx, None, None, None, None, None, None
+
+
+def roi_pool_backward(dy, argmax, shape, rois, sizes, scales, levels, c):
+    """dx [M, Cs] of roi_pool for dy, argmax [K, PH, PW, Cs] (scan_roi_pool_backward): per destination, no atomics"""
+    cs = dy.shape[-1]
+    dx = torch.empty((shape.rows, cs), dtype=torch.float32, device=dy.device)
+    call("scan_roi_pool_backward", _ptr(dy), _ptr(argmax), shape.ref(), c, cs, _ptr(rois), _ptr(levels), scales, rois.shape[0],
+         sizes[0], sizes[1], _ptr(dx), _stream())
+    return dx
+
+
+def roi_pool(rows, shape, rois, output_size, scales, levels=None, c=None, return_argmax=False):
+    """ROIPool (reference csrc/cuda/ROIPool_cuda.cu; include/scan_hip.h has the definition) of pyramid rows [M, Cs]: returns
+    [K, PH, PW, Cs] channel-last (and, with return_argmax, the int32 argmax h * W + w of the ROI's level per channel, -1 for an
+    empty bin).  ``scales`` / ``levels`` as for roi_align.  Autograd to ``rows`` only; the gradient is summed per destination
+    in ascending (ROI, ph, pw) order without float atomics: bit-identical from run to run, no host read."""
+    rois, levels, sizes, sc, c = _roi_args("roi_pool", rows, shape, rois, output_size, scales, levels, c)
+    y, argmax = _RoiPool.apply(rows, shape, rois, levels, sizes, sc, c)
+    return (y, argmax) if return_argmax else y
+
+
 # ----------------------------------------------------------------------------- 2x2 max pooling
 class _MaxPool2x2(torch.autograd.Function):
     @staticmethod
