@@ -669,6 +669,47 @@ int scan_atss_giou_backward(const scan_pyramid_t* d, const int32_t* strides, con
                             const float* target, const int64_t* rows, const float* weight, int64_t P,
                             const float* g_num_dev, float* d_pred, void* stream);
 
+/* ---- the RetinaNet head's ground-truth plan and smooth-L1 loss (csrc/retina.hip; reference modeling/matcher.py:42-112 with
+ *      allow_low_quality_matches, rpn/loss.py:42-89, rpn/retinanet/loss.py:43-80, modeling/box_coder.py:22-50,
+ *      layers/smooth_l1_loss.py).  A = 1..16 anchors per location: anchor i = m * A + a of pyramid row m = (level l, image, y, x)
+ *      is cells[l][a] + (x s, y s, x s, y s), s = strides[l] (host array), cells [n_levels][A][4] fp32 xyxy a DEVICE buffer,
+ *      16-byte aligned; no [M * A][4] anchor tensor exists.  boxes [N][G][4] (16-byte aligned), glabels [N][G], ng [N] as
+ *      scan_fcos_assign; boxes beyond ng[n] take no part.
+ *      scan_retina_match: IoU = boxlist_iou in fp32 (+1 extents, clamp(min=0), inter / (a1 + a2 - inter), every operation
+ *      rounded on its own: torch-CPU's bits).  Pass 1: per (image, box) the max IoU over the image's anchors (integer max of the
+ *      bits, reduced in the wave before one atomic).  Pass 2, per anchor: max / argmax over the image's boxes (equal IoUs: the
+ *      smaller box index -- this library's rule); max < bg_thr: label 0; bg_thr <= max < fg_thr: label -1; else glabels of the
+ *      argmax box; an anchor whose IoU with SOME real box equals that box's maximum gets the label of its OWN argmax box
+ *      whatever its IoU (ties included; a box that overlaps no anchor has maximum 0, which every anchor missing it equals).
+ *      ng[n] = 0: all background (the reference raises).  Outputs: labels_i32 [M * A], matched [M * A] = argmax box where
+ *      label > 0 else 0, n_pos[0] = anchors with label > 0 (device counter, cleared here).  ws: scan_retina_match_ws_bytes
+ *      bytes.  Two memsets and two launches; integer atomics only, so the result is bit-reproducible whatever scan_tune
+ *      "deterministic" says and there is no *_ordered twin.
+ *      scan_retina_smooth_l1_*: over ALL M * A anchors, no compaction.  Where labels_i32 > 0 the target is
+ *      BoxCoder.encode(boxes[n][matched], anchor), weights (10, 10, 5, 5), TO_REMOVE = 1, formed in fp64 and rounded to fp32
+ *      once; the prediction is columns [4a, 4a + 4) of row m of bbox_reg, whose row pitch is ld floats (a multiple of 4,
+ *      >= 4 A; 16-byte aligned).  Forward ADDS sum of (0.5 d^2 / beta where |d| < beta, |d| - 0.5 beta elsewhere) to out[0]
+ *      (clear it first); the _ordered twin writes it from per-block slots in a fixed order (ws:
+ *      scan_retina_smooth_l1_ordered_ws_floats(M * A) floats).  targets_out (optional, [M * A][4], 16-byte aligned): the
+ *      encoded targets, zero where label <= 0.  Backward: d_pred (row pitch ld_out) = g_dev[0] * (d / beta where |d| < beta,
+ *      sign(d) elsewhere) for EVERY anchor, zero where label <= 0. ---- */
+int64_t scan_retina_match_ws_bytes(const scan_pyramid_t* d, int32_t G);
+int scan_retina_match(const scan_pyramid_t* d, const int32_t* strides, const float* cells, int32_t A, const float* boxes,
+                      const int64_t* glabels, const int32_t* ng, int32_t G, float bg_thr, float fg_thr, int32_t* labels_i32,
+                      int32_t* matched, int32_t* n_pos, void* ws, void* stream);
+int scan_retina_smooth_l1_forward(const scan_pyramid_t* d, const int32_t* strides, const float* cells, int32_t A,
+                                  const float* boxes, int32_t G, const int32_t* labels_i32, const int32_t* matched,
+                                  const float* bbox_reg, int64_t ld, float beta, float* targets_out, float* out, void* stream);
+int64_t scan_retina_smooth_l1_ordered_ws_floats(int64_t n_anchors);
+int scan_retina_smooth_l1_forward_ordered(const scan_pyramid_t* d, const int32_t* strides, const float* cells, int32_t A,
+                                          const float* boxes, int32_t G, const int32_t* labels_i32, const int32_t* matched,
+                                          const float* bbox_reg, int64_t ld, float beta, float* targets_out, float* out,
+                                          float* ws, void* stream);
+int scan_retina_smooth_l1_backward(const scan_pyramid_t* d, const int32_t* strides, const float* cells, int32_t A,
+                                   const float* boxes, int32_t G, const int32_t* labels_i32, const int32_t* matched,
+                                   const float* bbox_reg, int64_t ld, float beta, const float* g_dev, float* d_pred,
+                                   int64_t ld_out, void* stream);
+
 /* ---- FPN top-down join on NHWC rows (reference backbone/fpn.py:62-75: inner = lateral + F.interpolate(top,
  *      scale_factor=2, mode="nearest")).  lat / y [N, 2h, 2w, C], coarse [N, h, w, C], C % 4 == 0.  Backward:
  *      d_lateral is the incoming gradient itself, d_coarse its 2x2 window sums (scan_downsample2x_sum: g [N, 2h, 2w, C]

@@ -161,7 +161,17 @@ SIGNATURES = {
     "scan_atss_giou_ordered_ws_floats": (c_i64, [c_i64]),
     "scan_atss_giou_forward_ordered": (ctypes.c_int, [_PD, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "scan_atss_giou_backward": (ctypes.c_int, [_PD, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
-    "scan_groupnorm_relu_forward_ld": (ctypes.c_int, [c_vp, _PD, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp]),
+    "scan_retina_match_ws_bytes": (c_i64, [_PD, c_i32]),
+    "scan_retina_match": (ctypes.c_int, [_PD, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp,
+                                         c_vp]),
+    "scan_retina_smooth_l1_forward": (ctypes.c_int, [_PD, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_f32, c_vp,
+                                                     c_vp, c_vp]),
+    "scan_retina_smooth_l1_ordered_ws_floats": (c_i64, [c_i64]),
+    "scan_retina_smooth_l1_forward_ordered": (ctypes.c_int, [_PD, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_f32,
+                                                             c_vp, c_vp, c_vp, c_vp]),
+    "scan_retina_smooth_l1_backward": (ctypes.c_int, [_PD, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_f32, c_vp,
+                                                      c_vp, c_i64, c_vp]),
+    "scan_groupnorm_relu_forward_ld":(ctypes.c_int, [c_vp, _PD, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp]),
     "scan_groupnorm_relu_forward_from_sums_ld": (ctypes.c_int, [c_vp, _PD, c_i32, c_i32, c_vp, c_f32, c_vp, c_vp, c_i32, c_vp,
                                                                 c_i32, c_vp, c_vp]),
     "scan_groupnorm_relu_backward_ld": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, _PD, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp,

@@ -83,6 +83,16 @@ ATSS_DEFAULTS = {
 }
 
 
+# The RetinaNet head (MODEL.RETINANET_ON, modeling/retinanet.py) with the reference's defaults (defaults.py:415-470).  Kept OUT
+# of DEFAULTS for the same reason as ATSS_DEFAULTS; retinanet_settings(cfg) reads a cfg's MODEL.RETINANET block over these.
+RETINANET_DEFAULTS = {
+    "NUM_CLASSES": 81, "ANCHOR_SIZES": (32, 64, 128, 256, 512), "ASPECT_RATIOS": (0.5, 1.0, 2.0),
+    "ANCHOR_STRIDES": (8, 16, 32, 64, 128), "STRADDLE_THRESH": 0, "OCTAVE": 2.0, "SCALES_PER_OCTAVE": 3, "USE_C5": True,
+    "NUM_CONVS": 4, "BBOX_REG_WEIGHT": 4.0, "BBOX_REG_BETA": 0.11, "PRE_NMS_TOP_N": 1000, "FG_IOU_THRESHOLD": 0.5,
+    "BG_IOU_THRESHOLD": 0.4, "LOSS_ALPHA": 0.25, "LOSS_GAMMA": 2.0, "PRIOR_PROB": 0.01, "INFERENCE_TH": 0.05, "NMS_TH": 0.4,
+}
+
+
 # Region poolers (modeling/poolers.make_pooler) with the reference's defaults for MODEL.<head_name> (defaults.py:214-216 for
 # ROI_BOX_HEAD; ROI_MASK_HEAD :231-233 and ROI_KEYPOINT_HEAD :249-251 carry the same three values).  Kept OUT of DEFAULTS for
 # the same reason as ATSS_DEFAULTS; pooler_settings(cfg, head_name) reads a cfg's MODEL[head_name] block over these.
@@ -318,6 +328,46 @@ def atss_settings(cfg):
         topk=int(A.TOPK), reg_loss_weight=float(A.REG_LOSS_WEIGHT), prior_prob=float(A.PRIOR_PROB),
         inference_th=float(A.INFERENCE_TH), pre_nms_top_n=int(A.PRE_NMS_TOP_N), nms_th=float(A.NMS_TH),
         detections_per_img=int(cfg.TEST.DETECTIONS_PER_IMG))
+
+
+def retinanet_settings(cfg):
+    """Flat view of MODEL.RETINANET for modeling.retinanet.RetinaNetModule; raises, naming the key, on every value that is not
+    built.  The backbones here make P6 from P5, so USE_C5 (the reference's default) must be switched off explicitly.
+    STRADDLE_THRESH: the RetinaNet loss never reads the anchors' visibility field (rpn/retinanet/loss.py:40 discards only
+    'between_thresholds'), so only the reference's 0 is accepted and it has no effect."""
+    R = Cfg(RETINANET_DEFAULTS)
+    R._merge(cfg.MODEL.get("RETINANET", {}))
+    if bool(R.USE_C5):
+        raise ValueError("MODEL.RETINANET.USE_C5 True is not built: the pyramid's P6 is made from P5 (set it to False)")
+    if tuple(R.ANCHOR_STRIDES) != (8, 16, 32, 64, 128):
+        raise ValueError("MODEL.RETINANET.ANCHOR_STRIDES %r: the pyramid has strides (8, 16, 32, 64, 128)" % (R.ANCHOR_STRIDES,))
+    if len(R.ANCHOR_SIZES) != 5 or any(float(a) < 1 for a in R.ANCHOR_SIZES):
+        raise ValueError("MODEL.RETINANET.ANCHOR_SIZES %r: one size >= 1 per pyramid level" % (R.ANCHOR_SIZES,))
+    if any(float(r) <= 0 for r in R.ASPECT_RATIOS) or not 1 <= len(R.ASPECT_RATIOS) <= 16:
+        raise ValueError("MODEL.RETINANET.ASPECT_RATIOS %r: 1..16 positive ratios" % (R.ASPECT_RATIOS,))
+    if not (int(R.SCALES_PER_OCTAVE) >= 1 and 1 <= len(R.ASPECT_RATIOS) * int(R.SCALES_PER_OCTAVE) <= 16):
+        raise ValueError("MODEL.RETINANET.SCALES_PER_OCTAVE %r with %d ASPECT_RATIOS: 1..16 anchors per location are built"
+                         % (R.SCALES_PER_OCTAVE, len(R.ASPECT_RATIOS)))
+    if float(R.OCTAVE) <= 0:
+        raise ValueError("MODEL.RETINANET.OCTAVE %r must be positive" % (R.OCTAVE,))
+    if not 2 <= int(R.NUM_CLASSES) <= 32:
+        raise ValueError("MODEL.RETINANET.NUM_CLASSES %r (background included): 2..32 are built" % (R.NUM_CLASSES,))
+    if R.STRADDLE_THRESH != 0:
+        raise ValueError("MODEL.RETINANET.STRADDLE_THRESH %r: the RetinaNet loss never reads visibility; only 0" % (R.STRADDLE_THRESH,))
+    if float(R.BG_IOU_THRESHOLD) > float(R.FG_IOU_THRESHOLD):
+        raise ValueError("MODEL.RETINANET.BG_IOU_THRESHOLD %r above FG_IOU_THRESHOLD %r" % (R.BG_IOU_THRESHOLD, R.FG_IOU_THRESHOLD))
+    if int(R.NUM_CONVS) < 1:
+        raise ValueError("MODEL.RETINANET.NUM_CONVS %r: at least one tower conv" % (R.NUM_CONVS,))
+    if float(R.BBOX_REG_BETA) <= 0:
+        raise ValueError("MODEL.RETINANET.BBOX_REG_BETA %r must be positive" % (R.BBOX_REG_BETA,))
+    return dict(
+        num_classes=int(R.NUM_CLASSES), anchor_sizes=tuple(float(a) for a in R.ANCHOR_SIZES),
+        anchor_strides=tuple(int(s) for s in R.ANCHOR_STRIDES), aspect_ratios=tuple(float(r) for r in R.ASPECT_RATIOS),
+        octave=float(R.OCTAVE), scales_per_octave=int(R.SCALES_PER_OCTAVE), num_convs=int(R.NUM_CONVS),
+        bbox_reg_weight=float(R.BBOX_REG_WEIGHT), bbox_reg_beta=float(R.BBOX_REG_BETA), pre_nms_top_n=int(R.PRE_NMS_TOP_N),
+        fg_iou_threshold=float(R.FG_IOU_THRESHOLD), bg_iou_threshold=float(R.BG_IOU_THRESHOLD), loss_alpha=float(R.LOSS_ALPHA),
+        loss_gamma=float(R.LOSS_GAMMA), prior_prob=float(R.PRIOR_PROB), inference_th=float(R.INFERENCE_TH),
+        nms_th=float(R.NMS_TH), detections_per_img=int(cfg.TEST.DETECTIONS_PER_IMG))
 
 
 def epm_settings(cfg):

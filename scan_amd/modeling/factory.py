@@ -29,6 +29,7 @@ from .condgraph import GRAPHModule
 from .discriminator import FCOSDiscriminator_con
 from .fcos import FCOSModule
 from .resnet import ResNetFPNBackbone
+from .retinanet import RetinaNetModule
 
 LEVELS = ("P3", "P4", "P5", "P6", "P7")
 DIS_ORDER = ("P7", "P6", "P5", "P4", "P3")  # order the reference builds them in (tools/train_net_da.py:223-274)
@@ -177,14 +178,36 @@ class ATSSModuleNCHW(_RpnForwardNCHW, ATSSModule):
     by that function."""
 
 
+class RetinaNetModuleNCHW(_RpnForwardNCHW, RetinaNetModule):
+    """RetinaNetModule.forward of the reference (rpn/retinanet/retinanet.py:112-148) with the ``return_maps`` / ``act_maps``
+    arguments foward_detector passes (engine/trainer.py:20-72), which the reference's own forward lacks.  Two losses
+    (loss_retina_cls, loss_retina_reg) and no centerness: score_maps = {"box_cls", "box_regression"}."""
+
+    def forward(self, images, features, targets=None, return_maps=False, act_maps=None):
+        if not self.training or not return_maps:
+            return super().forward(images, features, targets, return_maps, act_maps)
+        rows, shape = ops.pack_levels(features)
+        targets = target_tuples(targets)
+        logits, reg = self.head(rows, shape)
+        if targets is None:
+            losses = {"zero": rows.new_zeros(())}
+        else:
+            lc, lr = self.loss_evaluator(shape, logits, reg, targets)
+            losses = {"loss_retina_cls": lc, "loss_retina_reg": lr}
+        return None, losses, {"box_cls": ops.PyramidLevels(logits, shape), "box_regression": ops.PyramidLevels(reg, shape)}
+
+
 def build_rpn(cfg, in_channels):
-    """reference modeling/rpn/rpn.py:201-212: ATSS_ON -> the ATSS head, else FCOS_ON -> the FCOS head."""
+    """reference modeling/rpn/rpn.py:201-212: ATSS_ON -> the ATSS head, else FCOS_ON -> the FCOS head, else RETINANET_ON -> the
+    RetinaNet head."""
     if in_channels != 256:
         raise ValueError("the dense heads are built for 256 input channels, got %d" % in_channels)
     if cfg.MODEL.get("ATSS_ON", False):
         return _channels_last_(ATSSModuleNCHW(cfg=config.atss_settings(cfg)))
     if not cfg.MODEL.get("FCOS_ON", False):
-        raise ValueError("MODEL.ATSS_ON and MODEL.FCOS_ON are False: only those two heads are built (no RPN / RetinaNet)")
+        if cfg.MODEL.get("RETINANET_ON", False):
+            return _channels_last_(RetinaNetModuleNCHW(cfg=config.retinanet_settings(cfg)))
+        raise ValueError("MODEL.ATSS_ON, MODEL.FCOS_ON and MODEL.RETINANET_ON are False: only those three heads are built (no RPN)")
     if not cfg.MODEL.MIDDLE_HEAD.CONDGRAPH_ON:  # the EPM baseline: the plain head, centerness where MODEL.FCOS.REG_CTR_ON puts it
         h = config.epm_settings(cfg)["head"]
         return _channels_last_(FCOSModuleNCHW(h["num_classes"], h["test_mode"], h))

@@ -630,13 +630,13 @@ def conv_pool_fusable(x, weight, bias, shape):
 
 # ----------------------------------------------------------------------------- pyramid row split
 # ----------------------------------------------------------------------------- deformable convolution (DCNv2)
-def _row_pitch(t, cols, name):
+def _row_pitch(t, cols, name, who="deform_conv2d"):
     """offset / mask operands: fp32 GPU matrices with at least `cols` columns whose rows are contiguous; a column slice of a
     wider matrix is taken as it is (its pitch is passed on)"""
     if not t.is_cuda:
         raise RuntimeError("scan_amd ops run only on the GPU (HIP) -- got a %s tensor; no CPU fallback" % t.device)
     if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] < cols or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
-        raise RuntimeError("deform_conv2d: %s must be an fp32 [M, >= %d] matrix with contiguous rows" % (name, cols))
+        raise RuntimeError("%s: %s must be an fp32 [M, >= %d] matrix with contiguous rows" % (who, name, cols))
     return t.stride(0)
 
 
@@ -1578,6 +1578,51 @@ def atss_giou_loss(pred, target, rows, weight, shape, strides, sizes):
         raise ValueError("atss_giou_loss: %d strides / %d anchor sizes for %d levels" % (len(strides), len(sizes), shape.n_levels))
     return _AtssGiouLoss.apply(pred.contiguous(), target.contiguous(), rows.contiguous(), weight.contiguous(), shape,
                                [int(s) for s in strides], [float(a) for a in sizes])
+
+
+class _RetinaSmoothL1(torch.autograd.Function):
+    """sum over the anchors with label > 0 of smooth_l1(bbox_reg slice - BoxCoder.encode(matched box, anchor)) (reference
+    rpn/retinanet/loss.py:66-71, layers/smooth_l1_loss.py with size_average=False); anchors and targets are formed in the
+    kernel (csrc/retina.hip), over all M * A anchors.  bbox_reg is read in place through its row pitch."""
+
+    @staticmethod
+    def forward(ctx, bbox_reg, geo, boxes, labels_i32, matched, beta, targets_out):
+        shape, strides, cells, A = geo
+        _chk(boxes, labels_i32, matched, cells, targets_out)
+        ld = _row_pitch(bbox_reg, 4 * A, "bbox_reg", who="retina_smooth_l1_loss")
+        out = bbox_reg.new_zeros((1,))
+        args = (shape.ref(), strides, _ptr(cells), A, _ptr(boxes), boxes.shape[1], _ptr(labels_i32), _ptr(matched), _ptr(bbox_reg),
+                ld, beta)
+        _call_reduction("scan_retina_smooth_l1", "_forward", bbox_reg, (shape.rows * A,), *args, _ptr(targets_out), _ptr(out))
+        ctx.save_for_backward(bbox_reg, boxes, labels_i32, matched, cells)
+        ctx.args = args + (shape,)  # (the shape owns the descriptor args[0] points to)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        bbox_reg = ctx.saved_tensors[0]
+        d = torch.empty(bbox_reg.shape, dtype=torch.float32, device=bbox_reg.device)
+        call("scan_retina_smooth_l1_backward", *ctx.args[:-1], _ptr(g.reshape(1).contiguous()), _ptr(d), d.shape[1], _stream())
+        return d, None, None, None, None, None, None
+
+
+def retina_smooth_l1_loss(bbox_reg, shape, strides, cells, boxes, labels_i32, matched, beta, targets_out=None):
+    """bbox_reg [M, 4 A] (a column slice of a wider row matrix is read in place through its pitch), cells [n_levels, A, 4] the
+    cell anchors on the device, boxes [N, G, 4], labels_i32 / matched [M * A] of the RetinaNet plan: the summed smooth-L1 loss
+    of the positive anchors against their encoded boxes.  targets_out [M * A, 4] (optional) receives the targets."""
+    if cells.dim() != 3 or cells.shape[0] != shape.n_levels or cells.shape[2] != 4 or len(strides) != shape.n_levels:
+        raise ValueError("retina_smooth_l1_loss: %d strides / cell anchors %r for %d levels"
+                         % (len(strides), tuple(cells.shape), shape.n_levels))
+    A = int(cells.shape[1])
+    if bbox_reg.dim() != 2 or bbox_reg.shape != (shape.rows, 4 * A):
+        raise ValueError("retina_smooth_l1_loss: bbox_reg %r for %d rows of %d anchors" % (tuple(bbox_reg.shape), shape.rows, A))
+    if labels_i32.dtype != torch.int32 or matched.dtype != torch.int32 or labels_i32.numel() != shape.rows * A \
+            or matched.numel() != shape.rows * A:
+        raise ValueError("retina_smooth_l1_loss: labels / matched must be int32 [M * A]")
+    if targets_out is not None and (targets_out.shape != (shape.rows * A, 4) or targets_out.dtype != torch.float32):
+        raise ValueError("retina_smooth_l1_loss: targets_out must be fp32 [M * A, 4]")
+    geo = (shape, (ctypes.c_int32 * shape.n_levels)(*[int(s) for s in strides]), cells, A)
+    return _RetinaSmoothL1.apply(bbox_reg, geo, boxes, labels_i32, matched, float(beta), targets_out)
 
 
 class _BceLogitsMean(torch.autograd.Function):
