@@ -25,7 +25,11 @@
 //
 // GIoU: min / max with equal arguments send the gradient to their FIRST argument (the prediction's corner in the
 // intersection / enclosure terms, x1 in x2 = max(x1, x2)); a delta exactly at the log(1000 / 16) clamp keeps its gradient.
+// The forward's sums end in block_result<ORD>; the ordered twin's second stage is ordered_sum_launch (losses.hip).
+//
+// Per-level selects, the level search, the pyramid check and the wave reductions are common.h's; boxlist_iou is boxes.h's.
 #include "common.h"
+#include "boxes.h"
 
 #define ATSS_MAX_TOPK 64
 #define ATSS_BBOX_CLIP 4.135166556742356f  // log(1000 / 16), atss.py:84-85
@@ -57,41 +61,13 @@ struct AtssLevel {
   float c0, half;
 };
 __device__ __forceinline__ AtssLevel atss_level(const AtssLevels& lv, int l) {
-  AtssLevel r = {lv.stride[0], lv.c0[0], lv.half[0]};
-#pragma unroll
-  for (int i = 1; i < SCAN_MAX_LEVELS; ++i)
-    if (l == i) {
-      r.s = lv.stride[i];
-      r.c0 = lv.c0[i];
-      r.half = lv.half[i];
-    }
-  return r;
-}
-__device__ __forceinline__ int level_h(const scan_pyramid_t& d, int l) {
-  int r = d.h[0];
-#pragma unroll
-  for (int i = 1; i < SCAN_MAX_LEVELS; ++i)
-    if (l == i) r = d.h[i];
-  return r;
-}
-__device__ __forceinline__ int level_w(const scan_pyramid_t& d, int l) {
-  int r = d.w[0];
-#pragma unroll
-  for (int i = 1; i < SCAN_MAX_LEVELS; ++i)
-    if (l == i) r = d.w[i];
-  return r;
-}
-__device__ __forceinline__ int64_t level_off(const scan_pyramid_t& d, int l) {
-  int64_t r = d.row_off[0];
-#pragma unroll
-  for (int i = 1; i < SCAN_MAX_LEVELS; ++i)
-    if (l == i) r = d.row_off[i];
-  return r;
+  return {pick_level(lv.stride, l), pick_level(lv.c0, l), pick_level(lv.half, l)};
 }
 
 // anchor of cell (y, x): centre and corners (xyxy)
 struct Anchor {
   float cx, cy, x1, y1, x2, y2;
+  __device__ __forceinline__ float4 box() const { return make_float4(x1, y1, x2, y2); }
 };
 __device__ __forceinline__ Anchor anchor_of(const AtssLevel lv, int y, int x) {
   Anchor a;
@@ -102,22 +78,6 @@ __device__ __forceinline__ Anchor anchor_of(const AtssLevel lv, int y, int x) {
   a.x2 = a.cx + lv.half;
   a.y2 = a.cy + lv.half;
   return a;
-}
-
-__device__ __forceinline__ unsigned long long shfl_down_u64(unsigned long long v, int off) {
-  const unsigned lo = __shfl_down((unsigned)(v & 0xffffffffull), off, 64);
-  const unsigned hi = __shfl_down((unsigned)(v >> 32), off, 64);
-  return ((unsigned long long)hi << 32) | lo;
-}
-
-// boxlist_iou(anchor, box), TO_REMOVE = 1
-__device__ __forceinline__ float atss_iou(const Anchor a, const float4 b) {
-  const float area1 = (a.x2 - a.x1 + 1.f) * (a.y2 - a.y1 + 1.f);
-  const float area2 = (b.z - b.x + 1.f) * (b.w - b.y + 1.f);
-  const float w = fmaxf(fminf(a.x2, b.z) - fmaxf(a.x1, b.x) + 1.f, 0.f);
-  const float h = fmaxf(fminf(a.y2, b.w) - fmaxf(a.y1, b.y) + 1.f, 0.f);
-  const float inter = w * h;
-  return inter / (area1 + area2 - inter);
 }
 
 // grid (n_levels, G, N).  cand_row / cand_iou [N][G][n_levels][topk]; unused slots: row -1
@@ -134,8 +94,8 @@ __global__ __launch_bounds__(256) void atss_candidates_kernel(scan_pyramid_t d, 
     return;
   }
   const AtssLevel lv = atss_level(lvs, l);
-  const int H = level_h(d, l), W = level_w(d, l), hw = H * W;
-  const int64_t row0 = level_off(d, l) + (int64_t)n * hw;
+  const int H = pick_level(d.h, l), W = pick_level(d.w, l), hw = H * W;
+  const int64_t row0 = pick_level(d.row_off, l) + (int64_t)n * hw;
   const float4 b = *reinterpret_cast<const float4*>(boxes + ((int64_t)n * G + g) * 4);
   const float gcx = (b.z + b.x) / 2.0f, gcy = (b.w + b.y) / 2.0f;
   const int k = topk < hw ? topk : hw;
@@ -156,11 +116,7 @@ __global__ __launch_bounds__(256) void atss_candidates_kernel(scan_pyramid_t d, 
         ++y;
       }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const unsigned long long o = shfl_down_u64(best, off);
-      best = o < best ? o : best;
-    }
+    best = wave_min_u64(best);
     if (lane == 0) wmin[wid] = best;
     __syncthreads();
     if (tid == 0) {
@@ -170,7 +126,7 @@ __global__ __launch_bounds__(256) void atss_candidates_kernel(scan_pyramid_t d, 
       const int i = (int)(m & 0xffffffffull);
       const int yy = i / W, xx = i - yy * W;
       cand_row[slot0 + round] = (int32_t)(row0 + i);
-      cand_iou[slot0 + round] = atss_iou(anchor_of(lv, yy, xx), b);
+      cand_iou[slot0 + round] = boxlist_iou(anchor_of(lv, yy, xx).box(), b);
     }
     __syncthreads();
     last = chosen;
@@ -215,8 +171,8 @@ __global__ __launch_bounds__(64) void atss_vote_kernel(scan_pyramid_t d, AtssLev
     const float iou = cand_iou[slot0 + c];
     const int l = c / topk;
     const AtssLevel lv = atss_level(lvs, l);
-    const int W = level_w(d, l), hw = level_h(d, l) * W;
-    const int i = (int)(row - level_off(d, l) - (int64_t)n * hw);
+    const int W = pick_level(d.w, l), hw = pick_level(d.h, l) * W;
+    const int i = (int)(row - pick_level(d.row_off, l) - (int64_t)n * hw);
     const int y = i / W, x = i - y * W;
     const float cx = (float)(x * lv.s) + lv.c0, cy = (float)(y * lv.s) + lv.c0;
     const float mn = fminf(fminf(cx - b.x, cy - b.y), fminf(b.z - cx, b.w - cy));
@@ -271,11 +227,8 @@ __global__ __launch_bounds__(256) void atss_targets_kernel(scan_pyramid_t d, Ats
                                                            float* __restrict__ ctr_pos) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= t.pos_off[d.n_levels]) return;
-  int l = 0;
-#pragma unroll
-  for (int k = 1; k < SCAN_MAX_LEVELS; ++k)
-    if (k < d.n_levels && p >= t.pos_off[k]) l = k;
-  const int64_t row = pos_list[level_off(d, l) + (p - t.pos_off[l])];
+  const int l = level_of(t.pos_off, d.n_levels, p);
+  const int64_t row = pos_list[pick_level(d.row_off, l) + (p - t.pos_off[l])];
   const RowCoord rc = decode_row(d, row);
   const Anchor a = anchor_of(atss_level(lvs, rc.lvl), rc.y, rc.x);
   const float4 b = *reinterpret_cast<const float4*>(boxes + ((int64_t)rc.n * G + matched[row]) * 4);
@@ -299,12 +252,9 @@ __global__ __launch_bounds__(256) void atss_targets_kernel(scan_pyramid_t d, Ats
   ctr_pos[p] = (float)sqrt((fmin(cl, cr) / fmax(cl, cr)) * (fmin(ct, cb) / fmax(ct, cb)));
 }
 
-static int atss_check_plan(const scan_pyramid_t* d, const char* who) {
-  SCAN_CHECK_ARG(d && d->n_levels >= 1 && d->n_levels <= SCAN_MAX_LEVELS && d->n_images >= 1, "%s: bad pyramid", who);
-  for (int l = 0; l < d->n_levels; ++l)
-    SCAN_CHECK_ARG(d->h[l] >= 1 && d->w[l] >= 1 && (int64_t)d->h[l] * d->w[l] < (1ll << 31) &&
-                       d->row_off[l + 1] - d->row_off[l] == (int64_t)d->n_images * d->h[l] * d->w[l],
-                   "%s: level %d of the pyramid is inconsistent", who, l);
+// the shared check, and row indices that fit the int32 lists (candidates, scan_fcos_compact's positives)
+static int atss_check(const scan_pyramid_t* d, const char* who) {
+  if (scan_check_pyramid(d, who)) return -1;
   SCAN_CHECK_ARG(d->row_off[d->n_levels] < (1ll << 31), "%s: more than 2^31 rows", who);
   return 0;
 }
@@ -319,7 +269,7 @@ extern "C" int64_t scan_atss_assign_ws_bytes(const scan_pyramid_t* d, int32_t G,
 extern "C" int scan_atss_assign(const scan_pyramid_t* d, const int32_t* strides, const float* anchor_sizes, const float* boxes,
                                 const int64_t* glabels, const int32_t* ng, int32_t G, int32_t topk, int64_t* labels,
                                 int32_t* labels_i32, int32_t* matched, int32_t* level_pos, void* ws, void* stream) {
-  if (atss_check_plan(d, "atss_assign")) return -1;
+  if (atss_check(d, "atss_assign")) return -1;
   SCAN_CHECK_ARG(strides && anchor_sizes && boxes && glabels && ng && labels && labels_i32 && matched && level_pos && ws,
                  "atss_assign: null pointer");
   SCAN_CHECK_ARG(G >= 1 && G <= 65535 && d->n_images <= 65535, "atss_assign: G=%d / N=%d outside 1..65535", G, d->n_images);
@@ -354,7 +304,7 @@ extern "C" int scan_atss_assign(const scan_pyramid_t* d, const int32_t* strides,
 extern "C" int scan_atss_targets(const scan_pyramid_t* d, const int32_t* strides, const float* anchor_sizes,
                                  const int32_t* level_pos, const float* boxes, int32_t G, const int32_t* matched,
                                  const int32_t* pos_list, int64_t* pos_inds, float* reg_pos, float* ctr_pos, void* stream) {
-  if (atss_check_plan(d, "atss_targets")) return -1;
+  if (atss_check(d, "atss_targets")) return -1;
   SCAN_CHECK_ARG(strides && anchor_sizes && level_pos && boxes && matched && pos_list && G >= 1,
                  "atss_targets: null pointer or G < 1");
   AtssLevels lv;
@@ -441,23 +391,9 @@ __global__ __launch_bounds__(256) void giou_fwd_kernel(scan_pyramid_t d, AtssLev
   const float sn = block_sum_256(num, red);
   const float sd = block_sum_256(den, red);
   if (threadIdx.x == 0) {
-    if (ORD) {
-      out2[2 * blockIdx.x] = sn;
-      out2[2 * blockIdx.x + 1] = sd;
-    } else {
-      atomicAdd(&out2[0], sn);
-      atomicAdd(&out2[1], sd);
-    }
+    block_result<ORD>(out2, 0, 2, sn);
+    block_result<ORD>(out2, 1, 2, sd);
   }
-}
-
-// the blocks' slots in one fixed order: lane l of wave k adds slots l, l + 64, ... of column k, then wave_sum's fixed tree
-__global__ __launch_bounds__(128) void giou_ordered_sum_kernel(const float* __restrict__ part, int nblk, float* __restrict__ out2) {
-  const int lane = threadIdx.x & 63, k = threadIdx.x >> 6;
-  float s = 0.f;
-  for (int b = lane; b < nblk; b += 64) s += part[2 * b + k];
-  s = wave_sum(s);
-  if (lane == 0) out2[k] = s;
 }
 
 __global__ __launch_bounds__(256) void giou_bwd_kernel(scan_pyramid_t d, AtssLevels lvs, const float* __restrict__ pred,
@@ -509,15 +445,9 @@ __global__ __launch_bounds__(256) void giou_bwd_kernel(scan_pyramid_t d, AtssLev
   }
 }
 
-// one block per 2,048 boxes, at most 256: the grid is a function of P alone, so is the ordered sum
-static inline int giou_grid(int64_t P) {
-  int64_t g = (P + 2047) / 2048;
-  return (int)(g < 1 ? 1 : (g > 256 ? 256 : g));
-}
-
 static int giou_check(const scan_pyramid_t* d, const int32_t* strides, const float* sizes, const float* pred,
                       const float* target, const int64_t* rows, const float* weight, AtssLevels* lv, const char* who) {
-  if (atss_check_plan(d, who)) return -1;
+  if (atss_check(d, who)) return -1;
   SCAN_CHECK_ARG(strides && sizes, "%s: null strides / anchor sizes", who);
   if (atss_levels(lv, d, strides, sizes, who)) return -1;
   SCAN_CHECK_ARG(pred && target && rows && weight, "%s: null input", who);
@@ -526,9 +456,9 @@ static int giou_check(const scan_pyramid_t* d, const int32_t* strides, const flo
   return 0;
 }
 
-extern "C" int64_t scan_atss_giou_ordered_ws_floats(int64_t P) { return 2 * (int64_t)giou_grid(P); }
+extern "C" int64_t scan_atss_giou_ordered_ws_floats(int64_t P) { return 2 * (int64_t)head_loss_grid(P); }
 
-// ORD = false: float atomics on out2.  ORD = true: the blocks' sums go to ws [giou_grid(P)][2], giou_ordered_sum_kernel forms out2
+// ORD = false: float atomics on out2.  ORD = true: the blocks' sums go to ws [head_loss_grid(P)][2], ordered_sum_launch forms out2
 template <bool ORD>
 static int giou_forward_launch(const scan_pyramid_t* d, const int32_t* strides, const float* anchor_sizes, const float* pred,
                                const float* target, const int64_t* rows, const float* weight, int64_t P, float* out2, float* ws,
@@ -537,15 +467,11 @@ static int giou_forward_launch(const scan_pyramid_t* d, const int32_t* strides, 
   if (P == 0) return 0;
   AtssLevels lv;
   if (giou_check(d, strides, anchor_sizes, pred, target, rows, weight, &lv, who)) return -1;
-  const int grid = giou_grid(P);
+  const int grid = head_loss_grid(P);
   hipLaunchKernelGGL(giou_fwd_kernel<ORD>, dim3(grid), dim3(256), 0, as_stream(stream), *d, lv, pred, target, rows, weight, P,
                      ORD ? ws : out2);
   SCAN_LAUNCH_CHECK(ORD ? "atss_giou_fwd_ordered" : "atss_giou_fwd");
-  if (ORD) {
-    hipLaunchKernelGGL(giou_ordered_sum_kernel, dim3(1), dim3(128), 0, as_stream(stream), ws, grid, out2);
-    SCAN_LAUNCH_CHECK("atss_giou_fwd_ordered_sum");
-  }
-  return 0;
+  return ORD ? ordered_sum_launch(ws, grid, 2, out2, 0, nullptr, stream, "atss_giou_fwd_ordered_sum") : 0;
 }
 
 extern "C" int scan_atss_giou_forward(const scan_pyramid_t* d, const int32_t* strides, const float* anchor_sizes,

@@ -69,10 +69,7 @@ __global__ __launch_bounds__(256) void row_scale_levels_kernel(RowScaleLevels L,
   for (idx_t e = (idx_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += step) {
     const idx_t m = e / (idx_t)c4;
     const int c = (int)(e - m * (idx_t)c4) << 2;
-    int lvl = 0;
-#pragma unroll
-    for (int i = 1; i < SCAN_MAX_LEVELS; ++i)
-      if (i < d.n_levels && (int64_t)m >= d.row_off[i]) lvl = i;
+    const int lvl = level_of(d.row_off, d.n_levels, (int64_t)m);
     const float* xl = L.x[lvl];
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (xl) {

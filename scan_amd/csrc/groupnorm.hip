@@ -31,10 +31,7 @@ struct GnBlock {
 };
 __device__ __forceinline__ GnBlock gn_block(const scan_pyramid_t& d, const GnTab& t) {
   GnBlock b;
-  int lvl = 0;
-#pragma unroll
-  for (int i = 1; i < SCAN_MAX_LEVELS; ++i)
-    if (i < d.n_levels && (int)blockIdx.x >= t.blk_off[i]) lvl = i;
+  const int lvl = level_of(t.blk_off, d.n_levels, (int)blockIdx.x);
   const int r = blockIdx.x - t.blk_off[lvl];
   const int n = r / t.per_img[lvl], chunk = r - n * t.per_img[lvl];
   b.il = lvl * d.n_images + n;

@@ -3,7 +3,8 @@
 // allows, grid-stride loops.  Every forward that ends in a sum has ONE host launcher, template <bool ORD>: it owns the argument
 // checks, the choice of kernel form, the grid and the launch for the atomic entry point (ORD = false) and for its *_ordered twin
 // (ORD = true: the blocks' sums go to a workspace, ordered_sum_kernel adds them up); the *_ordered_ws_floats query of a loss
-// calls the grid function its launcher calls.
+// calls the grid function its launcher calls.  The first stage of an ordered sum (block_result<ORD>) is in common.h; the second
+// (ordered_sum_kernel, ordered_sum_launch) is here, once for the library: the heads' losses in atss.hip and retina.hip use it too.
 #include <float.h>
 
 #include "common.h"
@@ -99,20 +100,7 @@ __device__ __forceinline__ void focal_rowcol(int64_t q, int C, const int* __rest
   }
 }
 
-// ------------------------------------------------------------------ ordered reductions (scan_tune "deterministic")
-// Every reducing kernel below ends in one line: the block's partial sum goes to `dst`.  ORD = false (the product default):
-// a float atomic on dst[k] -- fastest, but the sum then depends on the order the blocks arrive in.  ORD = true (the *_ordered
-// entry points): an ordinary store to the block's own slot dst[blockIdx.x][k] of a caller-supplied workspace, which
-// ordered_sum_kernel -- a launch of its own behind the kernel -- adds up in a fixed order.  A second launch, not the
-// last-arriving block: stream order makes every slot visible to it with no fence, ticket or device-scope read-back (the
-// per-XCD L2s are not coherent: a last block would have to read 2,048 slots back past its own L2), and no block ever
-// depends on another.
-template <bool ORD>
-__device__ __forceinline__ void block_result(float* __restrict__ dst, int k, int ncols, float v) {
-  if (ORD) dst[(int64_t)blockIdx.x * ncols + k] = v;
-  else atomicAdd(dst + k, v);
-}
-
+// ------------------------------------------------------------------ ordered reductions: the second stage (common.h has the first)
 #define CKA_MAXC 32  // foreground classes: scan_dynconv_max_classes() - 1 fit
 // Second stage: out[k] = sum over the blocks' slots part[b][k], b < nblk, in one fixed order -- lane l of the wave that owns
 // column k adds slots l, l + 64, l + 128, ... in ascending order, then the 64 lane sums go through wave_sum's fixed shuffle
@@ -141,8 +129,7 @@ __global__ __launch_bounds__(256) void ordered_sum_kernel(const float* __restric
   }
 }
 
-static int ordered_sum_launch(const float* part, int nblk, int ncols, float* out, int Cf, float* fin, void* stream,
-                              const char* who) {
+int ordered_sum_launch(const float* part, int nblk, int ncols, float* out, int Cf, float* fin, void* stream, const char* who) {
   hipLaunchKernelGGL(ordered_sum_kernel, dim3(1), dim3(256), 0, as_stream(stream), part, nblk, ncols, out, Cf, fin);
   SCAN_LAUNCH_CHECK(who);
   return 0;

@@ -315,10 +315,7 @@ __global__ __launch_bounds__(256) void take_images_bwd_kernel(const float* __res
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
     const int64_t m = e / C;
     const int c = (int)(e - m * C);
-    int lvl = 0;
-#pragma unroll
-    for (int i = 1; i < SCAN_MAX_LEVELS; ++i)
-      if (i < d.n_levels && m >= d.row_off[i]) lvl = i;
+    const int lvl = level_of(d.row_off, d.n_levels, m);
     const int64_t hw = (int64_t)d.h[lvl] * d.w[lvl];
     const int64_t r = m - d.row_off[lvl];
     const int64_t n = r / hw;

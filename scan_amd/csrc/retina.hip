@@ -6,7 +6,7 @@
 // a < A; anchor index i = m * A + a, which is the reference's order level by level (a head output row [A * C] is A anchors of C
 // classes).  The anchors are never stored: every kernel forms them from the row and the cell table [n_levels][A][4], a tiny
 // device buffer.  This file is built with -ffp-contract=off: the IoU is boxlist_iou's (structures/boxlist_ops.py) in fp32 with
-// every operation rounded on its own, so its bits are torch-CPU's, and the two passes below recompute identical bits.
+// every operation rounded on its own (boxes.h), so its bits are torch-CPU's, and the two passes below recompute identical bits.
 //
 // The plan, per image n with ng[n] real boxes (padding boxes beyond ng[n] take no part; ng[n] = 0: all background, where the
 // reference raises):
@@ -23,8 +23,12 @@
 // Smooth-L1 runs over ALL anchors, no compaction: where label > 0 the target is encode(boxes[n][matched], anchor) with weights
 // (10, 10, 5, 5) and TO_REMOVE = 1, formed in fp64 and rounded to fp32 once (as scan_atss_targets), compared with the four
 // columns [4a, 4a + 4) of row m of bbox_reg (row pitch ld floats); loss = 0.5 d^2 / beta where |d| < beta, |d| - 0.5 beta
-// elsewhere, summed.  The backward writes d_pred for every anchor (zero where label <= 0).
+// elsewhere, summed (block_result<ORD>; the ordered twin's second stage is ordered_sum_launch of losses.hip).  The backward
+// writes d_pred for every anchor (zero where label <= 0).
+//
+// Per-level selects, the pyramid check and the wave reductions are common.h's; boxlist_iou is boxes.h's (box first here).
 #include "common.h"
+#include "boxes.h"
 
 #define RETINA_MAX_A 16
 
@@ -32,48 +36,13 @@ struct RetinaStrides {
   int s[SCAN_MAX_LEVELS];
 };
 
-__device__ __forceinline__ int stride_of(const RetinaStrides& st, int l) {
-  int r = st.s[0];
-#pragma unroll
-  for (int i = 1; i < SCAN_MAX_LEVELS; ++i)
-    if (l == i) r = st.s[i];
-  return r;
-}
-
 // anchor a of row rc: the cell anchor plus the location's shift, one fp32 addition per corner (anchor_generator.py:73-95)
 __device__ __forceinline__ float4 retina_anchor(const RetinaStrides& st, const float* __restrict__ cells, int A, const RowCoord rc,
                                                 int a) {
   const float4 c = *reinterpret_cast<const float4*>(cells + ((int64_t)rc.lvl * A + a) * 4);
-  const int s = stride_of(st, rc.lvl);
+  const int s = pick_level(st.s, rc.lvl);
   const float sx = (float)(rc.x * s), sy = (float)(rc.y * s);
   return make_float4(c.x + sx, c.y + sy, c.z + sx, c.w + sy);
-}
-
-// boxlist_iou(box, anchor), TO_REMOVE = 1
-__device__ __forceinline__ float retina_iou(const float4 b, const float4 a) {
-  const float area1 = (b.z - b.x + 1.f) * (b.w - b.y + 1.f);
-  const float area2 = (a.z - a.x + 1.f) * (a.w - a.y + 1.f);
-  const float w = fmaxf(fminf(b.z, a.z) - fmaxf(b.x, a.x) + 1.f, 0.f);
-  const float h = fmaxf(fminf(b.w, a.w) - fmaxf(b.y, a.y) + 1.f, 0.f);
-  const float inter = w * h;
-  return inter / (area1 + area2 - inter);
-}
-
-__device__ __forceinline__ int wave_max_i32(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const int o = __shfl_xor(v, off, 64);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned o = __shfl_xor(v, off, 64);
-    v = o > v ? o : v;
-  }
-  return v;
 }
 
 // pass 1: gt_max[n * G + g] (zeroed by the caller).  All 64 lanes of a wave stay in the loop together (the shuffles need them).
@@ -96,14 +65,14 @@ __global__ __launch_bounds__(256) void retina_gtmax_kernel(scan_pyramid_t d, Ret
       cnt = cnt < G ? cnt : G;
       an = retina_anchor(st, cells, A, rc, (int)(i - m * A));
     }
-    const int gmax = wave_max_i32(cnt);
+    const int gmax = wave_max(cnt);
     const int n0 = __shfl(n, 0, 64);
     const bool uniform = __all(n == n0);  // every lane live and of one image: one atomic per box for the wave
     for (int g = 0; g < gmax; ++g) {
       unsigned v = 0u;
-      if (g < cnt) v = __float_as_uint(retina_iou(*reinterpret_cast<const float4*>(boxes + ((int64_t)n * G + g) * 4), an));
+      if (g < cnt) v = __float_as_uint(boxlist_iou(*reinterpret_cast<const float4*>(boxes + ((int64_t)n * G + g) * 4), an));
       if (uniform) {
-        const unsigned wv = wave_max_u32(v);
+        const unsigned wv = wave_max(v);
         if ((threadIdx.x & 63) == 0 && wv != 0u) atomicMax(&gt_max[(int64_t)n0 * G + g], wv);
       } else if (v != 0u) {
         atomicMax(&gt_max[(int64_t)n * G + g], v);
@@ -132,7 +101,7 @@ __global__ __launch_bounds__(256) void retina_labels_kernel(scan_pyramid_t d, Re
     int arg = 0;
     bool low = false;
     for (int g = 0; g < cnt; ++g) {
-      const float v = retina_iou(*reinterpret_cast<const float4*>(boxes + ((int64_t)rc.n * G + g) * 4), an);
+      const float v = boxlist_iou(*reinterpret_cast<const float4*>(boxes + ((int64_t)rc.n * G + g) * 4), an);
       if (v > best) {
         best = v;
         arg = g;
@@ -149,8 +118,7 @@ __global__ __launch_bounds__(256) void retina_labels_kernel(scan_pyramid_t d, Re
     matched[i] = lab > 0 ? arg : 0;
     pos += lab > 0 ? 1 : 0;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) pos += __shfl_down(pos, off, 64);
+  pos = wave_sum(pos);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = pos;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -161,11 +129,7 @@ __global__ __launch_bounds__(256) void retina_labels_kernel(scan_pyramid_t d, Re
 
 static int retina_check(const scan_pyramid_t* d, const int32_t* strides, const float* cells, int32_t A, RetinaStrides* st,
                         const char* who) {
-  SCAN_CHECK_ARG(d && d->n_levels >= 1 && d->n_levels <= SCAN_MAX_LEVELS && d->n_images >= 1, "%s: bad pyramid", who);
-  for (int l = 0; l < d->n_levels; ++l)
-    SCAN_CHECK_ARG(d->h[l] >= 1 && d->w[l] >= 1 && (int64_t)d->h[l] * d->w[l] < (1ll << 31) &&
-                       d->row_off[l + 1] - d->row_off[l] == (int64_t)d->n_images * d->h[l] * d->w[l],
-                   "%s: level %d of the pyramid is inconsistent", who, l);
+  if (scan_check_pyramid(d, who)) return -1;
   SCAN_CHECK_ARG(A >= 1 && A <= RETINA_MAX_A, "%s: A=%d anchors per location outside 1..%d", who, A, RETINA_MAX_A);
   SCAN_CHECK_ARG(d->row_off[d->n_levels] * A < (1ll << 40), "%s: too many anchors", who);
   SCAN_CHECK_ARG(strides && cells, "%s: null strides / cell anchors", who);
@@ -261,7 +225,7 @@ __device__ __forceinline__ float smooth_l1_grad(float x, float t, float beta) {
   return fabsf(e) < beta ? e / beta : (e > 0.f ? 1.f : -1.f);
 }
 
-// ORD: every block writes its sum to its own slot out[blockIdx.x] instead of adding it to out[0]
+// ORD: every block writes its sum to its own slot out[blockIdx.x] instead of adding it to out[0] (block_result)
 template <bool ORD>
 __global__ __launch_bounds__(256) void smooth_l1_fwd_kernel(SmoothL1Args p, float* __restrict__ targets_out, float* __restrict__ out) {
   __shared__ float red[4];
@@ -279,18 +243,7 @@ __global__ __launch_bounds__(256) void smooth_l1_fwd_kernel(SmoothL1Args p, floa
     if (targets_out != nullptr) reinterpret_cast<float4*>(targets_out)[i] = t;
   }
   const float s = block_sum_256(acc, red);
-  if (threadIdx.x == 0) {
-    if (ORD) out[blockIdx.x] = s;
-    else atomicAdd(out, s);
-  }
-}
-
-// the blocks' slots in one fixed order: lane l adds slots l, l + 64, ..., then wave_sum's fixed tree
-__global__ __launch_bounds__(64) void smooth_l1_ordered_sum_kernel(const float* __restrict__ part, int nblk, float* __restrict__ out) {
-  float s = 0.f;
-  for (int b = threadIdx.x; b < nblk; b += 64) s += part[b];
-  s = wave_sum(s);
-  if (threadIdx.x == 0) out[0] = s;
+  if (threadIdx.x == 0) block_result<ORD>(out, 0, 1, s);
 }
 
 __global__ __launch_bounds__(256) void smooth_l1_bwd_kernel(SmoothL1Args p, const float* __restrict__ g_dev,
@@ -311,13 +264,7 @@ __global__ __launch_bounds__(256) void smooth_l1_bwd_kernel(SmoothL1Args p, cons
   }
 }
 
-// one block per 2,048 anchors, at most 256: the grid is a function of the anchor count alone, so is the ordered sum
-static inline int smooth_l1_grid(int64_t total) {
-  int64_t g = (total + 2047) / 2048;
-  return (int)(g < 1 ? 1 : (g > 256 ? 256 : g));
-}
-
-extern "C" int64_t scan_retina_smooth_l1_ordered_ws_floats(int64_t n_anchors) { return smooth_l1_grid(n_anchors); }
+extern "C" int64_t scan_retina_smooth_l1_ordered_ws_floats(int64_t n_anchors) { return head_loss_grid(n_anchors); }
 
 static int smooth_l1_args(SmoothL1Args* p, const scan_pyramid_t* d, const int32_t* strides, const float* cells, int32_t A,
                           const float* boxes, int32_t G, const int32_t* labels, const int32_t* matched, const float* pred,
@@ -352,14 +299,10 @@ static int smooth_l1_forward_launch(const scan_pyramid_t* d, const int32_t* stri
   if (smooth_l1_args(&p, d, strides, cells, A, boxes, G, labels, matched, pred, ld, beta, who)) return -1;
   SCAN_CHECK_ARG(out && (!ORD || ws), "%s: null output", who);
   SCAN_CHECK_ARG((reinterpret_cast<uintptr_t>(targets_out) & 15) == 0, "%s: targets_out must be 16-byte aligned", who);
-  const int grid = smooth_l1_grid(d->row_off[d->n_levels] * A);
+  const int grid = head_loss_grid(d->row_off[d->n_levels] * A);
   hipLaunchKernelGGL(smooth_l1_fwd_kernel<ORD>, dim3(grid), dim3(256), 0, as_stream(stream), p, targets_out, ORD ? ws : out);
   SCAN_LAUNCH_CHECK(ORD ? "retina_smooth_l1_fwd_ordered" : "retina_smooth_l1_fwd");
-  if (ORD) {
-    hipLaunchKernelGGL(smooth_l1_ordered_sum_kernel, dim3(1), dim3(64), 0, as_stream(stream), ws, grid, out);
-    SCAN_LAUNCH_CHECK("retina_smooth_l1_fwd_ordered_sum");
-  }
-  return 0;
+  return ORD ? ordered_sum_launch(ws, grid, 1, out, 0, nullptr, stream, "retina_smooth_l1_fwd_ordered_sum") : 0;
 }
 
 extern "C" int scan_retina_smooth_l1_forward(const scan_pyramid_t* d, const int32_t* strides, const float* cells, int32_t A,

@@ -10,7 +10,9 @@
 // iteration; here the host reads five counters once.  Integer / index work and single fp32 operations in the reference's
 // order: bit-identical to the torch spelling (tests/test_gpu_kernels.py::test_target_plan_kernels_equal_torch_plan) and to
 // the host oracle of tests/targets_ref.py at ties, boundary equalities, zero positives, images without boxes and short
-// pyramids, with guarded outputs (tests/test_gpu_targets.py).
+// pyramids, with guarded outputs (tests/test_gpu_targets.py).  Every entry point starts with scan_check_pyramid (common.h): a
+// descriptor whose levels do not hold n_images * h * w rows each is refused before any launch (decode_row would read past the
+// images' box counts with it).
 #include "common.h"
 
 #define FCOS_INF 100000000.0f  // reference rpn/fcos/loss.py:22
@@ -28,15 +30,8 @@ __global__ __launch_bounds__(256) void fcos_assign_kernel(scan_pyramid_t d, Fcos
   const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= d.row_off[d.n_levels]) return;
   const RowCoord rc = decode_row(d, m);
-  int s = lv.stride[0];
-  float lo = lv.lo[0], hi = lv.hi[0];
-#pragma unroll
-  for (int i = 1; i < SCAN_MAX_LEVELS; ++i)
-    if (rc.lvl == i) {
-      s = lv.stride[i];
-      lo = lv.lo[i];
-      hi = lv.hi[i];
-    }
+  const int s = pick_level(lv.stride, rc.lvl);
+  const float lo = pick_level(lv.lo, rc.lvl), hi = pick_level(lv.hi, rc.lvl);
   // compute_locations (fcos.py:234-258): arange(0, w * s, s) + s // 2
   const float xs = (float)(rc.x * s) + (float)(s / 2), ys = (float)(rc.y * s) + (float)(s / 2);
   const float* bx = boxes + (int64_t)rc.n * G * 4;
@@ -118,17 +113,8 @@ __global__ __launch_bounds__(256) void fcos_nodes_kernel(scan_pyramid_t d, FcosN
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= picks + npos) return;
   if (i < picks) {
-    int l = 0;
-#pragma unroll
-    for (int k = 1; k < SCAN_MAX_LEVELS; ++k)
-      if (k < d.n_levels && i >= t.pick_off[k]) l = k;
-    int np = t.n_pos[0], nn = t.n_neg[0];
-#pragma unroll
-    for (int k = 1; k < SCAN_MAX_LEVELS; ++k)
-      if (l == k) {
-        np = t.n_pos[k];
-        nn = t.n_neg[k];
-      }
+    const int l = level_of(t.pick_off, d.n_levels, i);
+    const int np = pick_level(t.n_pos, l), nn = pick_level(t.n_neg, l);
     const int j = i - t.pick_off[l];
     long long idx = j;  // n_pos > n_neg: every background row
     if (np <= nn) {
@@ -148,10 +134,7 @@ __global__ __launch_bounds__(256) void fcos_nodes_kernel(scan_pyramid_t d, FcosN
     return;
   }
   const int p = i - picks;
-  int l = 0;
-#pragma unroll
-  for (int k = 1; k < SCAN_MAX_LEVELS; ++k)
-    if (k < d.n_levels && p >= t.pos_off[k]) l = k;
+  const int l = level_of(t.pos_off, d.n_levels, p);
   const int64_t row = pos_list[d.row_off[l] + (p - t.pos_off[l])];
   node_index[i] = row;
   node_labels[i] = labels[row];
@@ -166,7 +149,7 @@ __global__ __launch_bounds__(256) void fcos_nodes_kernel(scan_pyramid_t d, FcosN
 extern "C" int scan_fcos_assign(const scan_pyramid_t* d, const int32_t* strides, const float* soi, const float* boxes,
                                 const int64_t* glabels, const int32_t* ng, int32_t G, int64_t* labels,
                                 int32_t* labels_i32, float* reg, int32_t* level_pos, void* stream) {
-  SCAN_CHECK_ARG(d && d->n_levels >= 1 && d->n_levels <= SCAN_MAX_LEVELS && d->n_images >= 1, "fcos_assign: bad pyramid");
+  if (scan_check_pyramid(d, "fcos_assign")) return -1;
   SCAN_CHECK_ARG(strides && soi && boxes && glabels && ng && labels && labels_i32 && reg && level_pos && G >= 1,
                  "fcos_assign: null pointer or G < 1");
   FcosLevels lv;
@@ -189,7 +172,7 @@ extern "C" int scan_fcos_assign(const scan_pyramid_t* d, const int32_t* strides,
 
 extern "C" int scan_fcos_compact(const scan_pyramid_t* d, const int64_t* labels, int32_t* pos_list, int32_t* neg_list,
                                  void* stream) {
-  SCAN_CHECK_ARG(d && d->n_levels >= 1 && d->n_levels <= SCAN_MAX_LEVELS, "fcos_compact: bad pyramid");
+  if (scan_check_pyramid(d, "fcos_compact")) return -1;
   SCAN_CHECK_ARG(labels && pos_list && neg_list, "fcos_compact: null pointer");
   SCAN_CHECK_ARG(d->row_off[d->n_levels] < (1ll << 31), "fcos_compact: more than 2^31 rows");
   hipLaunchKernelGGL(fcos_compact_kernel, dim3(d->n_levels), dim3(1024), 0, as_stream(stream), *d, labels, pos_list,
@@ -211,7 +194,7 @@ extern "C" int64_t scan_fcos_nodes_count(const scan_pyramid_t* d, const int32_t*
 extern "C" int scan_fcos_nodes(const scan_pyramid_t* d, const int32_t* level_pos, const int64_t* labels, const float* reg,
                                const int32_t* pos_list, const int32_t* neg_list, int64_t* node_index,
                                int64_t* node_labels, int64_t* pos_inds, float* reg_pos, float* ctr_pos, void* stream) {
-  SCAN_CHECK_ARG(d && d->n_levels >= 1 && d->n_levels <= SCAN_MAX_LEVELS, "fcos_nodes: bad pyramid");
+  if (scan_check_pyramid(d, "fcos_nodes")) return -1;
   SCAN_CHECK_ARG(level_pos && labels && reg && pos_list && neg_list, "fcos_nodes: null pointer");
   FcosNodeTab t;
   t.pick_off[0] = t.pos_off[0] = 0;

@@ -17,10 +17,10 @@ import torch.distributed as dist
 from . import config, ops, synth
 from .engine import DIS_ORDER, LEVELS, FlatGroup, _padded_shape, _plan_stream, warmup_factor
 from .modeling import fcos as fcos_mod
-from .modeling.atss import ATSSModule, _event_if_device, build_atss
+from .modeling.atss import ATSSModule, build_atss
 from .modeling.backbone import build_backbone
 from .modeling.discriminator import FCOSDiscriminator, FCOSDiscriminator_CA
-from .modeling.fcos import FCOSModule
+from .modeling.fcos import FCOSModule, _event_if_device
 from .modeling.resnet import build_resnet_fpn_backbone
 from .structures import to_image_list
 

@@ -312,21 +312,12 @@ class ATSSModule(nn.Module):
                 return None, {"zero": rows.new_zeros(())}
             if rows.is_cuda:  # the plan's host read hides behind the head's convolutions
                 self.loss_evaluator.plan(shape, targets, rows.device, side_stream=ops.borrow_side_streams(3)[0],
-                                         after=_event_if_device(targets))
+                                         after=fcos_mod._event_if_device(targets))
             logits, reg, ctr = self.head(rows, shape)
             lc, lr, lctr = self.loss_evaluator(shape, logits, reg, ctr, targets)
             return None, {"loss_cls": lc, "loss_reg": lr, "loss_centerness": lctr}
         logits, reg, ctr = self.head(rows, shape)
         return self.box_selector_test(shape, logits, reg, ctr, image_sizes), {}
-
-
-def _event_if_device(targets):
-    """device-resident ground truth was produced on the calling stream: the event the plan's stream waits for"""
-    if not any(b.is_cuda or l.is_cuda for b, l in targets):
-        return None
-    ev = torch.cuda.Event()
-    ev.record(torch.cuda.current_stream())
-    return ev
 
 
 def build_atss(cfg=None, num_classes=None):

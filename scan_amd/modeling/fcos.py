@@ -130,6 +130,15 @@ def target_plan(shape, targets, device, side_stream=None, after=None, build=None
     return p
 
 
+def _event_if_device(targets):
+    """device-resident ground truth was produced on the calling stream: the event the plan's stream waits for"""
+    if not any(b.is_cuda or l.is_cuda for b, l in targets):
+        return None
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream())
+    return ev
+
+
 DEVICE_PLAN = True  # False: the torch spelling below also on the GPU (A/B, cross-checks)
 _plan_staging = {}  # (N, device) -> pinned host buffers of the packed ground truth, grown (never shrunk) to a power of two of boxes
 

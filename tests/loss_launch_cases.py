@@ -1,5 +1,6 @@
-"""The cases of tests/test_gpu_loss_launch.py and tools/make_loss_parent_golden.py: the loss forwards of csrc/losses.hip and the
-ATSS GIoU forward of csrc/atss.hip, called through the C ABI on inputs drawn from a seeded CPU generator.  run(case, device)
+"""The cases of tests/test_gpu_loss_launch.py and tools/make_loss_parent_golden.py: the loss forwards of csrc/losses.hip, the
+GIoU forward / backward and the plan targets of csrc/atss.hip and the smooth-L1 forward / backward of csrc/retina.hip, called
+through the C ABI on inputs drawn from a seeded CPU generator or taken from the heads' fixtures.  run(case, device)
 returns the raw bits of what a call wrote.  Ordered calls get a workspace of exactly the size their *_ordered_ws_floats query
 gives, filled with NaN, and NaN-filled outputs: a block count or slot stride that does not match the launch ends in NaN or in
 other bits.  Atomic calls add to zeroed outputs, from ONE workgroup (at most 2,048 work items): a single atomic onto a zeroed
@@ -51,6 +52,13 @@ CASES = [
     ("a_sfl_k9", "sfl", False, None, dict(M=200, K=9)),
     ("a_sfl_k20", "sfl", False, None, dict(M=200, K=20)),
     ("a_giou", "giou", False, None, dict(P=200)),
+    # ---- the heads' smooth-L1 (csrc/retina.hip); new cases go at the end: the seed of a case is 7000 + its index
+    ("sl1_a9", "sl1", True, None, dict(A=9)),                                    # ordered, 2,322 anchors, 2
+    ("a_sl1_a3", "sl1", False, None, dict(A=3)),                                 # atomic, 774 anchors, 1
+    # ---- float outputs of the heads that no sum folds: backward gradients and the ATSS plan's targets
+    ("sl1_bwd_a9", "sl1_bwd", True, None, dict(A=9)),
+    ("giou_bwd", "giou_bwd", True, None, dict(P=5000)),
+    ("atss_targets", "atss_targets", True, None, dict()),
 ]
 IDS = [c[0] for c in CASES]
 
@@ -158,20 +166,116 @@ def _sfl(device, ordered, seed, M, K):
     return {"sum": _bits(out)}
 
 
-def _giou(device, ordered, seed, P):
-    """P rows drawn with repetition from the 1,364 rows of the 128x256 pyramid of tests/atss_ref.py with two images"""
+def _giou_inputs(device, P):
+    """P rows drawn with repetition from the 1,364 rows of the 128x256 pyramid of tests/atss_ref.py with two images; the shape
+    is returned too: it owns the descriptor the first argument points to"""
     import atss_ref as R
     from scan_amd import ops
     pred, target, rows, weight = (t.to(device) for t in R.giou_inputs(P, "generic"))
     shape = ops.PyramidShape(2, R.SIZES_128x256)
     geo = (shape.ref(), (ctypes.c_int32 * shape.n_levels)(*R.STRIDES), (ctypes.c_float * shape.n_levels)(*R.SIZES))
+    return shape, geo + (ops._ptr(pred), ops._ptr(target), ops._ptr(rows), ops._ptr(weight), P), (pred, target, rows, weight)
+
+
+def _giou(device, ordered, seed, P):
+    from scan_amd.ops import _ptr
+    shape, args, keep = _giou_inputs(device, P)
     out = _out(2, ordered, device)
-    _launch("scan_atss_giou", "_forward", ordered, (P,), device, *geo, ops._ptr(pred), ops._ptr(target), ops._ptr(rows),
-            ops._ptr(weight), P, ops._ptr(out))
+    _launch("scan_atss_giou", "_forward", ordered, (P,), device, *args, _ptr(out))
     return {"out2": _bits(out)}
 
 
-_FAMILY = {"focal": _focal, "iou": _iou, "bce": _bce, "cka": _cka, "sfl": _sfl, "giou": _giou}
+def _giou_bwd(device, ordered, seed, P):
+    """the gradient of the giou case's inputs under an upstream gradient of 0.75"""
+    from scan_amd import _lib
+    from scan_amd.ops import _ptr, _stream
+    shape, args, keep = _giou_inputs(device, P)
+    g = torch.full((1,), 0.75, device=device)
+    d = torch.full((P, 4), NAN, device=device)
+    _lib.call("scan_atss_giou_backward", *args, _ptr(g), _ptr(d), _stream())
+    torch.cuda.synchronize()
+    assert torch.isfinite(d).all()
+    return {"d_pred_crc32": _crc(d)}
+
+
+_SL1_SEED = 7777  # sl1_a9 and sl1_bwd_a9 share their inputs
+
+
+def _sl1_inputs(device, A):
+    """the 64x96 pyramid of tests/retinanet_ref.py with the two images and boxes of the retinanet_64x96 fixture, A = 9 (the
+    fixture's cell anchors) or 3 (one scale per octave); the plan is retinanet.build_plan's; bbox_reg is the first 4 A columns
+    of a seeded [M, 4 A + 4] matrix, read in place through its pitch"""
+    import os
+    import retinanet_ref as R
+    from scan_amd import ops
+    from scan_amd.modeling import retinanet
+    f = R.load_case(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"), "retinanet_64x96")
+    assert f["N"] == 2 and f["sizes"] == R.SIZES_64x96
+    shape = ops.PyramidShape(2, R.SIZES_64x96)
+    cells = retinanet.cell_anchors() if A == 9 else retinanet.cell_anchors(scales_per_octave=1)
+    assert cells.shape[1] == A
+    plan = retinanet.build_plan(shape, f["targets"], device, cells=cells)
+    assert plan.n_pos > 0 and int((plan.labels_i32 > 0).sum()) == plan.n_pos
+    g = torch.Generator().manual_seed(_SL1_SEED + A)
+    wide = torch.randn(shape.rows, 4 * A + 4, generator=g).to(device)
+    cells_d = retinanet.device_cells(cells, device)
+    strides = (ctypes.c_int32 * shape.n_levels)(*R.STRIDES)
+    args = (shape.ref(), strides, ops._ptr(cells_d), A, ops._ptr(plan.boxes), plan.boxes.shape[1], ops._ptr(plan.labels_i32),
+            ops._ptr(plan.matched), ops._ptr(wide), 4 * A + 4, 0.11)
+    return shape, args, (plan, wide, cells_d)
+
+
+def _sl1(device, ordered, seed, A):
+    from scan_amd import _lib
+    from scan_amd.ops import _ptr
+    shape, args, keep = _sl1_inputs(device, A)
+    n = shape.rows * A
+    if ordered:
+        assert _lib.query("scan_retina_smooth_l1_ordered_ws_floats", n) >= 2  # more than one workgroup
+    else:
+        assert n <= 2048  # one workgroup
+    res = {}
+    for want in (True, False):  # the sum beside the targets, then the sum alone
+        tg = torch.full((n, 4), NAN, device=device) if want else None
+        s = _out(1, ordered, device)
+        _launch("scan_retina_smooth_l1", "_forward", ordered, (n,), device, *args, _ptr(tg), _ptr(s))
+        res["sum_with_targets" if want else "sum"] = _bits(s)
+        if want:
+            assert torch.isfinite(tg).all()
+            res["targets_crc32"] = _crc(tg)
+    return res
+
+
+def _sl1_bwd(device, ordered, seed, A):
+    """d_pred through a pitch of 4 A + 4 under an upstream gradient of 0.75: the 4 A columns are written, the rest is not"""
+    from scan_amd import _lib
+    from scan_amd.ops import _ptr, _stream
+    shape, args, keep = _sl1_inputs(device, A)
+    g = torch.full((1,), 0.75, device=device)
+    d = torch.full((shape.rows, 4 * A + 4), NAN, device=device)
+    _lib.call("scan_retina_smooth_l1_backward", *args, _ptr(g), _ptr(d), 4 * A + 4, _stream())
+    torch.cuda.synchronize()
+    assert torch.isfinite(d[:, :4 * A]).all() and torch.isnan(d[:, 4 * A:]).all()
+    assert int((d[:, :4 * A] != 0).sum()) > 0
+    return {"d_pred_crc32": _crc(d[:, :4 * A])}
+
+
+def _atss_targets(device, ordered, seed):
+    """the float targets of modeling.atss.build_plan on the boxes of the atss_64x96 fixture"""
+    import os
+    import atss_ref as R
+    from scan_amd import ops
+    from scan_amd.modeling import atss
+    f = R.load_case(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"), "atss_64x96")
+    shape = ops.PyramidShape(f["N"], f["sizes"])
+    plan = atss.build_plan(shape, f["targets"], device, R.STRIDES, [float(a) for a in f["anchor_sizes"]], int(f["topk"]))
+    torch.cuda.synchronize()
+    assert plan.n_pos > 0 and plan.reg_pos.shape == (plan.n_pos, 4) and plan.ctr_pos.shape == (plan.n_pos,)
+    return {"reg_pos": _bits(plan.reg_pos).reshape(-1), "ctr_pos": _bits(plan.ctr_pos), "pos_inds_crc32": _crc(plan.pos_inds)}
+
+
+_FAMILY = {"focal": _focal, "iou": _iou, "bce": _bce, "cka": _cka, "sfl": _sfl, "giou": _giou, "giou_bwd": _giou_bwd,
+           "sl1": _sl1, "sl1_bwd": _sl1_bwd, "atss_targets": _atss_targets}
 
 
 def run(case_id, device):

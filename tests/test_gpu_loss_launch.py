@@ -1,7 +1,10 @@
 """The host launch layer of the loss reductions (csrc/losses.hip, and the GIoU forward of csrc/atss.hip) picks the kernel form,
 the grid and the workspace stride; the kernels' bits follow from those alone.  tests/golden/loss_sums_parent.npz holds what the
 build before that layer was folded into one launcher per loss wrote for the cases of tests/loss_launch_cases.py
-(tools/make_loss_parent_golden.py recorded it on an MI355X): every case must reproduce it bit for bit.
+(tools/make_loss_parent_golden.py recorded it on an MI355X): every case must reproduce it bit for bit.  The heads' cases
+(smooth-L1 of csrc/retina.hip, the GIoU backward and the plan targets of csrc/atss.hip) were recorded the same way on the build
+before their select, IoU and ordered-sum helpers moved to csrc/common.h and csrc/boxes.h; every array recorded earlier came back
+identical then.
 
 Ordered entry points at the smallest shapes with more than one workgroup on every kernel form (and under reduce_blocks = 2);
 atomic entry points from one workgroup, where the sum is order-free.  Atomic sums of several workgroups are not reproducible

@@ -234,3 +234,34 @@ def test_plan_entry_points_refuse_bad_arguments_without_a_device():
         refused(nodes(outs=tuple(None if j == i else fake for j in range(5))), "fcos_nodes: null output")
     # ... and with none, the call returns before it looks at them (and before any launch)
     assert nodes(level_pos=i32(0, 0), outs=(None,) * 5) == 0
+
+
+def test_plan_entry_points_refuse_an_inconsistent_pyramid_before_any_launch():
+    """a level whose rows are not n_images * h * w would send the row decode past the images' box counts: every plan entry
+    point checks the whole descriptor (scan_check_pyramid in csrc/common.h), not only its level count"""
+    L, fake = _lib.lib(), ctypes.c_void_p(4096)  # never dereferenced
+    i32 = lambda *v: (ctypes.c_int32 * len(v))(*v)
+
+    def broken(edit):
+        s = ops.PyramidShape(2, [(4, 4), (2, 2)])
+        edit(s.desc)
+        return s
+
+    def rows_off(d):
+        d.row_off[1] += 1
+
+    def no_height(d):
+        d.h[1] = 0
+
+    def more_images(d):
+        d.n_images = 3
+
+    for edit in (rows_off, no_height, more_images):
+        s = broken(edit)
+        for rc in (L.scan_fcos_assign(s.ref(), *(fake,) * 5, 3, *(fake,) * 4, None),
+                   L.scan_fcos_compact(s.ref(), fake, fake, fake, None),
+                   L.scan_fcos_nodes(s.ref(), i32(0, 0), *(fake,) * 9, None)):
+            assert rc == -1 and re.search(r"fcos_\w+: level \d of the pyramid is inconsistent", L.scan_last_error().decode())
+    huge = ops.PyramidShape(1, [(46341, 46341)])
+    assert L.scan_fcos_assign(huge.ref(), *(fake,) * 5, 3, *(fake,) * 4, None) == -1
+    assert "level 0 alone has 2^31 rows or more" in L.scan_last_error().decode()

@@ -1,4 +1,4 @@
-"""Registers / scratch / occupancy of every kernel in one .hip file, as the compiler reports them (no GPU needed).
+"""Registers / scratch / occupancy / LDS of every kernel in one .hip file, as the compiler reports them (no GPU needed).
 
     python tools/kernel_resources.py scan_amd/csrc/conv_fwd.hip [filter]
 """
@@ -20,7 +20,7 @@ def main():
     err = subprocess.run(cmd, capture_output=True, text=True).stderr
     recs, cur = [], None
     for line in err.splitlines():
-        m = re.search(r"remark: +(Function Name|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs|"
+        m = re.search(r"remark: +(Function Name|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|TotalSGPRs|"
                       r"VGPRs Spill|LDS Size \[bytes/block\]): (\S+)", line)
         if not m:
             if "error" in line:
@@ -33,12 +33,12 @@ def main():
         elif cur is not None:
             cur[k.split(" [")[0]] = v
     names = demangle([r["name"] for r in recs])
-    print("%-78s %5s %5s %7s %5s %5s" % ("kernel", "VGPR", "AGPR", "scratch", "occ", "SGPR"))
+    print("%-78s %5s %5s %7s %5s %5s %6s" % ("kernel", "VGPR", "AGPR", "scratch", "occ", "SGPR", "LDS"))
     for r, n in zip(recs, names):
         n = n.replace("void ", "")
         if flt in n:
-            print("%-78s %5s %5s %7s %5s %5s" % (n[:78], r.get("VGPRs"), r.get("AGPRs"), r.get("ScratchSize"),
-                                                  r.get("Occupancy"), r.get("SGPRs")))
+            print("%-78s %5s %5s %7s %5s %5s %6s" % (n[:78], r.get("VGPRs"), r.get("AGPRs"), r.get("ScratchSize"),
+                                                      r.get("Occupancy"), r.get("TotalSGPRs"), r.get("LDS Size")))
 
 
 if __name__ == "__main__":
