@@ -82,8 +82,31 @@ __device__ __forceinline__ const __bf16* slot_plane_i(int i, int tid, const __bf
 }
 
 // the piece products of one (weight fragment set, pixel fragment set), smallest terms first (conv_split.h)
-template <int NP, int TM>
+// TEMP (the three-piece 1x1 instances): the products of a 32-channel chunk are summed in a temporary that starts at zero and is
+// added to the running accumulator ONCE, as conv_wgrad.hip's TCHAIN does -- one rounding at the accumulator's magnitude per
+// chunk instead of six.  A 1x1 conv has Cin / 32 chunks per output where a 3x3 has nine times as many, so its distance from
+// fp64 is made of these roundings: on post-ReLU inputs (zero operands make steps of an fp32 fma chain exact) K = 200 .. 512
+// sat at 1.12 - 1.15x the fp32-MFMA kernel's rms without the temporary and sit at 0.35 - 0.41x with it
+// (tests/test_gpu_conv1x1_parity.py).  Cost: TM x 4 registers and as many adds per channel tile -- same-box A/B against the
+// kernel without it (tools/conv_bench.py --ksize 1, forward, us): 512 -> 2048 97 -> 103, 256 -> 1024 107 -> 112, lateral
+// 512 -> 256 189 -> 200, 256 -> 64 177 -> 180; the VGG step 79.30 -> 79.40 ms.  A second temporary (the add of tile tn - 1 behind
+// the MFMAs of tile tn) spills in the 256-channel tile.
+template <int NP, int TM, bool TEMP = false>
 __device__ __forceinline__ void mma_pieces(const bf16x8 (&w)[NP], const bf16x8 (&p)[NP][TM], f32x4v (&acc)[TM]) {
+  if constexpr (TEMP) {
+    f32x4v t[TM];
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm) t[tm] = f32x4v{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = NP - 1; s >= 0; --s)
+#pragma unroll
+      for (int i = 0; i <= s; ++i)
+#pragma unroll
+        for (int tm = 0; tm < TM; ++tm) t[tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[i], p[s - i][tm], t[tm], 0, 0, 0);
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm) acc[tm] += t[tm];
+    return;
+  }
 #pragma unroll
   for (int s = NP - 1; s >= 0; --s)
 #pragma unroll
@@ -422,7 +445,7 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
       for (int tn = 0; tn < TN; ++tn) {
         bf16x8 wf[NP];
         read_w(bt, tn, wf);
-        mma_pieces<NP, TM>(wf, pf, acc[tn]);
+        mma_pieces<NP, TM, KS == 1 && NP == 3>(wf, pf, acc[tn]);
         if (tt == 0 && tn == SCAN_CONV_MID) {
           __builtin_amdgcn_sched_barrier(0);
           mid();
