@@ -82,7 +82,7 @@ __device__ __forceinline__ const __bf16* slot_plane_i(int i, int tid, const __bf
 }
 
 // the piece products of one (weight fragment set, pixel fragment set), smallest terms first (conv_split.h)
-// TEMP (the three-piece 1x1 instances): the products of a 32-channel chunk are summed in a temporary that starts at zero and is
+// TEMP = 1 (the three-piece 1x1 instances): the products of a 32-channel chunk are summed in a temporary that starts at zero and is
 // added to the running accumulator ONCE, as conv_wgrad.hip's TCHAIN does -- one rounding at the accumulator's magnitude per
 // chunk instead of six.  A 1x1 conv has Cin / 32 chunks per output where a 3x3 has nine times as many, so its distance from
 // fp64 is made of these roundings: on post-ReLU inputs (zero operands make steps of an fp32 fma chain exact) K = 200 .. 512
@@ -91,18 +91,36 @@ __device__ __forceinline__ const __bf16* slot_plane_i(int i, int tid, const __bf
 // kernel without it (tools/conv_bench.py --ksize 1, forward, us): 512 -> 2048 97 -> 103, 256 -> 1024 107 -> 112, lateral
 // 512 -> 256 189 -> 200, 256 -> 64 177 -> 180; the VGG step 79.30 -> 79.40 ms.  A second temporary (the add of tile tn - 1 behind
 // the MFMAs of tile tn) spills in the 256-channel tile.
-template <int NP, int TM, bool TEMP = false>
+// TEMP = 2 (the three-piece DIRECT 3x3 instances, per tap and chunk): the five SMALL products x1 w0 .. x0 w2 are summed in the
+// temporary, the main product x0 w0 goes into the running accumulator as before, then the temporary is added -- two roundings
+// at the accumulator's magnitude per (tap, chunk) instead of six.  On post-ReLU inputs these instances sat at 1.09 - 1.22x the
+// fp32-MFMA kernel's rms without it (Cin 64 .. 512, forward and data gradient: tests/test_gpu_conv3x3_parity.py, where the
+// figures with it are recorded).  The accumulator keeps the chain of main products it had, so results stay closer to the ones
+// of before than with TEMP = 1, under which one sampled gradient element of the full-size S2C golden step
+// (tests/test_gpu_model.py) left its bar through a flipped ReLU decision.  The Winograd instance, which carries the 128- and
+// 256-channel layers, has no temporary and passes the same bars at 0.8 - 0.9x.  With it the direct instances sit at 0.42 - 0.48x
+// on post-ReLU inputs.  Cost, same-session A/B against the library without it (tools/conv_bench.py, us): conv1_2 64 -> 64
+// forward 2936 -> 3111, data gradient 2863 -> 3087; under conv_wino = 0 conv2_2 2524 -> 2740, conv3_x (256-channel tile: 35
+// registers spill now) 2319 -> 2542; the remainder split 264 <- 1024 at P3 2692 -> 3000; the VGG step 78.99 / 79.19 -> 79.31 /
+// 79.13 ms.  A second temporary in the 64- and 128-channel tiles (the add of tile tn - 1 behind the MFMAs of tile tn) measured
+// 2 - 3 % better per kernel and the same per step: not kept.
+template <int NP, int TM, int TEMP = 0>
 __device__ __forceinline__ void mma_pieces(const bf16x8 (&w)[NP], const bf16x8 (&p)[NP][TM], f32x4v (&acc)[TM]) {
-  if constexpr (TEMP) {
+  if constexpr (TEMP != 0) {
+    constexpr int LAST = TEMP == 2 ? 1 : 0;  // the piece levels s = NP - 1 .. LAST go into the temporary
     f32x4v t[TM];
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm) t[tm] = f32x4v{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int s = NP - 1; s >= 0; --s)
+    for (int s = NP - 1; s >= LAST; --s)
 #pragma unroll
       for (int i = 0; i <= s; ++i)
 #pragma unroll
         for (int tm = 0; tm < TM; ++tm) t[tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[i], p[s - i][tm], t[tm], 0, 0, 0);
+    if constexpr (TEMP == 2) {
+#pragma unroll
+      for (int tm = 0; tm < TM; ++tm) acc[tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], p[0][tm], acc[tm], 0, 0, 0);
+    }
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm) acc[tm] += t[tm];
     return;
@@ -445,7 +463,7 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : 2) void conv_split_kernel(
       for (int tn = 0; tn < TN; ++tn) {
         bf16x8 wf[NP];
         read_w(bt, tn, wf);
-        mma_pieces<NP, TM, KS == 1 && NP == 3>(wf, pf, acc[tn]);
+        mma_pieces<NP, TM, NP != 3 ? 0 : KS == 1 ? 1 : 2>(wf, pf, acc[tn]);
         if (tt == 0 && tn == SCAN_CONV_MID) {
           __builtin_amdgcn_sched_barrier(0);
           mid();
