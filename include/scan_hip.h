@@ -710,6 +710,59 @@ int scan_retina_smooth_l1_backward(const scan_pyramid_t* d, const int32_t* strid
                                    const float* bbox_reg, int64_t ld, float beta, const float* g_dev, float* d_pred,
                                    int64_t ld_out, void* stream);
 
+/* ---- the region-proposal network (csrc/rpn.hip; reference modeling/rpn/loss.py:56-131, rpn/inference.py:74-121,
+ *      rpn/anchor_generator.py:97-110, modeling/balanced_positive_negative_sampler.py, modeling/box_coder.py).  Anchors, strides
+ *      and cells as in the RetinaNet block above: anchor i = m * A + a is formed in the kernel, no [M * A][4] tensor exists.
+ *      image_hw [N][2] int32 (DEVICE): the unpadded (height, width) of every image.
+ *      scan_rpn_visibility: runs behind scan_retina_match called with every box label 1 (labels 1 / 0 / -1).  Writes label -1
+ *      (and matched 0) where the anchor is not visible: visible = x1 >= -t and y1 >= -t and x2 < width + t and y2 < height + t,
+ *      t = straddle_thresh; t < 0: every anchor is visible, nothing is launched.  One launch, no visibility tensor.  Invisible
+ *      anchors have taken part in the per-box maxima of the low-quality rule, as in the reference.
+ *      scan_rpn_sample: per image n, num_pos = min(#label >= 1, max_positives), num_neg = min(#label == 0,
+ *      batch_size_per_image - num_pos).  The sampled positives are the num_pos anchors with label >= 1 that have the smallest
+ *      (key, anchor index) pairs; the sampled negatives likewise among label == 0.  key = keys[i] when keys is not NULL
+ *      ([M * A] uint32, device), else
+ *          fmix32(fmix32(seed ^ (0x9E3779B9 * (n + 1))) ^ (uint32)i),
+ *          fmix32(x): x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16   (all mod 2^32).
+ *      Outputs: sampled [M * A] uint8 (1 sampled positive, 2 sampled negative, 0 otherwise; every byte is written),
+ *      counts [N][2] int32 = (num_pos, num_neg).  Grid: 2 N workgroups of 256 threads, one per (image, class), each walking the
+ *      image's row range of every level; a radix select over the key bits (8 bits a pass, LDS histogram).  No cap on the
+ *      anchors per image; M * A < 2^31.  Integers only: bit-reproducible whatever scan_tune "deterministic" says, no ordered twin.
+ *      scan_rpn_loss_*: over ALL M * A anchors, no compaction.  objectness row m holds A logits (row pitch ld_obj floats),
+ *      bbox_reg row m holds 4 A (row pitch ld_reg, a multiple of 4; 16-byte aligned).  Forward ADDS to out2 (clear it first):
+ *      out2[0] += sum over sampled != 0 of max(x, 0) - x y + log1p(exp(-|x|)), y = 1 where sampled == 1 else 0;
+ *      out2[1] += sum over sampled == 1 of smooth-L1(pred - BoxCoder.encode(boxes[n][matched], anchor)), weights (1, 1, 1, 1),
+ *      TO_REMOVE = 1, the target formed in fp64 and rounded once, beta as in the RetinaNet block.  The _ordered twin writes both
+ *      from per-block slots in a fixed order (ws: scan_rpn_loss_ordered_ws_floats(M * A) floats).  targets_out as in the
+ *      RetinaNet block (zero where sampled != 1).  Backward writes, for EVERY anchor, d_obj[m][a] = g2_dev[0] *
+ *      (sigmoid(x) - y) and d_reg[m][4a..4a+4) = g2_dev[1] * smooth-L1', both zero where the anchor does not take part
+ *      (row pitches ldo_obj, ldo_reg).
+ *      scan_rpn_decode: one launch for all levels and images.  topk_idx [N][K] int64: column k in [k_off[l], k_off[l + 1]) is a
+ *      candidate of level l, its value the anchor's index within that image's level (y, x, a order, 0 .. h w A - 1); k_off a
+ *      HOST array [n_levels + 1], k_off[0] = 0.  boxes [N][K][4] = BoxCoder.decode(bbox_reg columns of the anchor, anchor) with
+ *      weights 1, dw / dh clamped at log(1000 / 16), +1 widths, x2 = ctr + 0.5 w - 1, clipped to [0, width - 1] x [0, height - 1];
+ *      keep [N][K] uint8 = width >= min_size and height >= min_size with +1 extents.  An index outside its level gives a zero
+ *      box and keep 0; nothing is read for it. ---- */
+int scan_rpn_visibility(const scan_pyramid_t* d, const int32_t* strides, const float* cells, int32_t A, const int32_t* image_hw,
+                        float straddle_thresh, int32_t* labels_i32, int32_t* matched, void* stream);
+int scan_rpn_sample(const scan_pyramid_t* d, int32_t A, const int32_t* labels_i32, int32_t batch_size_per_image,
+                    int32_t max_positives, uint32_t seed, const uint32_t* keys, uint8_t* sampled, int32_t* counts, void* stream);
+int scan_rpn_loss_forward(const scan_pyramid_t* d, const int32_t* strides, const float* cells, int32_t A, const float* boxes,
+                          int32_t G, const int32_t* matched, const uint8_t* sampled, const float* objectness, int64_t ld_obj,
+                          const float* bbox_reg, int64_t ld_reg, float beta, float* targets_out, float* out2, void* stream);
+int64_t scan_rpn_loss_ordered_ws_floats(int64_t n_anchors);
+int scan_rpn_loss_forward_ordered(const scan_pyramid_t* d, const int32_t* strides, const float* cells, int32_t A, const float* boxes,
+                                  int32_t G, const int32_t* matched, const uint8_t* sampled, const float* objectness,
+                                  int64_t ld_obj, const float* bbox_reg, int64_t ld_reg, float beta, float* targets_out,
+                                  float* out2, float* ws, void* stream);
+int scan_rpn_loss_backward(const scan_pyramid_t* d, const int32_t* strides, const float* cells, int32_t A, const float* boxes,
+                           int32_t G, const int32_t* matched, const uint8_t* sampled, const float* objectness, int64_t ld_obj,
+                           const float* bbox_reg, int64_t ld_reg, float beta, const float* g2_dev, float* d_obj, int64_t ldo_obj,
+                           float* d_reg, int64_t ldo_reg, void* stream);
+int scan_rpn_decode(const scan_pyramid_t* d, const int32_t* strides, const float* cells, int32_t A, const float* bbox_reg,
+                    int64_t ld, const int64_t* topk_idx, const int32_t* k_off, const int32_t* image_hw, float min_size,
+                    float* boxes, uint8_t* keep, void* stream);
+
 /* ---- FPN top-down join on NHWC rows (reference backbone/fpn.py:62-75: inner = lateral + F.interpolate(top,
  *      scale_factor=2, mode="nearest")).  lat / y [N, 2h, 2w, C], coarse [N, h, w, C], C % 4 == 0.  Backward:
  *      d_lateral is the incoming gradient itself, d_coarse its 2x2 window sums (scan_downsample2x_sum: g [N, 2h, 2w, C]

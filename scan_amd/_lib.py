@@ -171,6 +171,16 @@ SIGNATURES = {
                                                              c_vp, c_vp, c_vp, c_vp]),
     "scan_retina_smooth_l1_backward": (ctypes.c_int, [_PD, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_f32, c_vp,
                                                       c_vp, c_i64, c_vp]),
+    "scan_rpn_visibility": (ctypes.c_int, [_PD, c_vp, c_vp, c_i32, c_vp, c_f32, c_vp, c_vp, c_vp]),
+    "scan_rpn_sample": (ctypes.c_int, [_PD, c_i32, c_vp, c_i32, c_i32, ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp]),
+    "scan_rpn_loss_forward": (ctypes.c_int, [_PD, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_f32,
+                                             c_vp, c_vp, c_vp]),
+    "scan_rpn_loss_ordered_ws_floats": (c_i64, [c_i64]),
+    "scan_rpn_loss_forward_ordered": (ctypes.c_int, [_PD, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64,
+                                                     c_f32, c_vp, c_vp, c_vp, c_vp]),
+    "scan_rpn_loss_backward": (ctypes.c_int, [_PD, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_f32,
+                                              c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "scan_rpn_decode": (ctypes.c_int, [_PD, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp]),
     "scan_groupnorm_relu_forward_ld":(ctypes.c_int, [c_vp, _PD, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp]),
     "scan_groupnorm_relu_forward_from_sums_ld": (ctypes.c_int, [c_vp, _PD, c_i32, c_i32, c_vp, c_f32, c_vp, c_vp, c_i32, c_vp,
                                                                 c_i32, c_vp, c_vp]),

@@ -93,6 +93,18 @@ RETINANET_DEFAULTS = {
 }
 
 
+# The region-proposal network (a MODEL.RPN block in the cfg, modeling/rpn.py) with the reference's defaults (defaults.py:132-173)
+# except ANCHOR_STRIDE and USE_FPN: the pyramid here is P3..P7, so the reference's single-level (16,) / False become the FPN
+# spelling.  Kept OUT of DEFAULTS for the same reason as ATSS_DEFAULTS; rpn_settings(cfg) reads a cfg's MODEL.RPN block over these.
+RPN_DEFAULTS = {
+    "USE_FPN": True, "ANCHOR_SIZES": (32, 64, 128, 256, 512), "ANCHOR_STRIDE": (8, 16, 32, 64, 128),
+    "ASPECT_RATIOS": (0.5, 1.0, 2.0), "STRADDLE_THRESH": 0, "FG_IOU_THRESHOLD": 0.7, "BG_IOU_THRESHOLD": 0.3,
+    "BATCH_SIZE_PER_IMAGE": 256, "POSITIVE_FRACTION": 0.5, "PRE_NMS_TOP_N_TRAIN": 12000, "PRE_NMS_TOP_N_TEST": 6000,
+    "POST_NMS_TOP_N_TRAIN": 2000, "POST_NMS_TOP_N_TEST": 1000, "NMS_THRESH": 0.7, "MIN_SIZE": 0,
+    "FPN_POST_NMS_TOP_N_TRAIN": 2000, "FPN_POST_NMS_TOP_N_TEST": 2000, "RPN_HEAD": "SingleConvRPNHead",
+}
+
+
 # Region poolers (modeling/poolers.make_pooler) with the reference's defaults for MODEL.<head_name> (defaults.py:214-216 for
 # ROI_BOX_HEAD; ROI_MASK_HEAD :231-233 and ROI_KEYPOINT_HEAD :249-251 carry the same three values).  Kept OUT of DEFAULTS for
 # the same reason as ATSS_DEFAULTS; pooler_settings(cfg, head_name) reads a cfg's MODEL[head_name] block over these.
@@ -368,6 +380,43 @@ def retinanet_settings(cfg):
         fg_iou_threshold=float(R.FG_IOU_THRESHOLD), bg_iou_threshold=float(R.BG_IOU_THRESHOLD), loss_alpha=float(R.LOSS_ALPHA),
         loss_gamma=float(R.LOSS_GAMMA), prior_prob=float(R.PRIOR_PROB), inference_th=float(R.INFERENCE_TH),
         nms_th=float(R.NMS_TH), detections_per_img=int(cfg.TEST.DETECTIONS_PER_IMG))
+
+
+def rpn_settings(cfg):
+    """Flat view of MODEL.RPN (and MODEL.RPN_ONLY) for modeling.rpn.RPNModule; raises, naming the key, on every value that is not
+    built: the single-level RPN (USE_FPN False), strides other than the pyramid's, anything but one anchor size per level, other
+    heads than SingleConvRPNHead."""
+    R = Cfg(RPN_DEFAULTS)
+    R._merge(cfg.MODEL.get("RPN", {}))
+    if not bool(R.USE_FPN):
+        raise ValueError("MODEL.RPN.USE_FPN False is not built: the RPN runs on the P3..P7 pyramid (set it to True)")
+    if tuple(R.ANCHOR_STRIDE) != (8, 16, 32, 64, 128):
+        raise ValueError("MODEL.RPN.ANCHOR_STRIDE %r: the pyramid has strides (8, 16, 32, 64, 128)" % (R.ANCHOR_STRIDE,))
+    if len(R.ANCHOR_SIZES) != 5 or any(isinstance(a, (tuple, list)) or float(a) < 1 for a in R.ANCHOR_SIZES):
+        raise ValueError("MODEL.RPN.ANCHOR_SIZES %r: one size >= 1 per pyramid level" % (R.ANCHOR_SIZES,))
+    if any(float(r) <= 0 for r in R.ASPECT_RATIOS) or not 1 <= len(R.ASPECT_RATIOS) <= 16:
+        raise ValueError("MODEL.RPN.ASPECT_RATIOS %r: 1..16 positive ratios" % (R.ASPECT_RATIOS,))
+    if str(R.RPN_HEAD) != "SingleConvRPNHead":
+        raise ValueError("MODEL.RPN.RPN_HEAD %r is not built (only 'SingleConvRPNHead')" % (R.RPN_HEAD,))
+    if float(R.BG_IOU_THRESHOLD) > float(R.FG_IOU_THRESHOLD):
+        raise ValueError("MODEL.RPN.BG_IOU_THRESHOLD %r above FG_IOU_THRESHOLD %r" % (R.BG_IOU_THRESHOLD, R.FG_IOU_THRESHOLD))
+    if int(R.BATCH_SIZE_PER_IMAGE) < 1:
+        raise ValueError("MODEL.RPN.BATCH_SIZE_PER_IMAGE %r: at least 1" % (R.BATCH_SIZE_PER_IMAGE,))
+    if not 0 < float(R.POSITIVE_FRACTION) <= 1:
+        raise ValueError("MODEL.RPN.POSITIVE_FRACTION %r outside (0, 1]" % (R.POSITIVE_FRACTION,))
+    for key in ("PRE_NMS_TOP_N_TRAIN", "PRE_NMS_TOP_N_TEST", "POST_NMS_TOP_N_TRAIN", "POST_NMS_TOP_N_TEST",
+                "FPN_POST_NMS_TOP_N_TRAIN", "FPN_POST_NMS_TOP_N_TEST"):
+        if int(R[key]) < 1:
+            raise ValueError("MODEL.RPN.%s %r: at least 1" % (key, R[key]))
+    return dict(
+        anchor_sizes=tuple(float(a) for a in R.ANCHOR_SIZES), anchor_strides=tuple(int(s) for s in R.ANCHOR_STRIDE),
+        aspect_ratios=tuple(float(r) for r in R.ASPECT_RATIOS), straddle_thresh=float(R.STRADDLE_THRESH),
+        fg_iou_threshold=float(R.FG_IOU_THRESHOLD), bg_iou_threshold=float(R.BG_IOU_THRESHOLD),
+        batch_size_per_image=int(R.BATCH_SIZE_PER_IMAGE), positive_fraction=float(R.POSITIVE_FRACTION),
+        pre_nms_top_n_train=int(R.PRE_NMS_TOP_N_TRAIN), pre_nms_top_n_test=int(R.PRE_NMS_TOP_N_TEST),
+        post_nms_top_n_train=int(R.POST_NMS_TOP_N_TRAIN), post_nms_top_n_test=int(R.POST_NMS_TOP_N_TEST),
+        nms_thresh=float(R.NMS_THRESH), min_size=float(R.MIN_SIZE), fpn_post_nms_top_n_train=int(R.FPN_POST_NMS_TOP_N_TRAIN),
+        fpn_post_nms_top_n_test=int(R.FPN_POST_NMS_TOP_N_TEST), rpn_only=bool(cfg.MODEL.get("RPN_ONLY", False)))
 
 
 def epm_settings(cfg):

@@ -26,24 +26,11 @@
 // elsewhere, summed (block_result<ORD>; the ordered twin's second stage is ordered_sum_launch of losses.hip).  The backward
 // writes d_pred for every anchor (zero where label <= 0).
 //
-// Per-level selects, the pyramid check and the wave reductions are common.h's; boxlist_iou is boxes.h's (box first here).
+// Per-level selects, the pyramid check and the wave reductions are common.h's; boxlist_iou is boxes.h's (box first here); the
+// anchor of a row, BoxCoder.encode and the smooth-L1 element are anchors.h's (shared with rpn.hip).
 #include "common.h"
 #include "boxes.h"
-
-#define RETINA_MAX_A 16
-
-struct RetinaStrides {
-  int s[SCAN_MAX_LEVELS];
-};
-
-// anchor a of row rc: the cell anchor plus the location's shift, one fp32 addition per corner (anchor_generator.py:73-95)
-__device__ __forceinline__ float4 retina_anchor(const RetinaStrides& st, const float* __restrict__ cells, int A, const RowCoord rc,
-                                                int a) {
-  const float4 c = *reinterpret_cast<const float4*>(cells + ((int64_t)rc.lvl * A + a) * 4);
-  const int s = pick_level(st.s, rc.lvl);
-  const float sx = (float)(rc.x * s), sy = (float)(rc.y * s);
-  return make_float4(c.x + sx, c.y + sy, c.z + sx, c.w + sy);
-}
+#include "anchors.h"
 
 // pass 1: gt_max[n * G + g] (zeroed by the caller).  All 64 lanes of a wave stay in the loop together (the shuffles need them).
 __global__ __launch_bounds__(256) void retina_gtmax_kernel(scan_pyramid_t d, RetinaStrides st, const float* __restrict__ cells,
@@ -127,24 +114,6 @@ __global__ __launch_bounds__(256) void retina_labels_kernel(scan_pyramid_t d, Re
   }
 }
 
-static int retina_check(const scan_pyramid_t* d, const int32_t* strides, const float* cells, int32_t A, RetinaStrides* st,
-                        const char* who) {
-  if (scan_check_pyramid(d, who)) return -1;
-  SCAN_CHECK_ARG(A >= 1 && A <= RETINA_MAX_A, "%s: A=%d anchors per location outside 1..%d", who, A, RETINA_MAX_A);
-  SCAN_CHECK_ARG(d->row_off[d->n_levels] * A < (1ll << 40), "%s: too many anchors", who);
-  SCAN_CHECK_ARG(strides && cells, "%s: null strides / cell anchors", who);
-  SCAN_CHECK_ARG((reinterpret_cast<uintptr_t>(cells) & 15) == 0, "%s: cell anchors must be 16-byte aligned", who);
-  for (int l = 0; l < SCAN_MAX_LEVELS; ++l) {
-    st->s[l] = 1;
-    if (l < d->n_levels) {
-      SCAN_CHECK_ARG(strides[l] >= 1 && (int64_t)strides[l] * (d->h[l] > d->w[l] ? d->h[l] : d->w[l]) < (1 << 24),
-                     "%s: level %d has stride %d (shifts must stay exact in fp32)", who, l, strides[l]);
-      st->s[l] = strides[l];
-    }
-  }
-  return 0;
-}
-
 extern "C" int64_t scan_retina_match_ws_bytes(const scan_pyramid_t* d, int32_t G) {
   if (!d || d->n_images < 1 || G < 1) return -1;
   return 4 * (int64_t)d->n_images * G;  // gt_max
@@ -178,16 +147,6 @@ extern "C" int scan_retina_match(const scan_pyramid_t* d, const int32_t* strides
 }
 
 // ------------------------------------------------------------------ smooth-L1 on encoded targets
-// BoxCoder.encode(box, anchor), weights (10, 10, 5, 5), in fp64, rounded once
-__device__ __forceinline__ float4 retina_encode(const float4 b, const float4 a) {
-  const double ew = (double)a.z - (double)a.x + 1.0, eh = (double)a.w - (double)a.y + 1.0;
-  const double ecx = (double)a.x + 0.5 * ew, ecy = (double)a.y + 0.5 * eh;
-  const double gw = (double)b.z - (double)b.x + 1.0, gh = (double)b.w - (double)b.y + 1.0;
-  const double gcx = (double)b.x + 0.5 * gw, gcy = (double)b.y + 0.5 * gh;
-  return make_float4((float)(10.0 * (gcx - ecx) / ew), (float)(10.0 * (gcy - ecy) / eh), (float)(5.0 * log(gw / ew)),
-                     (float)(5.0 * log(gh / eh)));
-}
-
 struct SmoothL1Args {
   scan_pyramid_t d;
   RetinaStrides st;
@@ -211,18 +170,9 @@ __device__ __forceinline__ void smooth_l1_pair(const SmoothL1Args& p, int64_t i,
   int g = p.matched[i];
   g = g < 0 ? 0 : (g < p.G ? g : p.G - 1);  // a plan of scan_retina_match is inside already: never read out of bounds
   const float4 b = *reinterpret_cast<const float4*>(p.boxes + ((int64_t)rc.n * p.G + g) * 4);
-  *t = retina_encode(b, an);
+  *t = box_encode(b, an, 10.0, 5.0);  // weights (10, 10, 5, 5)
   *col0 = m * p.ld + 4 * a;
   *x = *reinterpret_cast<const float4*>(p.pred + *col0);
-}
-
-__device__ __forceinline__ float smooth_l1_elem(float x, float t, float beta) {
-  const float n = fabsf(x - t);
-  return n < beta ? 0.5f * n * n / beta : n - 0.5f * beta;
-}
-__device__ __forceinline__ float smooth_l1_grad(float x, float t, float beta) {
-  const float e = x - t;
-  return fabsf(e) < beta ? e / beta : (e > 0.f ? 1.f : -1.f);
 }
 
 // ORD: every block writes its sum to its own slot out[blockIdx.x] instead of adding it to out[0] (block_result)

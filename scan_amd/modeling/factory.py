@@ -30,6 +30,7 @@ from .discriminator import FCOSDiscriminator_con
 from .fcos import FCOSModule
 from .resnet import ResNetFPNBackbone
 from .retinanet import RetinaNetModule
+from .rpn import RPNModule
 
 LEVELS = ("P3", "P4", "P5", "P6", "P7")
 DIS_ORDER = ("P7", "P6", "P5", "P4", "P3")  # order the reference builds them in (tools/train_net_da.py:223-274)
@@ -197,9 +198,21 @@ class RetinaNetModuleNCHW(_RpnForwardNCHW, RetinaNetModule):
         return None, losses, {"box_cls": ops.PyramidLevels(logits, shape), "box_regression": ops.PyramidLevels(reg, shape)}
 
 
+class RPNModuleNCHW(RPNModule):
+    """RPNModule.forward of the reference (rpn/rpn.py:142-198): (images, features, targets) -> (list[BoxList] with field
+    "objectness" | None, losses).  With MODEL.RPN_ONLY in training the boxes are None (the reference returns its anchor lists;
+    there is no anchor tensor here)."""
+
+    def forward(self, images, features, targets=None):
+        il = to_image_list(images)
+        rows, shape = ops.pack_levels(features)
+        return super().forward(il.image_sizes, rows, shape, targets=target_tuples(targets))
+
+
 def build_rpn(cfg, in_channels):
     """reference modeling/rpn/rpn.py:201-212: ATSS_ON -> the ATSS head, else FCOS_ON -> the FCOS head, else RETINANET_ON -> the
-    RetinaNet head."""
+    RetinaNet head, else the region-proposal network -- built only when the cfg itself carries a MODEL.RPN block (the shipped
+    yamls carry none, and config.RPN_DEFAULTS stays out of config.DEFAULTS)."""
     if in_channels != 256:
         raise ValueError("the dense heads are built for 256 input channels, got %d" % in_channels)
     if cfg.MODEL.get("ATSS_ON", False):
@@ -207,7 +220,10 @@ def build_rpn(cfg, in_channels):
     if not cfg.MODEL.get("FCOS_ON", False):
         if cfg.MODEL.get("RETINANET_ON", False):
             return _channels_last_(RetinaNetModuleNCHW(cfg=config.retinanet_settings(cfg)))
-        raise ValueError("MODEL.ATSS_ON, MODEL.FCOS_ON and MODEL.RETINANET_ON are False: only those three heads are built (no RPN)")
+        if isinstance(cfg.MODEL.get("RPN"), dict):
+            return _channels_last_(RPNModuleNCHW(cfg=config.rpn_settings(cfg)))
+        raise ValueError("MODEL.ATSS_ON, MODEL.FCOS_ON and MODEL.RETINANET_ON are False and the cfg has no MODEL.RPN block: those "
+                         "three heads are built, and a MODEL.RPN block selects the RPN")
     if not cfg.MODEL.MIDDLE_HEAD.CONDGRAPH_ON:  # the EPM baseline: the plain head, centerness where MODEL.FCOS.REG_CTR_ON puts it
         h = config.epm_settings(cfg)["head"]
         return _channels_last_(FCOSModuleNCHW(h["num_classes"], h["test_mode"], h))

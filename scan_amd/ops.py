@@ -1625,6 +1625,148 @@ def retina_smooth_l1_loss(bbox_reg, shape, strides, cells, boxes, labels_i32, ma
     return _RetinaSmoothL1.apply(bbox_reg, geo, boxes, labels_i32, matched, float(beta), targets_out)
 
 
+# ----------------------------------------------------------------------------- region-proposal network (csrc/rpn.hip)
+def _rpn_geometry(who, shape, strides, cells):
+    if cells.dim() != 3 or cells.shape[0] != shape.n_levels or cells.shape[2] != 4 or len(strides) != shape.n_levels:
+        raise ValueError("%s: %d strides / cells %r for %d levels" % (who, len(strides), tuple(cells.shape), shape.n_levels))
+    return (ctypes.c_int32 * shape.n_levels)(*[int(s) for s in strides]), int(cells.shape[1])
+
+
+def _rpn_image_hw(who, shape, image_hw):
+    if image_hw.dtype != torch.int32 or tuple(image_hw.shape) != (shape.n_images, 2) or not image_hw.is_contiguous():
+        raise ValueError("%s: image_hw must be int32 [N, 2] (height, width), got %r %s" % (who, tuple(image_hw.shape), image_hw.dtype))
+
+
+def rpn_labels(shape, strides, cells, boxes, ng, image_hw, bg_thr, fg_thr, straddle_thresh):
+    """RPN labels of every anchor (reference rpn/loss.py:56-89): 1 matched (IoU >= fg_thr, or a low-quality match), 0 below
+    bg_thr, -1 between the thresholds or not visible in its image.  boxes [N, G, 4] fp32, ng [N] int32, image_hw [N, 2] int32
+    (height, width), all on the device.  -> labels_i32 [M * A], matched [M * A] int32.  The matcher's two launches with every
+    box label 1, then the visibility launch (none when straddle_thresh < 0); no host read."""
+    strides_h, A = _rpn_geometry("rpn_labels", shape, strides, cells)
+    if boxes.dim() != 3 or boxes.shape[0] != shape.n_images or boxes.shape[2] != 4 or boxes.shape[1] < 1 or boxes.dtype != torch.float32:
+        raise ValueError("rpn_labels: boxes must be fp32 [N, G >= 1, 4], got %r" % (tuple(boxes.shape),))
+    if ng.dtype != torch.int32 or ng.numel() != shape.n_images:
+        raise ValueError("rpn_labels: ng must be int32 [N]")
+    if not float(bg_thr) <= float(fg_thr):
+        raise ValueError("rpn_labels: bg_thr %r above fg_thr %r" % (bg_thr, fg_thr))
+    _rpn_image_hw("rpn_labels", shape, image_hw)
+    _chk(cells, boxes, ng, image_hw)
+    dev, G = boxes.device, int(boxes.shape[1])
+    labels = torch.empty((shape.rows * A,), dtype=torch.int32, device=dev)
+    matched = torch.empty((shape.rows * A,), dtype=torch.int32, device=dev)
+    glab = torch.ones((shape.n_images, G), dtype=torch.int64, device=dev)
+    # the matcher's ABI wants its positive counter; nothing reads it here (the visibility launch makes it stale, the sampler counts)
+    n_pos = torch.empty((1,), dtype=torch.int32, device=dev)
+    ws = torch.empty((query("scan_retina_match_ws_bytes", shape.ref(), G) // 4,), dtype=torch.int32, device=dev)
+    call("scan_retina_match", shape.ref(), strides_h, _ptr(cells), A, _ptr(boxes), _ptr(glab), _ptr(ng), G, float(bg_thr),
+         float(fg_thr), _ptr(labels), _ptr(matched), _ptr(n_pos), _ptr(ws), _stream())
+    call("scan_rpn_visibility", shape.ref(), strides_h, _ptr(cells), A, _ptr(image_hw), float(straddle_thresh), _ptr(labels),
+         _ptr(matched), _stream())
+    return labels, matched
+
+
+def rpn_sample(shape, A, labels_i32, batch_size_per_image, positive_fraction, seed=0, keys=None):
+    """BalancedPositiveNegativeSampler on the device, one launch for all images: per image the int(batch_size_per_image *
+    positive_fraction) positives (label >= 1) and then the negatives (label == 0) with the smallest (key, anchor index) pairs;
+    the key is the integer mix of (seed, image, anchor index) written out in include/scan_hip.h, or keys [M * A] (int32 /
+    uint32 bits) when given.  -> sampled uint8 [M * A] (1 positive, 2 negative, 0 not sampled), counts int32 [N, 2]."""
+    n = shape.rows * int(A)
+    if labels_i32.dtype != torch.int32 or labels_i32.numel() != n:
+        raise ValueError("rpn_sample: labels_i32 must be int32 [M * A] = [%d]" % n)
+    if int(batch_size_per_image) < 1:
+        raise ValueError("rpn_sample: batch_size_per_image %r < 1" % (batch_size_per_image,))
+    if not 0 < float(positive_fraction) <= 1:
+        raise ValueError("rpn_sample: positive_fraction %r outside (0, 1]" % (positive_fraction,))
+    if keys is not None and (keys.dtype not in (torch.int32, torch.uint32) or keys.numel() != n or not keys.is_contiguous()):
+        raise ValueError("rpn_sample: keys must be 32-bit integers [M * A]")
+    _chk(labels_i32, keys)
+    sampled = torch.empty((n,), dtype=torch.uint8, device=labels_i32.device)
+    counts = torch.empty((shape.n_images, 2), dtype=torch.int32, device=labels_i32.device)
+    call("scan_rpn_sample", shape.ref(), int(A), _ptr(labels_i32), int(batch_size_per_image),
+         int(int(batch_size_per_image) * float(positive_fraction)), int(seed) & 0xffffffff, _ptr(keys), _ptr(sampled), _ptr(counts),
+         _stream())
+    return sampled, counts
+
+
+class _RpnLoss(torch.autograd.Function):
+    """(sum of the objectness BCE over the sampled anchors, sum of smooth-L1 over the sampled positives) as a [2] tensor
+    (reference rpn/loss.py:92-131 before the division by the sampled count); anchors and encoded targets are formed in the
+    kernel (csrc/rpn.hip), over all M * A anchors.  Both head outputs are read in place through their row pitches."""
+
+    @staticmethod
+    def forward(ctx, objectness, bbox_reg, geo, boxes, matched, sampled, beta, targets_out):
+        shape, strides, cells, A = geo
+        _chk(boxes, matched, sampled, cells, targets_out)
+        ld_obj = _row_pitch(objectness, A, "objectness", who="rpn_loss")
+        ld_reg = _row_pitch(bbox_reg, 4 * A, "bbox_reg", who="rpn_loss")
+        out = bbox_reg.new_zeros((2,))
+        args = (shape.ref(), strides, _ptr(cells), A, _ptr(boxes), boxes.shape[1], _ptr(matched), _ptr(sampled), _ptr(objectness),
+                ld_obj, _ptr(bbox_reg), ld_reg, beta)
+        _call_reduction("scan_rpn_loss", "_forward", bbox_reg, (shape.rows * A,), *args, _ptr(targets_out), _ptr(out))
+        ctx.save_for_backward(objectness, bbox_reg, boxes, matched, sampled, cells)
+        ctx.args = args + (shape,)  # (the shape owns the descriptor args[0] points to)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        objectness, bbox_reg = ctx.saved_tensors[:2]
+        d_obj = torch.empty(objectness.shape, dtype=torch.float32, device=objectness.device)
+        d_reg = torch.empty(bbox_reg.shape, dtype=torch.float32, device=bbox_reg.device)
+        call("scan_rpn_loss_backward", *ctx.args[:-1], _ptr(g.reshape(2).contiguous()), _ptr(d_obj), d_obj.shape[1], _ptr(d_reg),
+             d_reg.shape[1], _stream())
+        return d_obj, d_reg, None, None, None, None, None, None
+
+
+def rpn_loss(objectness, bbox_reg, shape, strides, cells, boxes, matched, sampled, beta, targets_out=None):
+    """objectness [M, A] and bbox_reg [M, 4 A] (column slices of wider row matrices are read in place), cells [n_levels, A, 4]
+    on the device, boxes [N, G, 4], matched int32 [M * A] (ops.rpn_labels), sampled uint8 [M * A] (ops.rpn_sample) -> [2]:
+    the summed BCE-with-logits of the sampled anchors (target 1 where sampled == 1, 0 where sampled == 2) and the summed
+    smooth-L1 of the sampled positives against BoxCoder.encode (weights 1) of their matched boxes.  targets_out [M * A, 4]
+    (optional) receives the encoded targets."""
+    strides_h, A = _rpn_geometry("rpn_loss", shape, strides, cells)
+    n = shape.rows * A
+    if objectness.dim() != 2 or tuple(objectness.shape) != (shape.rows, A):
+        raise ValueError("rpn_loss: objectness %r for %d rows of %d anchors" % (tuple(objectness.shape), shape.rows, A))
+    if bbox_reg.dim() != 2 or tuple(bbox_reg.shape) != (shape.rows, 4 * A):
+        raise ValueError("rpn_loss: bbox_reg %r for %d rows of %d anchors" % (tuple(bbox_reg.shape), shape.rows, A))
+    if boxes.dim() != 3 or boxes.shape[0] != shape.n_images or boxes.shape[2] != 4 or boxes.shape[1] < 1:
+        raise ValueError("rpn_loss: boxes must be fp32 [N, G >= 1, 4], got %r" % (tuple(boxes.shape),))
+    if matched.dtype != torch.int32 or matched.numel() != n:
+        raise ValueError("rpn_loss: matched must be int32 [M * A]")
+    if sampled.dtype != torch.uint8 or sampled.numel() != n:
+        raise ValueError("rpn_loss: sampled must be uint8 [M * A]")
+    if targets_out is not None and (tuple(targets_out.shape) != (n, 4) or targets_out.dtype != torch.float32):
+        raise ValueError("rpn_loss: targets_out must be fp32 [M * A, 4]")
+    if not float(beta) > 0:
+        raise ValueError("rpn_loss: beta %r must be positive" % (beta,))
+    return _RpnLoss.apply(objectness, bbox_reg, (shape, strides_h, cells, A), boxes, matched, sampled, float(beta), targets_out)
+
+
+def rpn_decode_proposals(bbox_reg, shape, strides, cells, topk_idx, ks, image_hw, min_size=0):
+    """The decode / clip / small-box step of the proposal selection (reference rpn/inference.py:95-113) in one launch: topk_idx
+    [N, sum(ks)] int64, the per-level top-k anchor indices within each image's level side by side (ks[l] columns for level l)
+    -> boxes [N, K, 4] clipped to the image, keep [N, K] uint8 (both extents >= min_size)."""
+    strides_h, A = _rpn_geometry("rpn_decode_proposals", shape, strides, cells)
+    if bbox_reg.dim() != 2 or tuple(bbox_reg.shape) != (shape.rows, 4 * A):
+        raise ValueError("rpn_decode_proposals: bbox_reg %r for %d rows of %d anchors" % (tuple(bbox_reg.shape), shape.rows, A))
+    if len(ks) != shape.n_levels or any(not 0 <= int(k) <= h * w * A for k, (h, w) in zip(ks, shape.sizes)):
+        raise ValueError("rpn_decode_proposals: ks %r: one candidate count per level, at most h * w * A" % (tuple(ks),))
+    K = sum(int(k) for k in ks)
+    if topk_idx.dtype != torch.int64 or tuple(topk_idx.shape) != (shape.n_images, K) or not topk_idx.is_contiguous():
+        raise ValueError("rpn_decode_proposals: topk_idx must be contiguous int64 [N, sum(ks)] = [%d, %d]" % (shape.n_images, K))
+    _rpn_image_hw("rpn_decode_proposals", shape, image_hw)
+    _chk(cells, topk_idx, image_hw)
+    ld = _row_pitch(bbox_reg, 4 * A, "bbox_reg", who="rpn_decode_proposals")
+    off = [0]
+    for k in ks:
+        off.append(off[-1] + int(k))
+    boxes = torch.empty((shape.n_images, K, 4), dtype=torch.float32, device=bbox_reg.device)
+    keep = torch.empty((shape.n_images, K), dtype=torch.uint8, device=bbox_reg.device)
+    call("scan_rpn_decode", shape.ref(), strides_h, _ptr(cells), A, _ptr(bbox_reg), ld, _ptr(topk_idx),
+         (ctypes.c_int32 * len(off))(*off), _ptr(image_hw), float(min_size), _ptr(boxes), _ptr(keep), _stream())
+    return boxes, keep
+
+
 class _BceLogitsMean(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, targets):
