@@ -9,7 +9,6 @@ the anchor of row (level l, y, x) has centre (x * s + (s - 1) / 2, y * s + (s - 
 The assignment (loss.py:159-218) -- with this project's tie rules where the reference leaves the choice to torch.topk /
 torch.max -- is stated in csrc/atss.hip; ``assign_targets`` below is its torch spelling and the kernels are held equal to it.
 """
-import ctypes
 import math
 
 import torch
@@ -165,29 +164,11 @@ def _build_plan_device(shape, targets, device, strides, sizes, topk):
     level count are, and ONE host read (the per-level positive counts)."""
     p = ATSSTargetPlan()
     p.ready = None
-    N, L, M = shape.n_images, shape.n_levels, shape.rows
-    boxes, glab, ng, G = fcos_mod.upload_ground_truth(N, targets, device)
-    st = ops._stream()
-    p.labels = torch.empty((M,), dtype=torch.int64, device=device)
-    p.labels_i32 = torch.empty((M,), dtype=torch.int32, device=device)
-    p.matched = torch.empty((M,), dtype=torch.int32, device=device)
-    level_pos = torch.empty((8,), dtype=torch.int32, device=device)
-    pos_list = torch.empty((M,), dtype=torch.int32, device=device)
-    neg_list = torch.empty((M,), dtype=torch.int32, device=device)
-    ws = torch.empty((ops.query("scan_atss_assign_ws_bytes", shape.ref(), G, topk) // 8,), dtype=torch.int64, device=device)
-    strides_h = (ctypes.c_int32 * L)(*[int(s) for s in strides])
-    sizes_h = (ctypes.c_float * L)(*[float(a) for a in sizes])
-    ops.call("scan_atss_assign", shape.ref(), strides_h, sizes_h, ops._ptr(boxes), ops._ptr(glab), ops._ptr(ng), G, topk,
-             ops._ptr(p.labels), ops._ptr(p.labels_i32), ops._ptr(p.matched), ops._ptr(level_pos), ops._ptr(ws), st)
-    ops.call("scan_fcos_compact", shape.ref(), ops._ptr(p.labels), ops._ptr(pos_list), ops._ptr(neg_list), st)
-    counts = level_pos[:L].tolist()  # the one host round trip of the plan
-    cnt_h = (ctypes.c_int32 * L)(*counts)
+    boxes, glab, ng, _ = fcos_mod.upload_ground_truth(shape.n_images, targets, device)
+    p.labels, p.labels_i32, p.matched, level_pos, pos_list, _ = ops.atss_assign(shape, strides, sizes, topk, boxes, glab, ng)
+    counts = level_pos[:shape.n_levels].tolist()  # the one host round trip of the plan
     p.n_pos = int(sum(counts))
-    p.pos_inds = torch.empty((p.n_pos,), dtype=torch.int64, device=device)
-    p.reg_pos = torch.empty((p.n_pos, 4), dtype=torch.float32, device=device)
-    p.ctr_pos = torch.empty((p.n_pos,), dtype=torch.float32, device=device)
-    ops.call("scan_atss_targets", shape.ref(), strides_h, sizes_h, cnt_h, ops._ptr(boxes), G, ops._ptr(p.matched),
-             ops._ptr(pos_list), ops._ptr(p.pos_inds), ops._ptr(p.reg_pos), ops._ptr(p.ctr_pos), st)
+    p.pos_inds, p.reg_pos, p.ctr_pos = ops.atss_targets(shape, strides, sizes, counts, boxes, p.matched, pos_list)
     plan_stats.update(launches=4 + (1 if p.n_pos else 0), host_reads=1)
     return p
 
@@ -206,10 +187,7 @@ def build_plan(shape, targets, device, strides=ANCHOR_STRIDES, sizes=ANCHOR_SIZE
     off = torch.tensor(shape.row_off[:-1], device=device)
     lvl = torch.bucketize(p.pos_inds, torch.tensor(shape.row_off[1:], device=device), right=True)
     img = torch.div(p.pos_inds - off[lvl], hw[lvl], rounding_mode="floor")
-    G = max(1, max((int(b.shape[0]) for b, _ in targets), default=1))
-    boxes = torch.zeros((shape.n_images, G, 4), dtype=torch.float32, device=device)
-    for i, (b, _) in enumerate(targets):
-        boxes[i, :int(b.shape[0])] = b.to(device=device, dtype=torch.float32)
+    boxes = fcos_mod.pack_boxes(shape.n_images, targets, device)
     # targets in fp64, rounded once (as the kernel forms them: see scan_atss_targets in csrc/atss.hip)
     anchors = row_anchors(shape, device, strides, sizes)[p.pos_inds].double()
     reg = encode(boxes[img, p.matched[p.pos_inds].long()].double(), anchors)

@@ -280,8 +280,7 @@ class GRAPHModule(nn.Module):
         if P.is_cuda and P.dtype == torch.float32 and P.is_contiguous() and P.shape[1] <= 1024 and FUSED_PARADIGM_UPDATE:
             # the rest of this function as ONE launch (csrc/pointwise.hip: paradigm_update_kernel) instead of ~25 one-row torch
             # launches on the critical small-kernel stretch of the step
-            ops.call("scan_paradigm_update", ops._ptr(P), ops._ptr(pb.contiguous().float()), P.shape[0], P.shape[1], P.shape[2],
-                     int(it), ops._stream())
+            ops.paradigm_update_(P, pb, it)
             return
         exist = pb.sum(-1).bool()[:, None]
         slot = it - 1 if it == self.prototype_iter else it

@@ -8,7 +8,6 @@ image, y, x; rpn/fcos/loss.py:191-202) the losses consume the conv outputs with 
 permute/reshape/cat copies.
 """
 import contextlib
-import ctypes
 import math
 
 import torch
@@ -143,6 +142,16 @@ DEVICE_PLAN = True  # False: the torch spelling below also on the GPU (A/B, cros
 _plan_staging = {}  # (N, device) -> pinned host buffers of the packed ground truth, grown (never shrunk) to a power of two of boxes
 
 
+def pack_boxes(N, targets, device):
+    """the boxes of a batch zero-padded to [N, G, 4] fp32 on ``device``; G: the largest count of an image, at least 1"""
+    G = max(1, max((int(b.shape[0]) for b, _ in targets), default=1))
+    boxes = torch.zeros((N, G, 4), dtype=torch.float32, device=device)
+    for i, (b, _) in enumerate(targets):
+        if int(b.shape[0]):
+            boxes[i, :int(b.shape[0])] = b.to(device=device, dtype=torch.float32)
+    return boxes
+
+
 def upload_ground_truth(N, targets, device):
     """(boxes [N, G, 4] fp32 xyxy zero-padded, labels [N, G] int64, counts [N] int32, G) of a batch on ``device``."""
     G = max(1, max(int(b.shape[0]) for b, _ in targets))
@@ -171,13 +180,11 @@ def upload_ground_truth(N, targets, device):
             hn[i] = g
         boxes, glab, ng = (t.to(device, non_blocking=True) for t in (hb, hl, hn))
     else:
-        boxes = torch.zeros((N, G, 4), dtype=torch.float32, device=device)
+        boxes = pack_boxes(N, targets, device)
         glab = torch.zeros((N, G), dtype=torch.int64, device=device)
         for i, (b, l) in enumerate(targets):
-            g = int(b.shape[0])
-            if g:
-                boxes[i, :g] = b.to(device=device, dtype=torch.float32)
-                glab[i, :g] = l.to(device=device, dtype=torch.int64)
+            if int(b.shape[0]):
+                glab[i, :int(b.shape[0])] = l.to(device=device, dtype=torch.int64)
         ng = torch.tensor([int(b.shape[0]) for b, _ in targets], dtype=torch.int32).to(device)
     return boxes, glab, ng, G
 
@@ -187,32 +194,14 @@ def _build_plan_device(shape, targets, device):
     ~115 torch launches with a dozen host round trips; bit-identical to the torch spelling below."""
     p = TargetPlan()
     p.ready = None
-    N, L, M = shape.n_images, shape.n_levels, shape.rows
-    boxes, glab, ng, G = upload_ground_truth(N, targets, device)
-    st = ops._stream()
-    p.labels = torch.empty((M,), dtype=torch.int64, device=device)
-    p.labels_i32 = torch.empty((M,), dtype=torch.int32, device=device)
-    p.reg_targets = torch.empty((M, 4), dtype=torch.float32, device=device)
-    level_pos = torch.empty((8,), dtype=torch.int32, device=device)
-    pos_list = torch.empty((M,), dtype=torch.int32, device=device)
-    neg_list = torch.empty((M,), dtype=torch.int32, device=device)
-    strides_h = (ctypes.c_int32 * L)(*FPN_STRIDES[:L])
-    soi_h = (ctypes.c_float * (2 * L))(*[float(v) for l in range(L) for v in SIZES_OF_INTEREST[l]])
-    ops.call("scan_fcos_assign", shape.ref(), strides_h, soi_h, ops._ptr(boxes), ops._ptr(glab), ops._ptr(ng), G,
-             ops._ptr(p.labels), ops._ptr(p.labels_i32), ops._ptr(p.reg_targets), ops._ptr(level_pos), st)
-    ops.call("scan_fcos_compact", shape.ref(), ops._ptr(p.labels), ops._ptr(pos_list), ops._ptr(neg_list), st)
+    L = shape.n_levels
+    boxes, glab, ng, _ = upload_ground_truth(shape.n_images, targets, device)
+    p.labels, p.labels_i32, p.reg_targets, level_pos, pos_list, neg_list = ops.fcos_assign(
+        shape, FPN_STRIDES[:L], SIZES_OF_INTEREST[:L], boxes, glab, ng)
     counts = level_pos[:L].tolist()  # the one host round trip of the plan
-    cnt_h = (ctypes.c_int32 * L)(*counts)
-    n_nodes = ops.query("scan_fcos_nodes_count", shape.ref(), cnt_h)
     p.n_pos = int(sum(counts))
-    p.node_index = torch.empty((n_nodes,), dtype=torch.int64, device=device)
-    p.node_labels = torch.empty((n_nodes,), dtype=torch.int64, device=device)
-    p.pos_inds = torch.empty((p.n_pos,), dtype=torch.int64, device=device)
-    p.reg_pos = torch.empty((p.n_pos, 4), dtype=torch.float32, device=device)
-    ctr = torch.empty((p.n_pos,), dtype=torch.float32, device=device)
-    ops.call("scan_fcos_nodes", shape.ref(), cnt_h, ops._ptr(p.labels), ops._ptr(p.reg_targets), ops._ptr(pos_list),
-             ops._ptr(neg_list), ops._ptr(p.node_index), ops._ptr(p.node_labels), ops._ptr(p.pos_inds),
-             ops._ptr(p.reg_pos), ops._ptr(ctr), st)
+    p.node_index, p.node_labels, p.pos_inds, p.reg_pos, ctr = ops.fcos_nodes(shape, counts, p.labels, p.reg_targets, pos_list,
+                                                                             neg_list)
     p.ctr_pos = ctr if p.n_pos > 0 else None
     return p
 

@@ -13,7 +13,6 @@ COPY of their first A * C columns otherwise (autograd returns the gradient throu
 
 ``assign_targets`` is the torch spelling of the assignment, on any device; the kernels are held equal to it.
 """
-import ctypes
 import math
 
 import numpy as np
@@ -185,30 +184,13 @@ def _check_geometry(shape, strides, cells):
         raise ValueError("RetinaNet: %d anchors per location; the kernels are built for 1..%d" % (cells.shape[1], MAX_ANCHORS))
 
 
-def _pack_boxes(N, targets, device):
-    G = max(1, max((int(b.shape[0]) for b, _ in targets), default=1))
-    boxes = torch.zeros((N, G, 4), dtype=torch.float32, device=device)
-    for i, (b, _) in enumerate(targets):
-        boxes[i, :int(b.shape[0])] = b.to(device=device, dtype=torch.float32)
-    return boxes
-
-
 def _build_plan_device(shape, targets, device, strides, cells, bg, fg):
     """csrc/retina.hip: two memsets and two launches whatever N, G, A and the level count are, and ONE host read (the positive
     count)."""
     p = RetinaTargetPlan()
     p.ready = None
-    n_anchors = shape.rows * int(cells.shape[1])
-    boxes, glab, ng, G = fcos_mod.upload_ground_truth(shape.n_images, targets, device)
-    p.boxes = boxes
-    p.labels_i32 = torch.empty((n_anchors,), dtype=torch.int32, device=device)
-    p.matched = torch.empty((n_anchors,), dtype=torch.int32, device=device)
-    n_pos = torch.empty((1,), dtype=torch.int32, device=device)
-    ws = torch.empty((ops.query("scan_retina_match_ws_bytes", shape.ref(), G) // 4,), dtype=torch.int32, device=device)
-    strides_h = (ctypes.c_int32 * shape.n_levels)(*[int(s) for s in strides])
-    ops.call("scan_retina_match", shape.ref(), strides_h, ops._ptr(device_cells(cells, device)), int(cells.shape[1]),
-             ops._ptr(boxes), ops._ptr(glab), ops._ptr(ng), G, float(bg), float(fg), ops._ptr(p.labels_i32), ops._ptr(p.matched),
-             ops._ptr(n_pos), ops._ptr(ws), ops._stream())
+    p.boxes, glab, ng, _ = fcos_mod.upload_ground_truth(shape.n_images, targets, device)
+    p.labels_i32, p.matched, n_pos = ops.retina_match(shape, strides, device_cells(cells, device), p.boxes, glab, ng, bg, fg)
     p.n_pos = int(n_pos.item())  # the one host round trip of the plan
     plan_stats.update(launches=2, host_reads=1)
     return p
@@ -223,7 +205,7 @@ def build_plan(shape, targets, device, strides=ANCHOR_STRIDES, cells=None, bg=0.
     p.ready = None
     p.labels_i32, p.matched = assign_targets(shape, targets, cells.to(device), strides, bg, fg)
     p.n_pos = int((p.labels_i32 > 0).sum())
-    p.boxes = _pack_boxes(shape.n_images, targets, device)
+    p.boxes = fcos_mod.pack_boxes(shape.n_images, targets, device)
     return p
 
 

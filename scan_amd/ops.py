@@ -45,6 +45,15 @@ def pad4(c):
     return (c + 3) // 4 * 4
 
 
+def _level_table(who, shape, ctype, values, what, per_level=1):
+    """the host table of a per-level quantity (strides, anchor sizes, sizes of interest, counts) as the ctypes array the library
+    reads: ``per_level`` entries for each of the shape's levels"""
+    values = list(values)
+    if len(values) != per_level * shape.n_levels:
+        raise ValueError("%s: %d %s for a pyramid of %d levels" % (who, len(values) // per_level, what, shape.n_levels))
+    return (ctype * len(values))(*[(float if ctype is ctypes.c_float else int)(v) for v in values])
+
+
 # ----------------------------------------------------------------------------- deterministic mode
 # scan_tune "deterministic" (SCAN_TUNE=deterministic=1) lives in the library and is the only copy of the switch: it is read
 # at every call that chooses between an atomic reduction and its *_ordered twin, never cached -- for the losses and the conv
@@ -1545,6 +1554,164 @@ def iou_loss(pred, target, weight=None):
     return _IouLoss.apply(pred.contiguous(), target.contiguous(), weight.contiguous() if weight is not None else None)
 
 
+# ----------------------------------------------------------------------------- ground-truth plans of the heads
+# (csrc/targets.hip, atss.hip, retina.hip).  Ground truth as modeling.fcos.upload_ground_truth packs it: boxes [N, G, 4] fp32 xyxy
+# zero-padded, glab [N, G] int64, ng [N] int32 (the boxes each image has), on the device.  Nothing here reads the device: the
+# one host read of a plan (the positive counts) is its builder's, between the assignment and the target step.
+def _anchor_geometry(who, shape, strides, cells):
+    """(strides table, A) of a head with the cell anchors cells [n_levels, A, 4]"""
+    if cells.dim() != 3 or cells.shape[0] != shape.n_levels or cells.shape[2] != 4:
+        raise ValueError("%s: cell anchors %r for a pyramid of %d levels" % (who, tuple(cells.shape), shape.n_levels))
+    return _level_table(who, shape, ctypes.c_int32, strides, "strides"), int(cells.shape[1])
+
+
+def _ground_truth(who, shape, boxes, glab, ng):
+    if boxes.dim() != 3 or boxes.shape[0] != shape.n_images or boxes.shape[2] != 4 or boxes.shape[1] < 1 or boxes.dtype != torch.float32:
+        raise ValueError("%s: boxes must be fp32 [N, G >= 1, 4], got %r" % (who, tuple(boxes.shape)))
+    if glab.dtype != torch.int64 or tuple(glab.shape) != tuple(boxes.shape[:2]) or not glab.is_contiguous():
+        raise ValueError("%s: box labels must be contiguous int64 [N, G], got %r %s" % (who, tuple(glab.shape), glab.dtype))
+    if ng.dtype != torch.int32 or ng.numel() != shape.n_images:
+        raise ValueError("%s: ng must be int32 [N]" % who)
+    return int(boxes.shape[1])
+
+
+def _row_vector(who, shape, t, dtype, name, per_row=1):
+    if t.dtype != dtype or t.numel() != shape.rows * per_row or not t.is_contiguous():
+        raise ValueError("%s: %s must be contiguous %s with %d elements, got %r %s"
+                         % (who, name, dtype, shape.rows * per_row, tuple(t.shape), t.dtype))
+
+
+def _level_counts(who, shape, counts):
+    if len(counts) == shape.n_levels and any(not 0 <= int(c) <= shape.n_images * h * w for c, (h, w) in zip(counts, shape.sizes)):
+        raise ValueError("%s: positive counts %r beyond the levels' rows" % (who, list(counts)))
+    return _level_table(who, shape, ctypes.c_int32, counts, "positive counts")
+
+
+def _row_lists(shape, device):
+    """level_pos int32 [8] and the pos_list / neg_list int32 [M] scan_fcos_compact fills"""
+    return (torch.empty((8,), dtype=torch.int32, device=device), torch.empty((shape.rows,), dtype=torch.int32, device=device),
+            torch.empty((shape.rows,), dtype=torch.int32, device=device))
+
+
+def fcos_assign(shape, strides, sizes_of_interest, boxes, glab, ng):
+    """The FCOS assignment (reference rpn/fcos/loss.py:40-126) and its compaction, two launches: strides and sizes_of_interest
+    [(lo, hi)] per level -> labels int64 [M], labels_i32 [M], reg_targets [M, 4], level_pos int32 [8] (the positives of every
+    level, on the device) and pos_list / neg_list int32 [M] (the positive / background rows of every level in row order)."""
+    strides_h = _level_table("fcos_assign", shape, ctypes.c_int32, strides, "strides")
+    soi_h = _level_table("fcos_assign", shape, ctypes.c_float, [v for lo_hi in sizes_of_interest for v in lo_hi],
+                         "sizes of interest", per_level=2)
+    G = _ground_truth("fcos_assign", shape, boxes, glab, ng)
+    _chk(boxes, glab, ng)
+    dev, st = boxes.device, _stream()
+    labels = torch.empty((shape.rows,), dtype=torch.int64, device=dev)
+    labels_i32 = torch.empty((shape.rows,), dtype=torch.int32, device=dev)
+    reg_targets = torch.empty((shape.rows, 4), dtype=torch.float32, device=dev)
+    level_pos, pos_list, neg_list = _row_lists(shape, dev)
+    call("scan_fcos_assign", shape.ref(), strides_h, soi_h, _ptr(boxes), _ptr(glab), _ptr(ng), G, _ptr(labels), _ptr(labels_i32),
+         _ptr(reg_targets), _ptr(level_pos), st)
+    call("scan_fcos_compact", shape.ref(), _ptr(labels), _ptr(pos_list), _ptr(neg_list), st)
+    return labels, labels_i32, reg_targets, level_pos, pos_list, neg_list
+
+
+def fcos_nodes(shape, counts, labels, reg_targets, pos_list, neg_list):
+    """The positives' targets and the graph-node sampling index (reference rpn/fcos/loss.py:128-133, 428-463) from
+    ops.fcos_assign's outputs and counts, the per-level positives read on the host; one launch -> node_index / node_labels
+    int64 [nodes], pos_inds int64 [n_pos], reg_pos [n_pos, 4], ctr_pos [n_pos]."""
+    cnt_h = _level_counts("fcos_nodes", shape, counts)
+    _row_vector("fcos_nodes", shape, labels, torch.int64, "labels")
+    _row_vector("fcos_nodes", shape, reg_targets, torch.float32, "reg_targets", 4)
+    _row_vector("fcos_nodes", shape, pos_list, torch.int32, "pos_list")
+    _row_vector("fcos_nodes", shape, neg_list, torch.int32, "neg_list")
+    _chk(labels, reg_targets, pos_list, neg_list)
+    dev, n_pos = labels.device, int(sum(counts))
+    n_nodes = query("scan_fcos_nodes_count", shape.ref(), cnt_h)
+    node_index = torch.empty((n_nodes,), dtype=torch.int64, device=dev)
+    node_labels = torch.empty((n_nodes,), dtype=torch.int64, device=dev)
+    pos_inds = torch.empty((n_pos,), dtype=torch.int64, device=dev)
+    reg_pos = torch.empty((n_pos, 4), dtype=torch.float32, device=dev)
+    ctr_pos = torch.empty((n_pos,), dtype=torch.float32, device=dev)
+    call("scan_fcos_nodes", shape.ref(), cnt_h, _ptr(labels), _ptr(reg_targets), _ptr(pos_list), _ptr(neg_list), _ptr(node_index),
+         _ptr(node_labels), _ptr(pos_inds), _ptr(reg_pos), _ptr(ctr_pos), _stream())
+    return node_index, node_labels, pos_inds, reg_pos, ctr_pos
+
+
+def atss_assign(shape, strides, sizes, topk, boxes, glab, ng):
+    """The ATSS assignment (reference rpn/atss/loss.py:159-218; candidates, vote, labels) and scan_fcos_compact: strides and
+    anchor sizes per level -> labels int64 [M], labels_i32 [M], matched int32 [M] (the box of every row, 0 where background),
+    level_pos int32 [8] on the device and pos_list / neg_list int32 [M]."""
+    strides_h = _level_table("atss_assign", shape, ctypes.c_int32, strides, "strides")
+    sizes_h = _level_table("atss_assign", shape, ctypes.c_float, sizes, "anchor sizes")
+    G = _ground_truth("atss_assign", shape, boxes, glab, ng)
+    if int(topk) < 1:
+        raise ValueError("atss_assign: topk %r < 1" % (topk,))
+    _chk(boxes, glab, ng)
+    dev, st = boxes.device, _stream()
+    labels = torch.empty((shape.rows,), dtype=torch.int64, device=dev)
+    labels_i32 = torch.empty((shape.rows,), dtype=torch.int32, device=dev)
+    matched = torch.empty((shape.rows,), dtype=torch.int32, device=dev)
+    level_pos, pos_list, neg_list = _row_lists(shape, dev)
+    ws = torch.empty((query("scan_atss_assign_ws_bytes", shape.ref(), G, int(topk)) // 8,), dtype=torch.int64, device=dev)
+    call("scan_atss_assign", shape.ref(), strides_h, sizes_h, _ptr(boxes), _ptr(glab), _ptr(ng), G, int(topk), _ptr(labels),
+         _ptr(labels_i32), _ptr(matched), _ptr(level_pos), _ptr(ws), st)
+    call("scan_fcos_compact", shape.ref(), _ptr(labels), _ptr(pos_list), _ptr(neg_list), st)
+    return labels, labels_i32, matched, level_pos, pos_list, neg_list
+
+
+def atss_targets(shape, strides, sizes, counts, boxes, matched, pos_list):
+    """The positives of an ATSS plan from ops.atss_assign's outputs and counts, the per-level positives read on the host; one
+    launch (none without positives) -> pos_inds int64 [n_pos], reg_pos [n_pos, 4] (BoxCoder.encode of the matched box against
+    the row's anchor), ctr_pos [n_pos]."""
+    strides_h = _level_table("atss_targets", shape, ctypes.c_int32, strides, "strides")
+    sizes_h = _level_table("atss_targets", shape, ctypes.c_float, sizes, "anchor sizes")
+    cnt_h = _level_counts("atss_targets", shape, counts)
+    if boxes.dim() != 3 or boxes.shape[0] != shape.n_images or boxes.shape[2] != 4 or boxes.shape[1] < 1 or boxes.dtype != torch.float32:
+        raise ValueError("atss_targets: boxes must be fp32 [N, G >= 1, 4], got %r" % (tuple(boxes.shape),))
+    _row_vector("atss_targets", shape, matched, torch.int32, "matched")
+    _row_vector("atss_targets", shape, pos_list, torch.int32, "pos_list")
+    _chk(boxes, matched, pos_list)
+    dev, n_pos = boxes.device, int(sum(counts))
+    pos_inds = torch.empty((n_pos,), dtype=torch.int64, device=dev)
+    reg_pos = torch.empty((n_pos, 4), dtype=torch.float32, device=dev)
+    ctr_pos = torch.empty((n_pos,), dtype=torch.float32, device=dev)
+    call("scan_atss_targets", shape.ref(), strides_h, sizes_h, cnt_h, _ptr(boxes), int(boxes.shape[1]), _ptr(matched),
+         _ptr(pos_list), _ptr(pos_inds), _ptr(reg_pos), _ptr(ctr_pos), _stream())
+    return pos_inds, reg_pos, ctr_pos
+
+
+def retina_match(shape, strides, cells, boxes, glab, ng, bg_thr, fg_thr, who="retina_match"):
+    """The Matcher with allow_low_quality_matches (reference modeling/matcher.py:42-112) over the anchors of cells [n_levels,
+    A, 4] (on the device), two launches -> labels_i32 [M * A] (0 below bg_thr, -1 between the thresholds, else the matched
+    box's label), matched int32 [M * A] (0 where label <= 0) and the number of positives, int32 [1] on the device."""
+    strides_h, A = _anchor_geometry(who, shape, strides, cells)
+    G = _ground_truth(who, shape, boxes, glab, ng)
+    if not float(bg_thr) <= float(fg_thr):
+        raise ValueError("%s: bg_thr %r above fg_thr %r" % (who, bg_thr, fg_thr))
+    _chk(cells, boxes, glab, ng)
+    dev = boxes.device
+    labels = torch.empty((shape.rows * A,), dtype=torch.int32, device=dev)
+    matched = torch.empty((shape.rows * A,), dtype=torch.int32, device=dev)
+    n_pos = torch.empty((1,), dtype=torch.int32, device=dev)
+    ws = torch.empty((query("scan_retina_match_ws_bytes", shape.ref(), G) // 4,), dtype=torch.int32, device=dev)
+    call("scan_retina_match", shape.ref(), strides_h, _ptr(cells), A, _ptr(boxes), _ptr(glab), _ptr(ng), G, float(bg_thr),
+         float(fg_thr), _ptr(labels), _ptr(matched), _ptr(n_pos), _ptr(ws), _stream())
+    return labels, matched, n_pos
+
+
+def paradigm_update_(P, pb, it):
+    """GRAPHModule.update_prototype_nx1_rnn with COSINE_UPDATE_ON (reference rpn/fcos/condgraph.py:586-606) on the paradigm
+    buffer P [K, C, T] in place, one launch: slot ``it`` (the last one, after shifting the others down, when it == T) moves
+    towards the batch means pb [K, C] by their cosine similarity; classes whose mean is all zero keep their value."""
+    if P.dim() != 3 or P.dtype != torch.float32 or not P.is_contiguous() or P.shape[1] > 1024:
+        raise ValueError("paradigm_update_: P must be contiguous fp32 [K, C <= 1024, T], got %r %s" % (tuple(P.shape), P.dtype))
+    if tuple(pb.shape) != tuple(P.shape[:2]):
+        raise ValueError("paradigm_update_: pb %r for P %r" % (tuple(pb.shape), tuple(P.shape)))
+    if not 0 <= int(it) <= P.shape[2]:
+        raise ValueError("paradigm_update_: it %r outside 0..%d" % (it, P.shape[2]))
+    pb = pb.contiguous().float()
+    _chk(P, pb)
+    call("scan_paradigm_update", _ptr(P), _ptr(pb), P.shape[0], P.shape[1], P.shape[2], int(it), _stream())
+
+
 class _AtssGiouLoss(torch.autograd.Function):
     """sum(w * (1 - GIoU)) / sum(w) of anchor deltas (reference rpn/atss/loss.py:64-105, 396-397); the anchors are formed in the
     kernel from the rows (csrc/atss.hip).  The weight is a target (the centerness of the matched box): no gradient to it."""
@@ -1554,7 +1721,7 @@ class _AtssGiouLoss(torch.autograd.Function):
         _chk(pred, target, rows, weight)
         P = pred.shape[0]
         out = pred.new_zeros((2,))
-        geo = (shape.ref(), (ctypes.c_int32 * shape.n_levels)(*strides), (ctypes.c_float * shape.n_levels)(*sizes))
+        geo = (shape.ref(), strides, sizes)
         _call_reduction("scan_atss_giou", "_forward", pred, (P,), *geo, _ptr(pred), _ptr(target), _ptr(rows), _ptr(weight), P,
                         _ptr(out))
         ctx.save_for_backward(pred, target, rows, weight, out)
@@ -1574,10 +1741,9 @@ class _AtssGiouLoss(torch.autograd.Function):
 def atss_giou_loss(pred, target, rows, weight, shape, strides, sizes):
     """pred / target [P, 4] BoxCoder deltas of the pyramid rows ``rows`` [P] int64, weight [P]: the centerness-weighted GIoU
     loss of the ATSS head, normalised by the sum of the weights."""
-    if len(strides) != shape.n_levels or len(sizes) != shape.n_levels:
-        raise ValueError("atss_giou_loss: %d strides / %d anchor sizes for %d levels" % (len(strides), len(sizes), shape.n_levels))
     return _AtssGiouLoss.apply(pred.contiguous(), target.contiguous(), rows.contiguous(), weight.contiguous(), shape,
-                               [int(s) for s in strides], [float(a) for a in sizes])
+                               _level_table("atss_giou_loss", shape, ctypes.c_int32, strides, "strides"),
+                               _level_table("atss_giou_loss", shape, ctypes.c_float, sizes, "anchor sizes"))
 
 
 class _RetinaSmoothL1(torch.autograd.Function):
@@ -1610,10 +1776,7 @@ def retina_smooth_l1_loss(bbox_reg, shape, strides, cells, boxes, labels_i32, ma
     """bbox_reg [M, 4 A] (a column slice of a wider row matrix is read in place through its pitch), cells [n_levels, A, 4] the
     cell anchors on the device, boxes [N, G, 4], labels_i32 / matched [M * A] of the RetinaNet plan: the summed smooth-L1 loss
     of the positive anchors against their encoded boxes.  targets_out [M * A, 4] (optional) receives the targets."""
-    if cells.dim() != 3 or cells.shape[0] != shape.n_levels or cells.shape[2] != 4 or len(strides) != shape.n_levels:
-        raise ValueError("retina_smooth_l1_loss: %d strides / cell anchors %r for %d levels"
-                         % (len(strides), tuple(cells.shape), shape.n_levels))
-    A = int(cells.shape[1])
+    strides_h, A = _anchor_geometry("retina_smooth_l1_loss", shape, strides, cells)
     if bbox_reg.dim() != 2 or bbox_reg.shape != (shape.rows, 4 * A):
         raise ValueError("retina_smooth_l1_loss: bbox_reg %r for %d rows of %d anchors" % (tuple(bbox_reg.shape), shape.rows, A))
     if labels_i32.dtype != torch.int32 or matched.dtype != torch.int32 or labels_i32.numel() != shape.rows * A \
@@ -1621,17 +1784,10 @@ def retina_smooth_l1_loss(bbox_reg, shape, strides, cells, boxes, labels_i32, ma
         raise ValueError("retina_smooth_l1_loss: labels / matched must be int32 [M * A]")
     if targets_out is not None and (targets_out.shape != (shape.rows * A, 4) or targets_out.dtype != torch.float32):
         raise ValueError("retina_smooth_l1_loss: targets_out must be fp32 [M * A, 4]")
-    geo = (shape, (ctypes.c_int32 * shape.n_levels)(*[int(s) for s in strides]), cells, A)
-    return _RetinaSmoothL1.apply(bbox_reg, geo, boxes, labels_i32, matched, float(beta), targets_out)
+    return _RetinaSmoothL1.apply(bbox_reg, (shape, strides_h, cells, A), boxes, labels_i32, matched, float(beta), targets_out)
 
 
 # ----------------------------------------------------------------------------- region-proposal network (csrc/rpn.hip)
-def _rpn_geometry(who, shape, strides, cells):
-    if cells.dim() != 3 or cells.shape[0] != shape.n_levels or cells.shape[2] != 4 or len(strides) != shape.n_levels:
-        raise ValueError("%s: %d strides / cells %r for %d levels" % (who, len(strides), tuple(cells.shape), shape.n_levels))
-    return (ctypes.c_int32 * shape.n_levels)(*[int(s) for s in strides]), int(cells.shape[1])
-
-
 def _rpn_image_hw(who, shape, image_hw):
     if image_hw.dtype != torch.int32 or tuple(image_hw.shape) != (shape.n_images, 2) or not image_hw.is_contiguous():
         raise ValueError("%s: image_hw must be int32 [N, 2] (height, width), got %r %s" % (who, tuple(image_hw.shape), image_hw.dtype))
@@ -1642,24 +1798,13 @@ def rpn_labels(shape, strides, cells, boxes, ng, image_hw, bg_thr, fg_thr, strad
     bg_thr, -1 between the thresholds or not visible in its image.  boxes [N, G, 4] fp32, ng [N] int32, image_hw [N, 2] int32
     (height, width), all on the device.  -> labels_i32 [M * A], matched [M * A] int32.  The matcher's two launches with every
     box label 1, then the visibility launch (none when straddle_thresh < 0); no host read."""
-    strides_h, A = _rpn_geometry("rpn_labels", shape, strides, cells)
-    if boxes.dim() != 3 or boxes.shape[0] != shape.n_images or boxes.shape[2] != 4 or boxes.shape[1] < 1 or boxes.dtype != torch.float32:
-        raise ValueError("rpn_labels: boxes must be fp32 [N, G >= 1, 4], got %r" % (tuple(boxes.shape),))
-    if ng.dtype != torch.int32 or ng.numel() != shape.n_images:
-        raise ValueError("rpn_labels: ng must be int32 [N]")
-    if not float(bg_thr) <= float(fg_thr):
-        raise ValueError("rpn_labels: bg_thr %r above fg_thr %r" % (bg_thr, fg_thr))
+    strides_h, A = _anchor_geometry("rpn_labels", shape, strides, cells)
     _rpn_image_hw("rpn_labels", shape, image_hw)
-    _chk(cells, boxes, ng, image_hw)
-    dev, G = boxes.device, int(boxes.shape[1])
-    labels = torch.empty((shape.rows * A,), dtype=torch.int32, device=dev)
-    matched = torch.empty((shape.rows * A,), dtype=torch.int32, device=dev)
-    glab = torch.ones((shape.n_images, G), dtype=torch.int64, device=dev)
-    # the matcher's ABI wants its positive counter; nothing reads it here (the visibility launch makes it stale, the sampler counts)
-    n_pos = torch.empty((1,), dtype=torch.int32, device=dev)
-    ws = torch.empty((query("scan_retina_match_ws_bytes", shape.ref(), G) // 4,), dtype=torch.int32, device=dev)
-    call("scan_retina_match", shape.ref(), strides_h, _ptr(cells), A, _ptr(boxes), _ptr(glab), _ptr(ng), G, float(bg_thr),
-         float(fg_thr), _ptr(labels), _ptr(matched), _ptr(n_pos), _ptr(ws), _stream())
+    if image_hw.device != boxes.device:  # (the matcher refuses boxes that are not on the GPU)
+        raise ValueError("rpn_labels: image_hw on %s, boxes on %s" % (image_hw.device, boxes.device))
+    glab = torch.ones(tuple(boxes.shape[:2]), dtype=torch.int64, device=boxes.device)
+    # the matcher's positive counter is not read here: the visibility launch makes it stale, and the sampler counts
+    labels, matched, _ = retina_match(shape, strides, cells, boxes, glab, ng, bg_thr, fg_thr, who="rpn_labels")
     call("scan_rpn_visibility", shape.ref(), strides_h, _ptr(cells), A, _ptr(image_hw), float(straddle_thresh), _ptr(labels),
          _ptr(matched), _stream())
     return labels, matched
@@ -1723,7 +1868,7 @@ def rpn_loss(objectness, bbox_reg, shape, strides, cells, boxes, matched, sample
     the summed BCE-with-logits of the sampled anchors (target 1 where sampled == 1, 0 where sampled == 2) and the summed
     smooth-L1 of the sampled positives against BoxCoder.encode (weights 1) of their matched boxes.  targets_out [M * A, 4]
     (optional) receives the encoded targets."""
-    strides_h, A = _rpn_geometry("rpn_loss", shape, strides, cells)
+    strides_h, A = _anchor_geometry("rpn_loss", shape, strides, cells)
     n = shape.rows * A
     if objectness.dim() != 2 or tuple(objectness.shape) != (shape.rows, A):
         raise ValueError("rpn_loss: objectness %r for %d rows of %d anchors" % (tuple(objectness.shape), shape.rows, A))
@@ -1746,7 +1891,7 @@ def rpn_decode_proposals(bbox_reg, shape, strides, cells, topk_idx, ks, image_hw
     """The decode / clip / small-box step of the proposal selection (reference rpn/inference.py:95-113) in one launch: topk_idx
     [N, sum(ks)] int64, the per-level top-k anchor indices within each image's level side by side (ks[l] columns for level l)
     -> boxes [N, K, 4] clipped to the image, keep [N, K] uint8 (both extents >= min_size)."""
-    strides_h, A = _rpn_geometry("rpn_decode_proposals", shape, strides, cells)
+    strides_h, A = _anchor_geometry("rpn_decode_proposals", shape, strides, cells)
     if bbox_reg.dim() != 2 or tuple(bbox_reg.shape) != (shape.rows, 4 * A):
         raise ValueError("rpn_decode_proposals: bbox_reg %r for %d rows of %d anchors" % (tuple(bbox_reg.shape), shape.rows, A))
     if len(ks) != shape.n_levels or any(not 0 <= int(k) <= h * w * A for k, (h, w) in zip(ks, shape.sizes)):
