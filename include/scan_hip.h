@@ -763,6 +763,58 @@ int scan_rpn_decode(const scan_pyramid_t* d, const int32_t* strides, const float
                     int64_t ld, const int64_t* topk_idx, const int32_t* k_off, const int32_t* image_hw, float min_size,
                     float* boxes, uint8_t* keep, void* stream);
 
+/* ---- the Fast R-CNN box head (csrc/roi_box.hip; reference modeling/roi_heads/box_head/loss.py:39-167, inference.py:55-146,
+ *      modeling/matcher.py with allow_low_quality_matches False, modeling/box_coder.py).  Proposals of a batch are padded as the
+ *      ground truth is: props [N][P][4] fp32 xyxy (16-byte aligned), np [N] int32; rows p >= np[n] take no part.  boxes [N][G][4],
+ *      glabels [N][G] int64, ng [N] as scan_retina_match.  (wx, wy, ww, wh): BoxCoder's weights (BBOX_REG_WEIGHTS), positive.
+ *      scan_roi_box_match: one launch, no atomics, no workspace.  Per (image, proposal) max / argmax over the image's real boxes of
+ *      boxlist_iou(box, proposal) in fp32, every operation rounded on its own (the bits of scan_retina_match); equal IoUs: the
+ *      smaller box index.  max < bg_thr: label 0; bg_thr <= max < fg_thr: label -1; else glabels of the argmax; no low-quality
+ *      rule.  matched = argmax where label > 0, else 0.  Padding rows: label -1, matched 0.  ng[n] = 0: every real proposal is
+ *      background (the reference raises); np[n] = 0 is legal.  labels_i32 / matched [N * P].
+ *      Sampler: scan_rpn_sample on the pyramid of ONE level with h = P, w = 1 and N images, A = 1, walks exactly rows
+ *      [n P, (n + 1) P) of the padded labels for image n; padding (-1) is never drawn and gets sampled = 0; the key index of
+ *      proposal p of image n is i = n P + p.
+ *      scan_roi_box_gather: one launch, one workgroup per image; replaces proposals[img][nonzero(pos | neg)].  Reads sampled
+ *      [N * P] uint8 and counts [N][2] of the sampler and writes, for the sampled proposals in image-major order and ascending p
+ *      within an image (image n starts at the sum of the counts of the images before it, formed in the kernel; a running block
+ *      scan over P in chunks, no cap on P): rois [R][5] (image index, box), labels_out [R] int32 (the proposal's label where
+ *      sampled == 1, 0 for a sampled negative), reg_targets [R][4] (16-byte aligned) = BoxCoder.encode(boxes[n][matched],
+ *      proposal), TO_REMOVE = 1, formed in fp64 and rounded once, where label > 0 and zero elsewhere, src [R] int32 (p).  R comes
+ *      from the caller (the sum of counts); nothing is written at or beyond row R; R = 0 launches nothing.
+ *      scan_roi_box_loss_*: over the R sampled rows, a wave per row, any C >= 2.  class_logits [R][C] (row pitch ld_cls floats),
+ *      box_regression [R][4 Cr] (row pitch ld_reg, a multiple of 4; 16-byte aligned), Cr = C or 2 (CLS_AGNOSTIC_BBOX_REG), both
+ *      read in place; labels [R] int32 in 0 .. C - 1 (a row with any other label takes no part), reg_targets [R][4].  Forward
+ *      ADDS to out2 (clear it first): out2[0] += sum_r logsumexp(x_r) - x_r[label_r], max-subtracted in fp32 (m + log1p of the other exponentials' sum); out2[1] += sum over
+ *      label_r > 0 of smooth-L1 (beta 1) of columns [4 label_r, 4 label_r + 4) -- [4, 8) when Cr = 2 -- against reg_targets[r].
+ *      The host divides both by R.  R = 0 adds nothing.  The _ordered twin writes both from per-block slots in a fixed order (ws:
+ *      scan_roi_box_loss_ordered_ws_floats(R) floats).  Backward writes EVERY element: d_cls[r][j] = g2_dev[0] (softmax_j -
+ *      [j == label_r]) (row pitch ldo_cls), d_reg[r][..] = g2_dev[1] smooth-L1' on the label's four columns and exactly zero on
+ *      every other (row pitch ldo_reg, a multiple of 4; 16-byte aligned).
+ *      scan_roi_box_decode: one launch over R test-time rows; rois [R][5] as above, image_hw [N][2] int32 (DEVICE).  scores
+ *      [R][C] = softmax, max-subtracted; boxes [R][C][4] = BoxCoder.decode of the class's four columns (Cr = 2: columns [4, 8) for
+ *      every class) against the ROI: deltas divided by the weights, dw / dh clamped at log(1000 / 16), +1 widths, x2 = ctr +
+ *      0.5 w - 1, clipped to [0, width - 1] x [0, height - 1] of the ROI's image; cand [R][C] uint8 = j >= 1 and score >
+ *      score_thresh.  Every byte is written; a ROI whose image index is outside 0 .. N - 1 gives zeros and cand 0. ---- */
+int scan_roi_box_match(const float* props, const int32_t* np, int32_t N, int32_t P, const float* boxes, const int64_t* glabels,
+                       const int32_t* ng, int32_t G, float bg_thr, float fg_thr, int32_t* labels_i32, int32_t* matched,
+                       void* stream);
+int scan_roi_box_gather(const float* props, int32_t N, int32_t P, const float* boxes, int32_t G, const int32_t* labels_i32,
+                        const int32_t* matched, const uint8_t* sampled, const int32_t* counts, float wx, float wy, float ww,
+                        float wh, int32_t R, float* rois, int32_t* labels_out, float* reg_targets, int32_t* src, void* stream);
+int scan_roi_box_loss_forward(const float* class_logits, int64_t ld_cls, const float* box_regression, int64_t ld_reg, int32_t R,
+                              int32_t C, int32_t Cr, const int32_t* labels, const float* reg_targets, float* out2, void* stream);
+int64_t scan_roi_box_loss_ordered_ws_floats(int64_t R);
+int scan_roi_box_loss_forward_ordered(const float* class_logits, int64_t ld_cls, const float* box_regression, int64_t ld_reg,
+                                      int32_t R, int32_t C, int32_t Cr, const int32_t* labels, const float* reg_targets,
+                                      float* out2, float* ws, void* stream);
+int scan_roi_box_loss_backward(const float* class_logits, int64_t ld_cls, const float* box_regression, int64_t ld_reg, int32_t R,
+                               int32_t C, int32_t Cr, const int32_t* labels, const float* reg_targets, const float* g2_dev,
+                               float* d_cls, int64_t ldo_cls, float* d_reg, int64_t ldo_reg, void* stream);
+int scan_roi_box_decode(const float* class_logits, int64_t ld_cls, const float* box_regression, int64_t ld_reg, int32_t R, int32_t C,
+                        int32_t Cr, const float* rois, const int32_t* image_hw, int32_t N, float wx, float wy, float ww, float wh,
+                        float score_thresh, float* scores, float* boxes, uint8_t* cand, void* stream);
+
 /* ---- FPN top-down join on NHWC rows (reference backbone/fpn.py:62-75: inner = lateral + F.interpolate(top,
  *      scale_factor=2, mode="nearest")).  lat / y [N, 2h, 2w, C], coarse [N, h, w, C], C % 4 == 0.  Backward:
  *      d_lateral is the incoming gradient itself, d_coarse its 2x2 window sums (scan_downsample2x_sum: g [N, 2h, 2w, C]

@@ -105,6 +105,20 @@ RPN_DEFAULTS = {
 }
 
 
+# The Fast R-CNN box head (a MODEL.ROI_BOX_HEAD block in the cfg, modeling/roi_box_head.py) with the reference's defaults
+# (defaults.py:179-225; MODEL.CLS_AGNOSTIC_BBOX_REG at :33).  Kept OUT of DEFAULTS for the same reason as ATSS_DEFAULTS;
+# roi_box_settings(cfg) reads a cfg's MODEL.ROI_HEADS / MODEL.ROI_BOX_HEAD blocks over these.
+ROI_HEADS_DEFAULTS = {
+    "USE_FPN": False, "FG_IOU_THRESHOLD": 0.5, "BG_IOU_THRESHOLD": 0.5, "BBOX_REG_WEIGHTS": (10., 10., 5., 5.),
+    "BATCH_SIZE_PER_IMAGE": 512, "POSITIVE_FRACTION": 0.25, "SCORE_THRESH": 0.05, "NMS": 0.5, "DETECTIONS_PER_IMG": 100,
+}
+ROI_BOX_HEAD_DEFAULTS = {
+    "FEATURE_EXTRACTOR": "ResNet50Conv5ROIFeatureExtractor", "PREDICTOR": "FastRCNNPredictor", "POOLER_RESOLUTION": 14,
+    "POOLER_SAMPLING_RATIO": 0, "POOLER_SCALES": (1.0 / 16,), "NUM_CLASSES": 81, "MLP_HEAD_DIM": 1024, "USE_GN": False,
+    "DILATION": 1, "CONV_HEAD_DIM": 256, "NUM_STACKED_CONVS": 4,
+}
+
+
 # Region poolers (modeling/poolers.make_pooler) with the reference's defaults for MODEL.<head_name> (defaults.py:214-216 for
 # ROI_BOX_HEAD; ROI_MASK_HEAD :231-233 and ROI_KEYPOINT_HEAD :249-251 carry the same three values).  Kept OUT of DEFAULTS for
 # the same reason as ATSS_DEFAULTS; pooler_settings(cfg, head_name) reads a cfg's MODEL[head_name] block over these.
@@ -417,6 +431,54 @@ def rpn_settings(cfg):
         post_nms_top_n_train=int(R.POST_NMS_TOP_N_TRAIN), post_nms_top_n_test=int(R.POST_NMS_TOP_N_TEST),
         nms_thresh=float(R.NMS_THRESH), min_size=float(R.MIN_SIZE), fpn_post_nms_top_n_train=int(R.FPN_POST_NMS_TOP_N_TRAIN),
         fpn_post_nms_top_n_test=int(R.FPN_POST_NMS_TOP_N_TEST), rpn_only=bool(cfg.MODEL.get("RPN_ONLY", False)))
+
+
+def roi_box_settings(cfg):
+    """Flat view of MODEL.ROI_HEADS / MODEL.ROI_BOX_HEAD (and MODEL.CLS_AGNOSTIC_BBOX_REG) for modeling.roi_box_head.ROIBoxHead;
+    raises, naming the key, on every value that is not built.  What is built is the Faster R-CNN FPN head: FPN2MLPFeatureExtractor
+    and FPNPredictor on the pyramid, so the reference's defaults for FEATURE_EXTRACTOR, PREDICTOR and ROI_HEADS.USE_FPN must be
+    overridden explicitly (as MODEL.RETINANET.USE_C5 must be)."""
+    M = cfg.MODEL
+    H = Cfg(ROI_HEADS_DEFAULTS)
+    H._merge(M.get("ROI_HEADS", {}))
+    B = Cfg(ROI_BOX_HEAD_DEFAULTS)
+    B._merge(M.get("ROI_BOX_HEAD", {}))
+    if M.get("MASK_ON", False):
+        raise ValueError("MODEL.MASK_ON True is not built: there is no mask head")
+    if M.get("KEYPOINT_ON", False):
+        raise ValueError("MODEL.KEYPOINT_ON True is not built: there is no keypoint head")
+    if str(B.FEATURE_EXTRACTOR) != "FPN2MLPFeatureExtractor":
+        raise ValueError("MODEL.ROI_BOX_HEAD.FEATURE_EXTRACTOR %r is not built (only 'FPN2MLPFeatureExtractor'; set it explicitly)"
+                         % (B.FEATURE_EXTRACTOR,))
+    if str(B.PREDICTOR) != "FPNPredictor":
+        raise ValueError("MODEL.ROI_BOX_HEAD.PREDICTOR %r is not built (only 'FPNPredictor'; set it explicitly)" % (B.PREDICTOR,))
+    if bool(B.USE_GN):
+        raise ValueError("MODEL.ROI_BOX_HEAD.USE_GN True is not built")
+    if not bool(H.USE_FPN):
+        raise ValueError("MODEL.ROI_HEADS.USE_FPN False is not built: the box head runs on the P3..P7 pyramid (set it to True)")
+    pyramid = (1 / 8, 1 / 16, 1 / 32, 1 / 64, 1 / 128)
+    scales = tuple(float(s) for s in B.POOLER_SCALES)
+    if not 1 <= len(scales) <= 5 or scales != pyramid[:len(scales)]:
+        raise ValueError("MODEL.ROI_BOX_HEAD.POOLER_SCALES %r: a prefix of the pyramid's (1/8, 1/16, 1/32, 1/64, 1/128)" % (B.POOLER_SCALES,))
+    if float(H.BG_IOU_THRESHOLD) > float(H.FG_IOU_THRESHOLD):
+        raise ValueError("MODEL.ROI_HEADS.BG_IOU_THRESHOLD %r above FG_IOU_THRESHOLD %r" % (H.BG_IOU_THRESHOLD, H.FG_IOU_THRESHOLD))
+    if int(H.BATCH_SIZE_PER_IMAGE) < 1:
+        raise ValueError("MODEL.ROI_HEADS.BATCH_SIZE_PER_IMAGE %r: at least 1" % (H.BATCH_SIZE_PER_IMAGE,))
+    if not 0 < float(H.POSITIVE_FRACTION) <= 1:
+        raise ValueError("MODEL.ROI_HEADS.POSITIVE_FRACTION %r outside (0, 1]" % (H.POSITIVE_FRACTION,))
+    if len(H.BBOX_REG_WEIGHTS) != 4 or any(float(w) <= 0 for w in H.BBOX_REG_WEIGHTS):
+        raise ValueError("MODEL.ROI_HEADS.BBOX_REG_WEIGHTS %r: four positive weights" % (H.BBOX_REG_WEIGHTS,))
+    if int(B.NUM_CLASSES) < 2:
+        raise ValueError("MODEL.ROI_BOX_HEAD.NUM_CLASSES %r (background included): at least 2" % (B.NUM_CLASSES,))
+    if int(B.POOLER_RESOLUTION) < 1 or int(B.MLP_HEAD_DIM) < 1:
+        raise ValueError("MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION %r / MLP_HEAD_DIM %r: at least 1" % (B.POOLER_RESOLUTION, B.MLP_HEAD_DIM))
+    return dict(
+        fg_iou_threshold=float(H.FG_IOU_THRESHOLD), bg_iou_threshold=float(H.BG_IOU_THRESHOLD),
+        bbox_reg_weights=tuple(float(w) for w in H.BBOX_REG_WEIGHTS), batch_size_per_image=int(H.BATCH_SIZE_PER_IMAGE),
+        positive_fraction=float(H.POSITIVE_FRACTION), score_thresh=float(H.SCORE_THRESH), nms=float(H.NMS),
+        detections_per_img=int(H.DETECTIONS_PER_IMG), pooler_resolution=int(B.POOLER_RESOLUTION),
+        pooler_sampling_ratio=int(B.POOLER_SAMPLING_RATIO), pooler_scales=scales, num_classes=int(B.NUM_CLASSES),
+        mlp_head_dim=int(B.MLP_HEAD_DIM), cls_agnostic_bbox_reg=bool(M.get("CLS_AGNOSTIC_BBOX_REG", False)))
 
 
 def epm_settings(cfg):

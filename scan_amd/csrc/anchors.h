@@ -30,6 +30,16 @@ __device__ __forceinline__ float4 box_encode(const float4 b, const float4 a, dou
                      (float)(wwh * log(gh / eh)));
 }
 
+// the same with one weight per component (wx, wy, ww, wh): the box head's BBOX_REG_WEIGHTS (roi_box.hip)
+__device__ __forceinline__ float4 box_encode4(const float4 b, const float4 a, double wx, double wy, double ww, double wh) {
+  const double ew = (double)a.z - (double)a.x + 1.0, eh = (double)a.w - (double)a.y + 1.0;
+  const double ecx = (double)a.x + 0.5 * ew, ecy = (double)a.y + 0.5 * eh;
+  const double gw = (double)b.z - (double)b.x + 1.0, gh = (double)b.w - (double)b.y + 1.0;
+  const double gcx = (double)b.x + 0.5 * gw, gcy = (double)b.y + 0.5 * gh;
+  return make_float4((float)(wx * (gcx - ecx) / ew), (float)(wy * (gcy - ecy) / eh), (float)(ww * log(gw / ew)),
+                     (float)(wh * log(gh / eh)));
+}
+
 __device__ __forceinline__ float smooth_l1_elem(float x, float t, float beta) {
   const float n = fabsf(x - t);
   return n < beta ? 0.5f * n * n / beta : n - 0.5f * beta;

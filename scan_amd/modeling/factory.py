@@ -30,6 +30,7 @@ from .discriminator import FCOSDiscriminator_con
 from .fcos import FCOSModule
 from .resnet import ResNetFPNBackbone
 from .retinanet import RetinaNetModule
+from .roi_box_head import CombinedROIHeads, ROIBoxHead
 from .rpn import RPNModule
 
 LEVELS = ("P3", "P4", "P5", "P6", "P7")
@@ -229,6 +230,61 @@ def build_rpn(cfg, in_channels):
         return _channels_last_(FCOSModuleNCHW(h["num_classes"], h["test_mode"], h))
     s = config.settings(cfg)
     return _channels_last_(FCOSModuleNCHW(s["num_classes"], s["test_mode"], s))
+
+
+def build_roi_heads(cfg, in_channels):
+    """reference modeling/roi_heads/roi_heads.py:58-76: [] under MODEL.RETINANET_ON or MODEL.RPN_ONLY, else the combined heads
+    whose ``box`` entry is the Fast R-CNN box head (state_dict keys roi_heads.box. ...) -- built only when the cfg itself carries
+    a MODEL.ROI_BOX_HEAD block (the shipped yamls carry none, and config.ROI_BOX_HEAD_DEFAULTS stays out of config.DEFAULTS).
+    Mask and keypoint heads are not built: config.roi_box_settings refuses MODEL.MASK_ON / MODEL.KEYPOINT_ON."""
+    if cfg.MODEL.get("RETINANET_ON", False) or cfg.MODEL.get("RPN_ONLY", False):
+        return []
+    if not isinstance(cfg.MODEL.get("ROI_BOX_HEAD"), dict):
+        raise ValueError("the cfg has no MODEL.ROI_BOX_HEAD block: a MODEL.ROI_BOX_HEAD block selects the box head")
+    if in_channels != 256:
+        raise ValueError("the box head is built for 256 input channels, got %d" % in_channels)
+    return CombinedROIHeads({"box": ROIBoxHead(config.roi_box_settings(cfg), in_channels)})
+
+
+class GeneralizedRCNN(torch.nn.Module):
+    """reference modeling/detector/generalized_rcnn.py:16-70: backbone, rpn, roi_heads.  The middle head (the conditional graph
+    module) belongs to the FCOS path and is refused here by name."""
+
+    def __init__(self, cfg):
+        super().__init__()
+        if cfg.MODEL.get("MIDDLE_HEAD", {}).get("CONDGRAPH_ON", False) and isinstance(cfg.MODEL.get("RPN"), dict) \
+                and not (cfg.MODEL.get("FCOS_ON", False) or cfg.MODEL.get("ATSS_ON", False) or cfg.MODEL.get("RETINANET_ON", False)):
+            raise ValueError("MODEL.MIDDLE_HEAD.CONDGRAPH_ON True with the region-proposal network is not built (set it to False)")
+        self.backbone = build_backbone(cfg)
+        self.rpn = build_rpn(cfg, self.backbone.out_channels)
+        roi_heads = build_roi_heads(cfg, self.backbone.out_channels)
+        self.roi_heads = roi_heads if roi_heads else None
+
+    def forward(self, images, targets=None):
+        """images [N, 3, H, W] (or an ImageList), targets list[BoxList] -> the loss dict in training, list[BoxList] detections
+        (the RPN's proposals without roi_heads) in eval"""
+        if self.training and targets is None:
+            raise ValueError("In training mode, targets should be passed")
+        images = to_image_list(images)
+        features = self.backbone(images.tensors)
+        proposals, proposal_losses = self.rpn(images, features, targets)[:2]
+        if self.roi_heads is not None:
+            _, result, detector_losses = self.roi_heads(features, proposals, target_tuples(targets))
+        else:
+            result, detector_losses = proposals, {}
+        if self.training:
+            losses = dict(detector_losses)
+            losses.update(proposal_losses)
+            return losses
+        return result
+
+
+def build_detection_model(cfg):
+    """reference modeling/detector/detectors.py: META_ARCHITECTURE GeneralizedRCNN"""
+    arch = str(cfg.MODEL.get("META_ARCHITECTURE", "GeneralizedRCNN"))
+    if arch != "GeneralizedRCNN":
+        raise ValueError("MODEL.META_ARCHITECTURE %r is not built (only 'GeneralizedRCNN')" % arch)
+    return _channels_last_(GeneralizedRCNN(cfg))
 
 
 class FCOSDiscriminatorNCHW(FCOSDiscriminator_con):

@@ -1912,6 +1912,162 @@ def rpn_decode_proposals(bbox_reg, shape, strides, cells, topk_idx, ks, image_hw
     return boxes, keep
 
 
+# ----------------------------------------------------------------------------- Fast R-CNN box head (csrc/roi_box.hip)
+# Proposals of a batch are padded as the ground truth is: props [N, P, 4] fp32 xyxy, n_props [N] int32, on the device.
+def _roi_box_props(who, props, n_props=None):
+    if props.dim() != 3 or props.shape[2] != 4 or props.shape[0] < 1 or props.shape[1] < 1 or props.dtype != torch.float32:
+        raise ValueError("%s: proposals must be fp32 [N >= 1, P >= 1, 4], got %r %s" % (who, tuple(props.shape), props.dtype))
+    if props.shape[0] * props.shape[1] >= 2 ** 31:
+        raise ValueError("%s: 2^31 proposals or more" % who)
+    if n_props is not None and (n_props.dtype != torch.int32 or n_props.numel() != props.shape[0]):
+        raise ValueError("%s: proposal counts must be int32 [N]" % who)
+    return int(props.shape[0]), int(props.shape[1])
+
+
+def _roi_box_weights(who, weights):
+    weights = tuple(float(w) for w in weights)
+    if len(weights) != 4 or not all(w > 0 for w in weights):
+        raise ValueError("%s: box coder weights %r: four positive numbers (wx, wy, ww, wh)" % (who, weights))
+    return weights
+
+
+def _roi_box_plan_vector(who, t, dtype, n, name):
+    if t.dtype != dtype or t.numel() != n or not t.is_contiguous():
+        raise ValueError("%s: %s must be contiguous %s with N * P = %d elements, got %r %s" % (who, name, dtype, n, tuple(t.shape), t.dtype))
+
+
+def roi_box_match(props, n_props, boxes, glab, ng, bg_thr, fg_thr):
+    """The Matcher without the low-quality rule (reference roi_heads/box_head/loss.py:39-70) of padded proposals against the
+    padded ground truth (boxes [N, G, 4], glab [N, G] int64, ng [N] int32), one launch -> labels_i32 [N * P] (0 below bg_thr,
+    -1 between the thresholds and on padding rows, else the matched box's label), matched int32 [N * P] (0 where label <= 0)."""
+    N, P = _roi_box_props("roi_box_match", props, n_props)
+    G = _ground_truth("roi_box_match", PyramidShape(N, [(P, 1)]), boxes, glab, ng)
+    if not float(bg_thr) <= float(fg_thr):
+        raise ValueError("roi_box_match: bg_thr %r above fg_thr %r" % (bg_thr, fg_thr))
+    _chk(props, n_props, boxes, glab, ng)
+    labels = torch.empty((N * P,), dtype=torch.int32, device=props.device)
+    matched = torch.empty((N * P,), dtype=torch.int32, device=props.device)
+    call("scan_roi_box_match", _ptr(props), _ptr(n_props), N, P, _ptr(boxes), _ptr(glab), _ptr(ng), G, float(bg_thr), float(fg_thr),
+         _ptr(labels), _ptr(matched), _stream())
+    return labels, matched
+
+
+def roi_box_gather(props, boxes, labels_i32, matched, sampled, counts, R, weights=(10., 10., 5., 5.)):
+    """The sampled proposals of every image in one launch (reference loss.py:108-113: proposals[img][nonzero(pos | neg)]), image
+    by image and by ascending proposal index: sampled uint8 [N * P] and counts int32 [N, 2] of ops.rpn_sample on
+    PyramidShape(N, [(P, 1)]) with A = 1, R their total (read on the host by the caller) -> rois [R, 5] (image index, box),
+    labels int32 [R] (0 for a sampled negative), reg_targets [R, 4] (BoxCoder.encode with ``weights`` of the matched box where
+    label > 0, zero elsewhere), src int32 [R] (the proposal's index within its image)."""
+    N, P = _roi_box_props("roi_box_gather", props)
+    if boxes.dim() != 3 or boxes.shape[0] != N or boxes.shape[2] != 4 or boxes.shape[1] < 1 or boxes.dtype != torch.float32:
+        raise ValueError("roi_box_gather: boxes must be fp32 [N, G >= 1, 4], got %r" % (tuple(boxes.shape),))
+    _roi_box_plan_vector("roi_box_gather", labels_i32, torch.int32, N * P, "labels_i32")
+    _roi_box_plan_vector("roi_box_gather", matched, torch.int32, N * P, "matched")
+    _roi_box_plan_vector("roi_box_gather", sampled, torch.uint8, N * P, "sampled")
+    if counts.dtype != torch.int32 or tuple(counts.shape) != (N, 2) or not counts.is_contiguous():
+        raise ValueError("roi_box_gather: counts must be contiguous int32 [N, 2], got %r %s" % (tuple(counts.shape), counts.dtype))
+    if not 0 <= int(R) <= N * P:
+        raise ValueError("roi_box_gather: R %r outside 0..N * P = %d" % (R, N * P))
+    wx, wy, ww, wh = _roi_box_weights("roi_box_gather", weights)
+    _chk(props, boxes, labels_i32, matched, sampled, counts)
+    dev, R = props.device, int(R)
+    rois = torch.empty((R, 5), dtype=torch.float32, device=dev)
+    labels = torch.empty((R,), dtype=torch.int32, device=dev)
+    reg_targets = torch.empty((R, 4), dtype=torch.float32, device=dev)
+    src = torch.empty((R,), dtype=torch.int32, device=dev)
+    call("scan_roi_box_gather", _ptr(props), N, P, _ptr(boxes), int(boxes.shape[1]), _ptr(labels_i32), _ptr(matched), _ptr(sampled),
+         _ptr(counts), wx, wy, ww, wh, R, _ptr(rois), _ptr(labels), _ptr(reg_targets), _ptr(src), _stream())
+    return rois, labels, reg_targets, src
+
+
+def _roi_box_head_outputs(who, class_logits, box_regression):
+    """(R, C, Cr) of the predictor's outputs: class_logits [R, C >= 2], box_regression [R, 4 C] or [R, 8] (class-agnostic)"""
+    if class_logits.dim() != 2 or class_logits.shape[1] < 2 or class_logits.dtype != torch.float32:
+        raise ValueError("%s: class_logits must be fp32 [R, C >= 2], got %r %s" % (who, tuple(class_logits.shape), class_logits.dtype))
+    R, C = int(class_logits.shape[0]), int(class_logits.shape[1])
+    if box_regression.dim() != 2 or box_regression.shape[0] != R or box_regression.shape[1] not in (4 * C, 8) \
+            or box_regression.dtype != torch.float32:
+        raise ValueError("%s: box_regression %r %s for class_logits %r: fp32 [R, 4 C] or [R, 8] (class-agnostic)"
+                         % (who, tuple(box_regression.shape), box_regression.dtype, tuple(class_logits.shape)))
+    if R > 2 ** 30:
+        raise ValueError("%s: more than 2^30 rows" % who)
+    for t, name in ((class_logits, "class_logits"), (box_regression, "box_regression")):
+        if R > 0 and (t.stride(1) != 1 or t.stride(0) < t.shape[1]):
+            raise ValueError("%s: %s must have contiguous rows" % (who, name))
+    if R > 0 and (box_regression.stride(0) % 4 != 0 or box_regression.data_ptr() % 16 != 0):
+        raise ValueError("%s: box_regression must start 16-byte aligned with a row pitch that is a multiple of 4" % who)
+    return R, C, int(box_regression.shape[1]) // 4
+
+
+def _pitch(t):
+    """the row pitch of a head output (a column slice of a wider matrix is taken as it is); GPU tensors only"""
+    if not t.is_cuda:
+        raise RuntimeError("scan_amd ops run only on the GPU (HIP) -- got a %s tensor; no CPU fallback" % t.device)
+    return int(t.stride(0)) if t.shape[0] > 0 else int(t.shape[1])
+
+
+class _RoiBoxLoss(torch.autograd.Function):
+    """(sum of the cross-entropy over the R sampled rows, sum of the class-specific smooth-L1 over the positives) as a [2] tensor
+    (reference roi_heads/box_head/loss.py:146-164 before the divisions by R; csrc/roi_box.hip).  Both head outputs are read in
+    place through their row pitches."""
+
+    @staticmethod
+    def forward(ctx, class_logits, box_regression, dims, labels, reg_targets):
+        R, C, Cr = dims
+        _chk(labels, reg_targets)
+        out = class_logits.new_zeros((2,))
+        args = (_ptr(class_logits), _pitch(class_logits), _ptr(box_regression), _pitch(box_regression), R, C, Cr, _ptr(labels),
+                _ptr(reg_targets))
+        _call_reduction("scan_roi_box_loss", "_forward", class_logits, (R,), *args, _ptr(out))
+        ctx.save_for_backward(class_logits, box_regression, labels, reg_targets)
+        ctx.args = args
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        class_logits, box_regression = ctx.saved_tensors[:2]
+        d_cls = torch.empty(class_logits.shape, dtype=torch.float32, device=class_logits.device)
+        d_reg = torch.empty(box_regression.shape, dtype=torch.float32, device=box_regression.device)
+        call("scan_roi_box_loss_backward", *ctx.args, _ptr(g.reshape(2).contiguous()), _ptr(d_cls), d_cls.shape[1], _ptr(d_reg),
+             d_reg.shape[1], _stream())
+        return d_cls, d_reg, None, None, None
+
+
+def roi_box_loss(class_logits, box_regression, labels, reg_targets):
+    """class_logits [R, C] and box_regression [R, 4 C] ([R, 8]: class-agnostic; column slices of a wider row matrix are read in
+    place), labels int32 [R] and reg_targets [R, 4] of ops.roi_box_gather -> [2]: the summed cross-entropy of every row and the
+    summed smooth-L1 (beta 1) of the positives' own four regression columns.  The caller divides both by R."""
+    R, C, Cr = _roi_box_head_outputs("roi_box_loss", class_logits, box_regression)
+    if labels.dtype != torch.int32 or tuple(labels.shape) != (R,) or not labels.is_contiguous():
+        raise ValueError("roi_box_loss: labels must be contiguous int32 [R] = [%d], got %r %s" % (R, tuple(labels.shape), labels.dtype))
+    if reg_targets.dtype != torch.float32 or tuple(reg_targets.shape) != (R, 4) or not reg_targets.is_contiguous():
+        raise ValueError("roi_box_loss: reg_targets must be contiguous fp32 [R, 4], got %r %s" % (tuple(reg_targets.shape), reg_targets.dtype))
+    return _RoiBoxLoss.apply(class_logits, box_regression, (R, C, Cr), labels, reg_targets)
+
+
+def roi_box_decode(class_logits, box_regression, rois, image_hw, weights=(10., 10., 5., 5.), score_thresh=0.05):
+    """The test-time softmax, BoxCoder.decode, clip and score threshold of every (ROI, class) in one launch (reference
+    roi_heads/box_head/inference.py:55-84, 118): rois [R, 5] (image index, box), image_hw int32 [N, 2] on the device -> scores
+    [R, C], boxes [R, C, 4] clipped to the ROI's image, cand uint8 [R, C] (class >= 1 and score > score_thresh)."""
+    R, C, Cr = _roi_box_head_outputs("roi_box_decode", class_logits, box_regression)
+    if rois.dtype != torch.float32 or tuple(rois.shape) != (R, 5) or not rois.is_contiguous():
+        raise ValueError("roi_box_decode: rois must be contiguous fp32 [R, 5] = [%d, 5], got %r %s" % (R, tuple(rois.shape), rois.dtype))
+    if image_hw.dtype != torch.int32 or image_hw.dim() != 2 or image_hw.shape[0] < 1 or image_hw.shape[1] != 2 \
+            or not image_hw.is_contiguous():
+        raise ValueError("roi_box_decode: image_hw must be contiguous int32 [N >= 1, 2] (height, width), got %r %s"
+                         % (tuple(image_hw.shape), image_hw.dtype))
+    wx, wy, ww, wh = _roi_box_weights("roi_box_decode", weights)
+    _chk(rois, image_hw)
+    dev = class_logits.device
+    scores = torch.empty((R, C), dtype=torch.float32, device=dev)
+    boxes = torch.empty((R, C, 4), dtype=torch.float32, device=dev)
+    cand = torch.empty((R, C), dtype=torch.uint8, device=dev)
+    call("scan_roi_box_decode", _ptr(class_logits), _pitch(class_logits), _ptr(box_regression), _pitch(box_regression), R, C, Cr,
+         _ptr(rois), _ptr(image_hw), int(image_hw.shape[0]), wx, wy, ww, wh, float(score_thresh), _ptr(scores), _ptr(boxes),
+         _ptr(cand), _stream())
+    return scores, boxes, cand
+
+
 class _BceLogitsMean(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, targets):
