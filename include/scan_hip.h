@@ -815,6 +815,52 @@ int scan_roi_box_decode(const float* class_logits, int64_t ld_cls, const float* 
                         int32_t Cr, const float* rois, const int32_t* image_hw, int32_t N, float wx, float wy, float ww, float wh,
                         float score_thresh, float* scores, float* boxes, uint8_t* cand, void* stream);
 
+/* ---- the Mask R-CNN mask head (csrc/roi_mask.hip; reference modeling/roi_heads/mask_head/{mask_head.py, loss.py, inference.py},
+ *      structures/segmentation_mask.py in binary-mask mode).  No float atomics; every output element is written by its kernel, so
+ *      no buffer is cleared first.  Ground-truth masks: ONE flat uint8 buffer of mask_bytes bytes; image n owns bytes [moff[n],
+ *      moff[n + 1]) as [G_n][h_n][w_n], mhw [N][2] int32 = (h_n, w_n), moff int64 [N + 1], no padding to a common size, values 0 / 1.
+ *      scan_roi_mask_positives: one launch of ONE workgroup (a running block scan over R in chunks of 256, no cap on R); replaces
+ *      keep_only_positive_boxes and the mask loss's re-match.  labels [R] int32, rois [R][5] and src [R] of scan_roi_box_gather,
+ *      matched [N * P] of scan_roi_box_match.  For the rows with label > 0, in row order: pos_rows [Rp] (the row), pos_rois [Rp][5],
+ *      pos_labels [Rp], pos_gt [Rp] = matched[image P + src] (0 where the image index or src is out of range).  Rp comes from the
+ *      caller (the box plan's positive counts); nothing is written at or beyond row Rp; Rp = 0 launches nothing.
+ *      scan_roi_mask_targets: one launch over Rp M M outputs, targets [Rp][M][M] fp32 0 / 1 = BinaryMaskList.crop + .resize((M, M))
+ *      + get_mask_tensor of mask pos_gt[r] (clamped into 0 .. G_n - 1) of image pos_rois[r][0].  Crop: every coordinate rounded
+ *      half-to-even, xmin / ymin clamped to [0, w - 1] / [0, h - 1], xmax / ymax to [0, w] / [0, h], then xmax = max(xmax, xmin + 1),
+ *      likewise y.  Resize, decided in integers: along an axis of crop length n, output index d has num = max((2 d + 1) n - M, 0),
+ *      first neighbour i0 = num / (2 M), second min(i0 + 1, n - 1), which takes part iff num % (2 M) != 0; the target is 1 iff every
+ *      participating neighbour (up to 2 x 2) is nonzero -- the exact value of the reference's bilinear (align_corners False) sum
+ *      truncated to uint8.  (The reference evaluates that sum in fp32 and can round an exact 1 down to 0; the device never does.)
+ *      A ROI whose image index is outside 0 .. N - 1, or whose image has no mask, gives zeros.
+ *      scan_roi_mask_loss_*: logits are the conv output rows [Rp M M][ld] read in place, column labels[r] of ROI r's M M rows;
+ *      out1[0] = sum of max(x, 0) - x t + log1p(exp(-|x|)) (STORED, not added; the host divides by Rp M M).  A row whose label is
+ *      outside 0 .. C - 1 takes no part.  forward: one launch of one workgroup (one CU's load rate: for small Rp); the _ordered twin: per-block slots (ws:
+ *      scan_roi_mask_loss_ordered_ws_floats(Rp M M) floats) added in a fixed order by a second launch.  Rp = 0 stores 0.
+ *      backward writes EVERY element of d_logits [Rp M M][ldo]: g_dev[0] (sigmoid(x) - t) in the label's column, exact zeros
+ *      elsewhere (g_dev[0]: the incoming gradient already divided by Rp M M).
+ *      scan_roi_mask_prob: one launch, prob [K][1][M][M] = sigmoid(logits[r M M + e][labels[r]]) (MaskPostProcessor.forward).
+ *      scan_roi_mask_paste: one launch per image over K H W uint8 outputs (4-byte aligned), every one written
+ *      (Masker.forward_single_image with padding 1; a thread owns four consecutive pixels of a row): boxes [K][4] xyxy expanded about their centres by (M + 2) / M in fp32, truncated toward zero to int32,
+ *      w = max(x1 - x0 + 1, 1), likewise h; inside the box the bilinear sample (align_corners False, torch's source index with the
+ *      clamp at 0, fp32) of the mask zero-padded by 1 at size (h, w), compared > thresh; 0 outside the box.  thresh < 0 is
+ *      refused. ---- */
+int scan_roi_mask_positives(const int32_t* labels, const float* rois, const int32_t* src, const int32_t* matched, int32_t N, int32_t P,
+                            int32_t R, int32_t Rp, int32_t* pos_rows, float* pos_rois, int32_t* pos_labels, int32_t* pos_gt,
+                            void* stream);
+int scan_roi_mask_targets(const float* pos_rois, const int32_t* pos_gt, int32_t Rp, const uint8_t* masks, int64_t mask_bytes,
+                          const int64_t* moff, const int32_t* mhw, int32_t N, int32_t M, float* targets, void* stream);
+int scan_roi_mask_loss_forward(const float* logits, int64_t ld, int32_t Rp, int32_t M, int32_t C, const int32_t* labels,
+                               const float* targets, float* out1, void* stream);
+int64_t scan_roi_mask_loss_ordered_ws_floats(int64_t elems);
+int scan_roi_mask_loss_forward_ordered(const float* logits, int64_t ld, int32_t Rp, int32_t M, int32_t C, const int32_t* labels,
+                                       const float* targets, float* out1, float* ws, void* stream);
+int scan_roi_mask_loss_backward(const float* logits, int64_t ld, int32_t Rp, int32_t M, int32_t C, const int32_t* labels,
+                                const float* targets, const float* g_dev, float* d_logits, int64_t ldo, void* stream);
+int scan_roi_mask_prob(const float* logits, int64_t ld, int32_t K, int32_t M, int32_t C, const int32_t* labels, float* prob,
+                       void* stream);
+int scan_roi_mask_paste(const float* prob, const float* boxes, int32_t K, int32_t M, int32_t H, int32_t W, float thresh, uint8_t* out,
+                        void* stream);
+
 /* ---- FPN top-down join on NHWC rows (reference backbone/fpn.py:62-75: inner = lateral + F.interpolate(top,
  *      scale_factor=2, mode="nearest")).  lat / y [N, 2h, 2w, C], coarse [N, h, w, C], C % 4 == 0.  Backward:
  *      d_lateral is the incoming gradient itself, d_coarse its 2x2 window sums (scan_downsample2x_sum: g [N, 2h, 2w, C]

@@ -119,6 +119,17 @@ ROI_BOX_HEAD_DEFAULTS = {
 }
 
 
+# The Mask R-CNN mask head (MODEL.MASK_ON with a MODEL.ROI_MASK_HEAD block in the cfg, modeling/roi_mask_head.py) with the
+# reference's defaults (defaults.py:228-244).  Kept OUT of DEFAULTS for the same reason as ATSS_DEFAULTS; roi_mask_settings(cfg)
+# reads a cfg's MODEL.ROI_MASK_HEAD block over these.
+ROI_MASK_HEAD_DEFAULTS = {
+    "FEATURE_EXTRACTOR": "ResNet50Conv5ROIFeatureExtractor", "PREDICTOR": "MaskRCNNC4Predictor", "POOLER_RESOLUTION": 14,
+    "POOLER_SAMPLING_RATIO": 0, "POOLER_SCALES": (1.0 / 16,), "MLP_HEAD_DIM": 1024, "CONV_LAYERS": (256, 256, 256, 256),
+    "RESOLUTION": 14, "SHARE_BOX_FEATURE_EXTRACTOR": True, "POSTPROCESS_MASKS": False, "POSTPROCESS_MASKS_THRESHOLD": 0.5,
+    "DILATION": 1, "USE_GN": False,
+}
+
+
 # Region poolers (modeling/poolers.make_pooler) with the reference's defaults for MODEL.<head_name> (defaults.py:214-216 for
 # ROI_BOX_HEAD; ROI_MASK_HEAD :231-233 and ROI_KEYPOINT_HEAD :249-251 carry the same three values).  Kept OUT of DEFAULTS for
 # the same reason as ATSS_DEFAULTS; pooler_settings(cfg, head_name) reads a cfg's MODEL[head_name] block over these.
@@ -443,8 +454,8 @@ def roi_box_settings(cfg):
     H._merge(M.get("ROI_HEADS", {}))
     B = Cfg(ROI_BOX_HEAD_DEFAULTS)
     B._merge(M.get("ROI_BOX_HEAD", {}))
-    if M.get("MASK_ON", False):
-        raise ValueError("MODEL.MASK_ON True is not built: there is no mask head")
+    if M.get("MASK_ON", False) and not isinstance(M.get("ROI_MASK_HEAD"), dict):
+        raise ValueError("MODEL.MASK_ON True needs a MODEL.ROI_MASK_HEAD block (roi_mask_settings reads it)")
     if M.get("KEYPOINT_ON", False):
         raise ValueError("MODEL.KEYPOINT_ON True is not built: there is no keypoint head")
     if str(B.FEATURE_EXTRACTOR) != "FPN2MLPFeatureExtractor":
@@ -479,6 +490,63 @@ def roi_box_settings(cfg):
         detections_per_img=int(H.DETECTIONS_PER_IMG), pooler_resolution=int(B.POOLER_RESOLUTION),
         pooler_sampling_ratio=int(B.POOLER_SAMPLING_RATIO), pooler_scales=scales, num_classes=int(B.NUM_CLASSES),
         mlp_head_dim=int(B.MLP_HEAD_DIM), cls_agnostic_bbox_reg=bool(M.get("CLS_AGNOSTIC_BBOX_REG", False)))
+
+
+def roi_mask_settings(cfg):
+    """Flat view of MODEL.ROI_MASK_HEAD (with the box head's ROI_HEADS thresholds and ROI_BOX_HEAD.NUM_CLASSES) for
+    modeling.roi_mask_head.ROIMaskHead; raises, naming the key, on every value that is not built.  What is built is the Mask R-CNN
+    FPN head in binary-mask mode: MaskRCNNFPNFeatureExtractor with its own pooler, then MaskRCNNC4Predictor or
+    MaskRCNNConv1x1Predictor -- so the reference's defaults for FEATURE_EXTRACTOR and SHARE_BOX_FEATURE_EXTRACTOR must be
+    overridden explicitly."""
+    M = cfg.MODEL
+    if not isinstance(M.get("ROI_MASK_HEAD"), dict):
+        raise ValueError("the cfg has no MODEL.ROI_MASK_HEAD block: MODEL.MASK_ON True needs a MODEL.ROI_MASK_HEAD block")
+    if M.get("KEYPOINT_ON", False):
+        raise ValueError("MODEL.KEYPOINT_ON True is not built: there is no keypoint head")
+    H = Cfg(ROI_HEADS_DEFAULTS)
+    H._merge(M.get("ROI_HEADS", {}))
+    B = Cfg(ROI_BOX_HEAD_DEFAULTS)
+    B._merge(M.get("ROI_BOX_HEAD", {}))
+    K = Cfg(ROI_MASK_HEAD_DEFAULTS)
+    K._merge(M.ROI_MASK_HEAD)
+    if str(K.FEATURE_EXTRACTOR) != "MaskRCNNFPNFeatureExtractor":
+        raise ValueError("MODEL.ROI_MASK_HEAD.FEATURE_EXTRACTOR %r is not built (only 'MaskRCNNFPNFeatureExtractor'; set it explicitly)"
+                         % (K.FEATURE_EXTRACTOR,))
+    if str(K.PREDICTOR) not in ("MaskRCNNC4Predictor", "MaskRCNNConv1x1Predictor"):
+        raise ValueError("MODEL.ROI_MASK_HEAD.PREDICTOR %r is not built ('MaskRCNNC4Predictor' or 'MaskRCNNConv1x1Predictor')" % (K.PREDICTOR,))
+    if bool(K.SHARE_BOX_FEATURE_EXTRACTOR):
+        raise ValueError("MODEL.ROI_MASK_HEAD.SHARE_BOX_FEATURE_EXTRACTOR True is not built: the mask head pools for itself (set it "
+                         "to False explicitly)")
+    if bool(K.USE_GN):
+        raise ValueError("MODEL.ROI_MASK_HEAD.USE_GN True is not built")
+    if int(K.DILATION) != 1:
+        raise ValueError("MODEL.ROI_MASK_HEAD.DILATION %r is not built (only 1)" % (K.DILATION,))
+    pyramid = (1 / 8, 1 / 16, 1 / 32, 1 / 64, 1 / 128)
+    scales = tuple(float(s) for s in K.POOLER_SCALES)
+    if not 1 <= len(scales) <= 5 or scales != pyramid[:len(scales)]:
+        raise ValueError("MODEL.ROI_MASK_HEAD.POOLER_SCALES %r: a prefix of the pyramid's (1/8, 1/16, 1/32, 1/64, 1/128)" % (K.POOLER_SCALES,))
+    res, pres = int(K.RESOLUTION), int(K.POOLER_RESOLUTION)
+    if pres < 1:
+        raise ValueError("MODEL.ROI_MASK_HEAD.POOLER_RESOLUTION %r: at least 1" % (K.POOLER_RESOLUTION,))
+    want = 2 * pres if str(K.PREDICTOR) == "MaskRCNNC4Predictor" else pres
+    if res != want:
+        raise ValueError("MODEL.ROI_MASK_HEAD.RESOLUTION %r: %s gives masks of %d x %d for POOLER_RESOLUTION %d"
+                         % (K.RESOLUTION, K.PREDICTOR, want, want, pres))
+    layers = tuple(int(c) for c in K.CONV_LAYERS)
+    if not layers or any(c < 1 for c in layers):
+        raise ValueError("MODEL.ROI_MASK_HEAD.CONV_LAYERS %r: at least one layer of at least 1 channel" % (K.CONV_LAYERS,))
+    if not float(K.POSTPROCESS_MASKS_THRESHOLD) >= 0:
+        raise ValueError("MODEL.ROI_MASK_HEAD.POSTPROCESS_MASKS_THRESHOLD %r below 0 (the reference's debugging mode) is not built"
+                         % (K.POSTPROCESS_MASKS_THRESHOLD,))
+    if int(B.NUM_CLASSES) < 2:
+        raise ValueError("MODEL.ROI_BOX_HEAD.NUM_CLASSES %r (background included): at least 2" % (B.NUM_CLASSES,))
+    if float(H.BG_IOU_THRESHOLD) > float(H.FG_IOU_THRESHOLD):
+        raise ValueError("MODEL.ROI_HEADS.BG_IOU_THRESHOLD %r above FG_IOU_THRESHOLD %r" % (H.BG_IOU_THRESHOLD, H.FG_IOU_THRESHOLD))
+    return dict(
+        predictor=str(K.PREDICTOR), pooler_resolution=pres, pooler_sampling_ratio=int(K.POOLER_SAMPLING_RATIO), pooler_scales=scales,
+        conv_layers=layers, resolution=res, postprocess_masks=bool(K.POSTPROCESS_MASKS),
+        postprocess_masks_threshold=float(K.POSTPROCESS_MASKS_THRESHOLD), num_classes=int(B.NUM_CLASSES),
+        fg_iou_threshold=float(H.FG_IOU_THRESHOLD), bg_iou_threshold=float(H.BG_IOU_THRESHOLD))
 
 
 def epm_settings(cfg):

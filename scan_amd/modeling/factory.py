@@ -31,6 +31,7 @@ from .fcos import FCOSModule
 from .resnet import ResNetFPNBackbone
 from .retinanet import RetinaNetModule
 from .roi_box_head import CombinedROIHeads, ROIBoxHead
+from .roi_mask_head import ROIMaskHead
 from .rpn import RPNModule
 
 LEVELS = ("P3", "P4", "P5", "P6", "P7")
@@ -235,15 +236,19 @@ def build_rpn(cfg, in_channels):
 def build_roi_heads(cfg, in_channels):
     """reference modeling/roi_heads/roi_heads.py:58-76: [] under MODEL.RETINANET_ON or MODEL.RPN_ONLY, else the combined heads
     whose ``box`` entry is the Fast R-CNN box head (state_dict keys roi_heads.box. ...) -- built only when the cfg itself carries
-    a MODEL.ROI_BOX_HEAD block (the shipped yamls carry none, and config.ROI_BOX_HEAD_DEFAULTS stays out of config.DEFAULTS).
-    Mask and keypoint heads are not built: config.roi_box_settings refuses MODEL.MASK_ON / MODEL.KEYPOINT_ON."""
+    a MODEL.ROI_BOX_HEAD block (the shipped yamls carry none, and config.ROI_BOX_HEAD_DEFAULTS stays out of config.DEFAULTS) --
+    and, under MODEL.MASK_ON with a MODEL.ROI_MASK_HEAD block, whose ``mask`` entry is the Mask R-CNN mask head in binary-mask
+    mode (config.roi_mask_settings).  The keypoint head is not built: MODEL.KEYPOINT_ON is refused."""
     if cfg.MODEL.get("RETINANET_ON", False) or cfg.MODEL.get("RPN_ONLY", False):
         return []
     if not isinstance(cfg.MODEL.get("ROI_BOX_HEAD"), dict):
         raise ValueError("the cfg has no MODEL.ROI_BOX_HEAD block: a MODEL.ROI_BOX_HEAD block selects the box head")
     if in_channels != 256:
         raise ValueError("the box head is built for 256 input channels, got %d" % in_channels)
-    return CombinedROIHeads({"box": ROIBoxHead(config.roi_box_settings(cfg), in_channels)})
+    heads = [("box", ROIBoxHead(config.roi_box_settings(cfg), in_channels))]
+    if cfg.MODEL.get("MASK_ON", False):
+        heads.append(("mask", ROIMaskHead(config.roi_mask_settings(cfg), in_channels)))
+    return CombinedROIHeads(dict(heads))
 
 
 class GeneralizedRCNN(torch.nn.Module):
@@ -269,7 +274,9 @@ class GeneralizedRCNN(torch.nn.Module):
         features = self.backbone(images.tensors)
         proposals, proposal_losses = self.rpn(images, features, targets)[:2]
         if self.roi_heads is not None:
-            _, result, detector_losses = self.roi_heads(features, proposals, target_tuples(targets))
+            # the mask head reads the masks from the targets' ``masks`` field: the BoxLists go through as they are
+            heads_targets = targets if "mask" in self.roi_heads else target_tuples(targets)
+            _, result, detector_losses = self.roi_heads(features, proposals, heads_targets)
         else:
             result, detector_losses = proposals, {}
         if self.training:

@@ -168,7 +168,8 @@ class FastRCNNLossComputation:
         self.weights = tuple(float(w) for w in weights)
         self.cls_agnostic = bool(cls_agnostic)
         self.seed, self.calls = int(seed), 0
-        self.rois = self.labels = self.reg_targets = self.src = None
+        self.rois = self.labels = self.reg_targets = self.src = self.matched = self.padded = None
+        self.n_positive = 0
 
     next_seed = rpn_mod.RPNLossComputation.next_seed
 
@@ -201,8 +202,11 @@ class FastRCNNLossComputation:
             sampled = sampled.to(device=dev, dtype=torch.uint8).reshape(N, P).contiguous()
             counts = torch.stack(((sampled == 1).sum(1), (sampled == 2).sum(1)), 1).to(torch.int32).contiguous()
             sampled = sampled.reshape(-1)
-        per_image = counts.sum(1).tolist()  # the one host round trip
+        counts_h = counts.tolist()  # the one host round trip
+        per_image = [int(c[0]) + int(c[1]) for c in counts_h]
         R = int(sum(per_image))
+        # what the mask head's plan reads (modeling/roi_mask_head.py): the match of every padded proposal and the sampled positives
+        self.matched, self.padded, self.n_positive = matched, (N, P), sum(int(c[0]) for c in counts_h)
         self.rois, self.labels, self.reg_targets, self.src = ops.roi_box_gather(props, boxes, labels, matched, sampled, counts, R,
                                                                                  self.weights)
         plan_stats.update(launches=launches + 1, host_reads=1)
@@ -315,8 +319,15 @@ class ROIBoxHead(nn.Module):
 
 
 class CombinedROIHeads(nn.ModuleDict):
-    """reference roi_heads.py:9-55 with the box head alone (mask and keypoint heads are not built)."""
+    """reference roi_heads.py:9-55 with the box head and, under MODEL.MASK_ON, the mask head (modeling/roi_mask_head.py; the
+    keypoint head is not built).  In training the mask head reads the box head's plan, so it adds no host read to the box head's."""
 
-    def forward(self, features, proposals, targets=None):
-        x, detections, losses = self.box(features, proposals, targets)
-        return x, detections, dict(losses)
+    def forward(self, features, proposals, targets=None, sampled=None):
+        """sampled: the box head's ``sampled=`` override (ROIBoxHead.forward), training only"""
+        x, detections, losses = self.box(features, proposals, targets, **({} if sampled is None else {"sampled": sampled}))
+        losses = dict(losses)
+        if "mask" in self:
+            x, detections, loss_mask = self.mask(features, detections, targets,
+                                                 plan=self.box.loss_evaluator if self.training else None)
+            losses.update(loss_mask)
+        return x, detections, losses

@@ -2068,6 +2068,174 @@ def roi_box_decode(class_logits, box_regression, rois, image_hw, weights=(10., 1
     return scores, boxes, cand
 
 
+# ----------------------------------------------------------------------------- Mask R-CNN mask head (csrc/roi_mask.hip)
+# Ground-truth masks of a batch: masks uint8 [sum G_n h_n w_n] flat, moff int64 [N + 1], mhw int32 [N, 2] (h, w), on the device.
+def _roi_mask_vector(who, t, dtype, n, name):
+    if t.dtype != dtype or tuple(t.shape) != (n,) or not t.is_contiguous():
+        raise ValueError("%s: %s must be contiguous %s [%d], got %r %s" % (who, name, dtype, n, tuple(t.shape), t.dtype))
+
+
+def _roi_mask_rois(who, rois, n=None):
+    if rois.dtype != torch.float32 or rois.dim() != 2 or rois.shape[1] != 5 or not rois.is_contiguous() \
+            or (n is not None and rois.shape[0] != n):
+        raise ValueError("%s: rois must be contiguous fp32 [%s, 5], got %r %s" % (who, "R" if n is None else n, tuple(rois.shape), rois.dtype))
+    return int(rois.shape[0])
+
+
+def _roi_mask_size(who, M):
+    if not 1 <= int(M) <= 1024:
+        raise ValueError("%s: mask size M %r outside 1..1024" % (who, M))
+    return int(M)
+
+
+def _roi_mask_logits(who, logits, n, M, C):
+    """the conv output rows [n M M, Cs] holding C classes in their first columns -> C"""
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.shape[0] != n * M * M:
+        raise ValueError("%s: logits must be fp32 rows [%d * %d * %d, Cs], got %r %s" % (who, n, M, M, tuple(logits.shape), logits.dtype))
+    C = int(logits.shape[1] if C is None else C)
+    if not 1 <= C <= logits.shape[1]:
+        raise ValueError("%s: C %r classes in rows of %d columns" % (who, C, logits.shape[1]))
+    if n * M * M >= 2 ** 31:
+        raise ValueError("%s: 2^31 mask elements or more" % who)
+    if n > 0 and (logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]):
+        raise ValueError("%s: logits must have contiguous rows" % who)
+    return C
+
+
+def roi_mask_positives(labels, rois, src, matched, N, P, Rp):
+    """The positive rows of the box head's sampled plan in one launch (reference mask_head.py:14-32 keep_only_positive_boxes and
+    mask_head/loss.py:54-68, whose re-match gives the box plan's ``matched``): labels int32 [R], rois [R, 5], src int32 [R] of
+    ops.roi_box_gather, matched int32 [N * P] of ops.roi_box_match, Rp the number of rows with label > 0 (known to the caller from
+    the plan's per-image counts) -> pos_rows int32 [Rp], pos_rois [Rp, 5], pos_labels int32 [Rp], pos_gt int32 [Rp], in row order."""
+    R = _roi_mask_rois("roi_mask_positives", rois)
+    _roi_mask_vector("roi_mask_positives", labels, torch.int32, R, "labels")
+    _roi_mask_vector("roi_mask_positives", src, torch.int32, R, "src")
+    N, P, Rp = int(N), int(P), int(Rp)
+    if N < 1 or P < 1 or N * P >= 2 ** 31:
+        raise ValueError("roi_mask_positives: N %r, P %r: at least 1, N * P below 2^31" % (N, P))
+    _roi_mask_vector("roi_mask_positives", matched, torch.int32, N * P, "matched")
+    if not 0 <= Rp <= R:
+        raise ValueError("roi_mask_positives: Rp %r outside 0..R = %d" % (Rp, R))
+    _chk(labels, rois, src, matched)
+    dev = rois.device
+    pos_rows = torch.empty((Rp,), dtype=torch.int32, device=dev)
+    pos_rois = torch.empty((Rp, 5), dtype=torch.float32, device=dev)
+    pos_labels = torch.empty((Rp,), dtype=torch.int32, device=dev)
+    pos_gt = torch.empty((Rp,), dtype=torch.int32, device=dev)
+    call("scan_roi_mask_positives", _ptr(labels), _ptr(rois), _ptr(src), _ptr(matched), N, P, R, Rp, _ptr(pos_rows), _ptr(pos_rois),
+         _ptr(pos_labels), _ptr(pos_gt), _stream())
+    return pos_rows, pos_rois, pos_labels, pos_gt
+
+
+def roi_mask_targets(pos_rois, pos_gt, masks, moff, mhw, M):
+    """project_masks_on_boxes (reference mask_head/loss.py:11-42: BinaryMaskList.crop + resize((M, M)) + get_mask_tensor per
+    positive proposal) in one launch: pos_rois [Rp, 5], pos_gt int32 [Rp], the batch's masks (uint8 flat, moff int64 [N + 1], mhw
+    int32 [N, 2]) -> targets fp32 [Rp, M, M] of 0 / 1 by the integer rule of include/scan_hip.h."""
+    Rp = _roi_mask_rois("roi_mask_targets", pos_rois)
+    _roi_mask_vector("roi_mask_targets", pos_gt, torch.int32, Rp, "pos_gt")
+    M = _roi_mask_size("roi_mask_targets", M)
+    if masks.dtype != torch.uint8 or masks.dim() != 1 or not masks.is_contiguous():
+        raise ValueError("roi_mask_targets: masks must be a flat contiguous uint8 buffer, got %r %s" % (tuple(masks.shape), masks.dtype))
+    if mhw.dtype != torch.int32 or mhw.dim() != 2 or mhw.shape[0] < 1 or mhw.shape[1] != 2 or not mhw.is_contiguous():
+        raise ValueError("roi_mask_targets: mhw must be contiguous int32 [N >= 1, 2] (height, width), got %r %s" % (tuple(mhw.shape), mhw.dtype))
+    N = int(mhw.shape[0])
+    _roi_mask_vector("roi_mask_targets", moff, torch.int64, N + 1, "moff")
+    _chk(pos_rois, pos_gt, masks, moff, mhw)
+    out = torch.empty((Rp, M, M), dtype=torch.float32, device=pos_rois.device)
+    call("scan_roi_mask_targets", _ptr(pos_rois), _ptr(pos_gt), Rp, _ptr(masks), int(masks.numel()), _ptr(moff), _ptr(mhw), N, M,
+         _ptr(out), _stream())
+    return out
+
+
+# scan_roi_mask_loss_forward is ONE workgroup (no float atomics, no cleared output, one launch): about 1.1 us per 1024 elements,
+# a single CU's load rate -- 440 us at 401,408 elements against 25 us for the slots + ordered sum, and level with it (9.6 against
+# 8.5 us) at 7,840 elements (profiles/r24_roi_mask.txt).  Up to 8 passes of the workgroup it saves the host one launch at no
+# device time; past that the two-launch form is used whatever the mode.
+ROI_MASK_LOSS_ONE_LAUNCH_ELEMS = 8192
+
+
+class _RoiMaskLoss(torch.autograd.Function):
+    """the mean over Rp M M elements of the binary cross-entropy of the label's column of the logits rows, read in place"""
+
+    @staticmethod
+    def forward(ctx, logits, dims, labels, targets):
+        Rp, M, C = dims
+        out = logits.new_empty((1,))
+        args = (_ptr(logits), _pitch(logits), Rp, M, C, _ptr(labels), _ptr(targets))
+        if Rp * M * M > ROI_MASK_LOSS_ONE_LAUNCH_ELEMS:
+            call("scan_roi_mask_loss_forward_ordered", *args, _ptr(out),
+                 _ptr(_partials("scan_roi_mask_loss_ordered_ws_floats", logits, Rp * M * M)), _stream())
+        else:
+            _call_reduction("scan_roi_mask_loss", "_forward", logits, (Rp * M * M,), *args, _ptr(out))
+        ctx.save_for_backward(logits, labels, targets)
+        ctx.args, ctx.count = args, Rp * M * M
+        return out[0] / (Rp * M * M)
+
+    @staticmethod
+    def backward(ctx, g):
+        logits = ctx.saved_tensors[0]
+        gn = (g / ctx.count).reshape(1).contiguous()
+        d = torch.empty(logits.shape, dtype=torch.float32, device=logits.device)
+        call("scan_roi_mask_loss_backward", *ctx.args, _ptr(gn), _ptr(d), d.shape[1], _stream())
+        return d, None, None, None
+
+
+def roi_mask_loss(logits, labels, targets, C=None):
+    """F.binary_cross_entropy_with_logits(mask_logits[pos, labels_pos], targets), mean reduction (reference mask_head/loss.py:
+    124-127): logits the conv output rows [Rp M M, Cs] (C classes in the first columns; read in place), labels int32 [Rp],
+    targets fp32 [Rp, M, M] -> a scalar.  Rp = 0: a zero that still reaches the logits (the reference's mask_logits.sum() * 0)."""
+    if targets.dim() != 3 or targets.shape[1] != targets.shape[2] or targets.dtype != torch.float32 or not targets.is_contiguous():
+        raise ValueError("roi_mask_loss: targets must be contiguous fp32 [Rp, M, M], got %r %s" % (tuple(targets.shape), targets.dtype))
+    Rp = int(targets.shape[0])
+    M = _roi_mask_size("roi_mask_loss", targets.shape[1])
+    C = _roi_mask_logits("roi_mask_loss", logits, Rp, M, C)
+    _roi_mask_vector("roi_mask_loss", labels, torch.int32, Rp, "labels")
+    _chk(labels, targets)
+    if Rp == 0:
+        if not logits.is_cuda:
+            raise RuntimeError("scan_amd ops run only on the GPU (HIP) -- got a %s tensor; no CPU fallback" % logits.device)
+        return logits.sum() * 0
+    return _RoiMaskLoss.apply(logits, (Rp, M, C), labels, targets)
+
+
+def roi_mask_prob(logits, labels, M, C=None):
+    """MaskPostProcessor.forward's sigmoid of the predicted class's channel (reference mask_head/inference.py:41-49) in one
+    launch: logits rows [K M M, Cs], labels int32 / int64 [K] -> [K, 1, M, M]"""
+    M = _roi_mask_size("roi_mask_prob", M)
+    if labels.dim() != 1 or labels.dtype not in (torch.int32, torch.int64):
+        raise ValueError("roi_mask_prob: labels must be int32 or int64 [K], got %r %s" % (tuple(labels.shape), labels.dtype))
+    K = int(labels.shape[0])
+    C = _roi_mask_logits("roi_mask_prob", logits, K, M, C)
+    _chk(labels)
+    labels = labels.to(torch.int32).contiguous()
+    out = torch.empty((K, 1, M, M), dtype=torch.float32, device=logits.device)
+    call("scan_roi_mask_prob", _ptr(logits), _pitch(logits), K, M, C, _ptr(labels), _ptr(out), _stream())
+    return out
+
+
+def roi_mask_paste(prob, boxes, image_hw, thresh=0.5):
+    """Masker.forward_single_image with padding 1 (reference mask_head/inference.py:91-194) in one launch: prob [K, 1, M, M],
+    boxes fp32 [K, 4] xyxy of ONE image of size image_hw = (H, W) -> uint8 [K, 1, H, W]; K = 0 gives an empty [0, 1, M, M] as
+    the reference does.  thresh < 0 (the reference's mask * 255 debugging mode) is refused."""
+    if not float(thresh) >= 0:
+        raise ValueError("roi_mask_paste: thresh %r below 0 (the reference's mask * 255 debugging mode) is not built" % (thresh,))
+    if prob.dim() != 4 or prob.shape[1] != 1 or prob.shape[2] != prob.shape[3] or prob.dtype != torch.float32 or not prob.is_contiguous():
+        raise ValueError("roi_mask_paste: prob must be contiguous fp32 [K, 1, M, M], got %r %s" % (tuple(prob.shape), prob.dtype))
+    K = int(prob.shape[0])
+    M = _roi_mask_size("roi_mask_paste", prob.shape[2])
+    if boxes.dtype != torch.float32 or tuple(boxes.shape) != (K, 4) or not boxes.is_contiguous():
+        raise ValueError("roi_mask_paste: boxes must be contiguous fp32 [K, 4] = [%d, 4], got %r %s" % (K, tuple(boxes.shape), boxes.dtype))
+    H, W = (int(v) for v in image_hw)
+    if H < 1 or W < 1:
+        raise ValueError("roi_mask_paste: image_hw %r: a positive height and width" % (image_hw,))
+    _chk(prob, boxes)
+    if K == 0:
+        return prob.new_empty((0, 1, M, M))
+    out = torch.empty((K, 1, H, W), dtype=torch.uint8, device=prob.device)
+    call("scan_roi_mask_paste", _ptr(prob), _ptr(boxes), K, M, H, W, float(thresh), _ptr(out), _stream())
+    return out
+
+
 class _BceLogitsMean(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, targets):

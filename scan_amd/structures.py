@@ -177,6 +177,118 @@ class BoxList:
                                                                                   self.mode)
 
 
+# ----------------------------------------------------------------------------- SegmentationMask (binary-mask mode)
+class BinaryMaskList:
+    """The binary masks of ONE image's objects (reference structures/segmentation_mask.py:33-172): masks uint8 [n, H, W],
+    size = (image width, image height).  Plain torch ops: the head's targets are made on the device from the masks themselves
+    (ops.roi_mask_targets), not through crop / resize."""
+
+    def __init__(self, masks, size):
+        if isinstance(masks, BinaryMaskList):
+            masks = masks.masks
+        elif isinstance(masks, (list, tuple)):
+            if not masks or not all(isinstance(m, torch.Tensor) for m in masks):
+                raise ValueError("BinaryMaskList: a list of masks must hold [H, W] tensors (RLE dicts are not built)")
+            masks = torch.stack(list(masks), 0)
+        elif not isinstance(masks, torch.Tensor):
+            raise ValueError("BinaryMaskList: masks must be a tensor, a list of tensors or a BinaryMaskList, got %s" % type(masks))
+        masks = masks.clone()
+        if masks.dim() == 2:
+            masks = masks[None]
+        size = tuple(int(s) for s in size)
+        if masks.dim() != 3 or tuple(masks.shape[1:]) != (size[1], size[0]):
+            raise ValueError("BinaryMaskList: masks %r for an image of (width, height) %r" % (tuple(masks.shape), size))
+        self.masks, self.size = masks, size
+
+    def transpose(self, method):
+        if method not in (FLIP_LEFT_RIGHT, FLIP_TOP_BOTTOM):
+            raise NotImplementedError("Only FLIP_LEFT_RIGHT and FLIP_TOP_BOTTOM implemented")
+        return BinaryMaskList(self.masks.flip(1 if method == FLIP_TOP_BOTTOM else 2), self.size)
+
+    def crop(self, box):
+        """box xyxy: every coordinate rounded half-to-even (Python's round), the minima clamped into the image, the maxima to its
+        far edge, at least one pixel each way"""
+        width, height = self.size
+        xmin, ymin, xmax, ymax = [round(float(b)) for b in box]
+        xmin, ymin = min(max(xmin, 0), width - 1), min(max(ymin, 0), height - 1)
+        xmax, ymax = min(max(xmax, 0), width), min(max(ymax, 0), height)
+        xmax, ymax = max(xmax, xmin + 1), max(ymax, ymin + 1)
+        return BinaryMaskList(self.masks[:, ymin:ymax, xmin:xmax], (xmax - xmin, ymax - ymin))
+
+    def resize(self, size):
+        """bilinear (align_corners=False) in fp32, cast back to the masks' dtype as the reference does"""
+        width, height = (int(size), int(size)) if isinstance(size, (int, float)) else (int(s) for s in size)
+        if width < 1 or height < 1:
+            raise ValueError("BinaryMaskList.resize: size %r" % (size,))
+        m = torch.nn.functional.interpolate(self.masks[None].float(), size=(height, width), mode="bilinear", align_corners=False)
+        return BinaryMaskList(m[0].type_as(self.masks), (width, height))
+
+    def to(self, *args, **kwargs):
+        return self
+
+    def __len__(self):
+        return self.masks.shape[0]
+
+    def __getitem__(self, index):
+        if isinstance(index, torch.Tensor):
+            index = index.to(self.masks.device)
+        return BinaryMaskList(self.masks[index], self.size)
+
+    def __iter__(self):
+        return iter(self.masks)
+
+    def __repr__(self):
+        return "BinaryMaskList(num_instances=%d, image_width=%d, image_height=%d)" % (len(self), self.size[0], self.size[1])
+
+
+class SegmentationMask:
+    """reference structures/segmentation_mask.py:437-533 in mode "mask" (the ``masks`` field of a target BoxList).  Polygon
+    mode rasterises through pycocotools and is not built: mode="poly" raises, so ``mode`` must be given."""
+
+    def __init__(self, instances, size, mode="poly"):
+        if mode != "mask":
+            raise ValueError("SegmentationMask: mode %r is not built (only mode='mask', binary masks [n, H, W])" % (mode,))
+        if isinstance(instances, SegmentationMask):
+            instances = instances.instances
+        self.instances = BinaryMaskList(instances, size)
+        self.mode, self.size = mode, self.instances.size
+
+    def transpose(self, method):
+        return SegmentationMask(self.instances.transpose(method), self.size, self.mode)
+
+    def crop(self, box):
+        c = self.instances.crop(box)
+        return SegmentationMask(c, c.size, self.mode)
+
+    def resize(self, size, *args, **kwargs):
+        r = self.instances.resize(size)
+        return SegmentationMask(r, r.size, self.mode)
+
+    def to(self, *args, **kwargs):
+        return self
+
+    def convert(self, mode):
+        if mode != "mask":
+            raise ValueError("SegmentationMask.convert: mode %r is not built (only 'mask')" % (mode,))
+        return self
+
+    def get_mask_tensor(self):
+        return self.instances.masks.squeeze(0)
+
+    def __len__(self):
+        return len(self.instances)
+
+    def __getitem__(self, item):
+        return SegmentationMask(self.instances[item], self.size, self.mode)
+
+    def __iter__(self):
+        return (self[i] for i in range(len(self)))
+
+    def __repr__(self):
+        return "SegmentationMask(num_instances=%d, image_width=%d, image_height=%d, mode=%s)" % (len(self), self.size[0],
+                                                                                                 self.size[1], self.mode)
+
+
 def cat_boxlist(bboxes):
     """list of BoxList of one image size, mode and field set -> one BoxList (reference structures/boxlist_ops.py:127-153)"""
     if not isinstance(bboxes, (list, tuple)) or not bboxes or not all(isinstance(b, BoxList) for b in bboxes):
